@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +26,8 @@ def _bench(*flags):
     return json.loads(out.stdout.strip().splitlines()[-1])
 
 
-def test_bench_line_fields_and_graph_replay(dev):
-    eager = _bench()
+def test_bench_line_fields_and_graph_replay(dev, tmp_path):
+    eager = _bench('--dump-outputs', str(tmp_path / 'eager'))
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
                 'data', 'config', 'roofline'):
         assert key in eager, key
@@ -42,9 +43,20 @@ def test_bench_line_fields_and_graph_replay(dev):
     assert exact['dtype'] == 'f32' and list(exact)[-1] == 'split_precision' and exact['roofline']['peak'] == 157.3
     assert exact['parity']['ok'] and exact['parity_max_rel'] <= 1e-5
     assert eager['parity']['ok'] and eager['parity_max_rel'] <= 1e-5          # in-run parity vs the fp64 subset oracle (north_star tolerance)
-    graph = _bench('--graph')
+    graph = _bench('--graph', '--dump-outputs', str(tmp_path / 'graph'))
     assert graph['config']['hip_graph'] is True
     assert graph['config']['loss'] == eager['config']['loss']                 # same kernels, same order: bit-identical loss
+    # --dump-outputs: what the last timed step returned, within 64 MB; the same inputs and the same sampled elements in both runs
+    names = sorted(p.name for p in (tmp_path / 'eager').iterdir())
+    assert {'loss.npy', 'n_pair.npy', 'scores.npy', 'dx.npy', 'grad.head.kernel.npy', 'grad.head.bias.npy'} <= set(names) and len(names) == 4 + 17
+    assert sum(os.path.getsize(tmp_path / 'eager' / n) for n in names) <= 64e6
+    assert sorted(p.name for p in (tmp_path / 'graph').iterdir()) == names
+    assert np.load(tmp_path / 'eager' / 'scores.npy').shape == (65536,) and 0 < np.load(tmp_path / 'eager' / 'dx.npy').size < 65536 * 1024
+    assert float(np.load(tmp_path / 'eager' / 'n_pair.npy').reshape(-1)[0]) > 0
+    for n in names:
+        a, b = np.load(tmp_path / 'eager' / n), np.load(tmp_path / 'graph' / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        np.testing.assert_allclose(b, a, rtol=1e-5, atol=1e-5 * float(np.abs(a).max()), err_msg=n)
 
 
 def test_self_launch_one_rank_force_dist_is_self_verifying(dev):
@@ -111,14 +123,15 @@ def test_two_ranks_share_one_gpu_over_gloo_and_verify_across_ranks(dev):
 
 
 @pytest.mark.parametrize('config', ['c4', 'c5'])
-def test_model_configs_two_ranks_over_gloo_verify_across_ranks(dev, config):
+def test_model_configs_two_ranks_over_gloo_verify_across_ranks(dev, config, tmp_path):
     """`bench.py --config c4 | c5` (VERDICT round 5, row e''): the data-parallel MODEL steps of BASELINE.json's configs[3] / configs[4] -- CIN || FM -> head ->
     pairwise; PLE -> 3 heads -> listwise -- with two real ranks (two processes on GPU 0 over gloo), every rank its own whole groups / lists, the gradients
     all-reduced bucket by bucket from autograd's post-accumulate hooks (dp.OverlappedGradientReducer).  The line's gate: the reduced loss against the
     oracle's loss stage on the gathered batch, outputs and d loss / d x per rank and every all-reduced weight gradient against the sum of the ranks' fp64
     oracles.  /root/reference/rec_now/layers/cin_layer.py:72-122, ple_layer.py:295-321, rec_block/listwise_loss_from_batch.py:89-173."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', config, '--gpus', '2', '--backend', 'gloo', '--oversubscribe',
-                          '--rows', '2048', '--steps', '2', '--warmup', '1'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=_clean_env())
+                          '--rows', '2048', '--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=900,
+                         cwd=ROOT, env=_clean_env())
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config',
@@ -136,3 +149,9 @@ def test_model_configs_two_ranks_over_gloo_verify_across_ranks(dev, config):
         assert par['listwise_stage_oracle']['lists_gpu'] == par['listwise_stage_oracle']['lists_oracle'] > 0
         assert len([k for k in full if k.startswith('ple.')]) >= 4 * 2 * 2 * 2 + 4 and 'head.kernel' in full
     assert line['roofline']['bound'] == 'mfma' and len(line['comm']['buckets']) >= 1
+    # --dump-outputs (rank 0): loss, count, outputs, d loss / d x and a gradient per weight, within 64 MB
+    names = {p.name for p in tmp_path.iterdir()}
+    assert {'loss.npy', 'count.npy', 'dx.npy', 'grad.head.kernel.npy', ('scores.npy' if config == 'c4' else 'logits.npy')} <= names
+    assert len([n for n in names if n.startswith('grad.')]) == len(full) - 3                    # every gradient the gate holds (besides loss, outputs, dx)
+    assert sum(os.path.getsize(tmp_path / n) for n in names) <= 64e6
+    assert all(np.load(tmp_path / n).dtype in (np.float32, np.float64) for n in names)

@@ -6,8 +6,6 @@ import sys
 import time
 
 VAR = sys.argv[1] if len(sys.argv) > 1 else ''
-if 'q' in VAR:
-    os.environ['GPU_MAX_HW_QUEUES'] = '8'
 if 'c' in VAR:
     os.environ['DEBUG_CLR_GRAPH_PACKET_CAPTURE'] = '0'
 
