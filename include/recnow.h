@@ -315,6 +315,9 @@ int recnow_gemm(const recnow_gemm_desc* desc_host, void* ws, size_t ws_bytes, vo
  *   0 (default) exact fp32 MFMA -- an fp32 fma chain, what TF's fp32 matmul computes up to summation order;
  *   1 "bf16x3": every fp32 operand element split into three bf16 pieces, six bf16 MFMA terms per product, fp32 accumulation:
  *     relative error of a product <= 2^-25, results within the 1e-5 parity bound but NOT bit-identical to mode 0 (opt-in).
+ *     Finite operands up to FLT_MAX give finite products (piece 1 saturates at +-bf16_max, pieces 2 and 3 carry the rest).  Non-finite
+ *     operands give non-finite outputs where mode 0 does, but not always of the same class: an inf may come out as NaN.  Operands below
+ *     2^-100, where pieces 2 and 3 become subnormal, are not verified.
  * Also read once from the environment (RECNOW_GEMM_PRECISION=bf16x3).  Shapes without a split kernel run mode 0 regardless. */
 int recnow_set_gemm_precision(int mode);
 int recnow_get_gemm_precision(void);

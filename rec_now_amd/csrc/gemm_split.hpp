@@ -18,9 +18,13 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define SPL_BX_RING 4
 #define SPL_LDS (SPL_BX_OFF + SPL_BX_RING * SPL_BK * 4 * 4)
 
-// (u, v) -> three packed bf16 pairs (low half = piece of u, high half = piece of v)
+// (u, v) -> three packed bf16 pairs (low half = piece of u, high half = piece of v).  Piece 1 is taken from the input clamped to
+// +-bf16_max (v_med3_f32): a finite |x| >= 3.3961e38 would otherwise round to inf and turn pieces 2 and 3 into -inf / NaN; clamped, the
+// residual (<= 2^121) stays finite and pieces 2 and 3 carry it.  The residuals are formed from the unclamped input, so an inf or NaN
+// still yields a non-finite piece (inf may come out as NaN).
+#define SPL_BF16_MAX 3.38953139e38f                     // 0x7f7f0000: the largest finite bf16
 __device__ __forceinline__ void spl_split2(float u, float v, unsigned& p1, unsigned& p2, unsigned& p3) {
-    bf16x2 h = {(__bf16)u, (__bf16)v};
+    bf16x2 h = {(__bf16)__builtin_amdgcn_fmed3f(u, -SPL_BF16_MAX, SPL_BF16_MAX), (__bf16)__builtin_amdgcn_fmed3f(v, -SPL_BF16_MAX, SPL_BF16_MAX)};
     p1 = __builtin_bit_cast(unsigned, h);
     f32x2 r = {u - __builtin_bit_cast(float, p1 << 16), v - __builtin_bit_cast(float, p1 & 0xffff0000u)};
     bf16x2 g = {(__bf16)r.x, (__bf16)r.y};

@@ -94,7 +94,7 @@ def test_split_product_at_step_size(dev, split_mode, ta, tb, mul, M, K):
 
 
 def test_split_pieces_cover_extreme_magnitudes(dev, split_mode):
-    """Operands spanning 1e-30 .. 1e30 (bf16 keeps the fp32 exponent range: no scaling step): relative error per output
+    """Rows scaled by 1e-15 .. 1e15 (bf16 keeps the fp32 exponent range: no scaling step): relative error per output
     against its own magnitude, rows scaled independently."""
     from rec_now_amd import _lib
     rng = np.random.default_rng(3)
