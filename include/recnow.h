@@ -656,6 +656,28 @@ int recnow_embed_scatter_rows(const float* drows, const int64_t* row_ids, int64_
                               const int32_t* n_seg, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * StarDenseLayer / StackedDenseLayer (ABI 7): rec_now/layers/star_dense_layer.py:118-163, stacked_dense_layer.py:116-155.
+ * A Dense layer personalised per row by K <= 4 parameter rows.  params_host / dparams_host: HOST arrays of K DEVICE pointers to
+ * contiguous (B, R) fp32 tensors, R = D*U + U: the first D*U entries of a row are a kernel [d][u], the last U a bias.
+ *   RECNOW_STAR_MUL: Weff[b] = kernel * prod_k P_k[b][:DU]           beff[b] = sum_k P_k[b][DU:] + bias - K
+ *   RECNOW_STAR_ADD: Weff[b] = kernel + weight * sum_k P_k[b][:DU]   beff[b] = bias + weight * sum_k P_k[b][DU:]
+ *   y[b] = act(x[b] . Weff[b] + beff[b]);  x (B,D), kernel (D,U), bias (U) or NULL, y (B,U).
+ * No (B,D,U) tensor is formed: each P_k element is read once.  Backward, from y (act' through the output) and dy:
+ *   dx (may be NULL); dparams_host (may be NULL, and so may each entry: that dP_k is not written); dkernel, dbias (may be NULL).
+ *   dkernel / dbias are sums over fixed batch chunks in a fixed order (ws: recnow_star_dense_workspace_bytes, needed only
+ *   when one of them is requested; it is bounded by the backward's workgroups x R floats, independent of B).
+ *   K > 4: RECNOW_EUNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define RECNOW_STAR_MUL 0
+#define RECNOW_STAR_ADD 1
+size_t recnow_star_dense_workspace_bytes(int64_t B, int D, int U);
+int recnow_star_dense_fwd(const float* x, const float* const* params_host, int K, int mode, float weight, const float* kernel,
+                          const float* bias, int64_t B, int D, int U, int act, float* y, void* stream);
+int recnow_star_dense_bwd(const float* x, const float* const* params_host, int K, int mode, float weight, const float* kernel,
+                          const float* y, const float* dy, int64_t B, int D, int U, int act, float* dx, float* const* dparams_host,
+                          float* dkernel, float* dbias, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

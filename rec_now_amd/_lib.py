@@ -101,6 +101,9 @@ SIGNATURES = {
     'recnow_embed_rows_bwd_workspace_bytes': (_Z, [_L, _I]),
     'recnow_embed_rows_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     'recnow_embed_scatter_rows': (_I, [_P, _P, _L, _I, _L, _P, _P, _P]),
+    'recnow_star_dense_workspace_bytes': (_Z, [_L, _I, _I]),
+    'recnow_star_dense_fwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _I, _I, _I, _P, _P]),
+    'recnow_star_dense_bwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -133,7 +136,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 6      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 7      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -288,3 +288,49 @@ class CINFunction(torch.autograd.Function):
                   1 if output_input else 0, 1 if sum_channel else 0, _lib.ptr(demb), _host_ptr_array(dws), _lib.ptr(ws),
                   ws.numel(), _lib.stream())
         return (demb, None, None, None, None, None) + tuple(dws)
+
+
+# ---- StarDense / StackedDense -----------------------------------------------------------------------------------
+STAR_MUL, STAR_ADD = 0, 1      # RECNOW_STAR_MUL / RECNOW_STAR_ADD of include/recnow.h
+
+
+class StarDenseFunction(torch.autograd.Function):
+    """y = act(x[b] . Weff[b] + beff[b]) with the kernel and bias personalised per row by the K parameter rows P_k (B, D*U+U):
+    STAR_MUL: Weff = kernel * prod_k P_k[:, :DU], beff = sum_k P_k[:, DU:] + bias - K;  STAR_ADD: Weff = kernel + weight * sum_k P_k[:, :DU],
+    beff = bias + weight * sum_k P_k[:, DU:].  x (B,D), kernel (D,U), bias (U,) or None; no (B,D,U) tensor is formed."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, mode, weight, act_code, *params):
+        x = _lib.f32c(x, 'inputs')
+        kernel = _lib.f32c(kernel, 'kernel')
+        bias = _lib.f32c(bias, 'bias') if bias is not None else None
+        ps = [_lib.f32c(p, 'parameter row') for p in params]
+        B, D = x.shape
+        U = kernel.shape[1]
+        y = torch.empty((B, U), dtype=torch.float32, device=x.device)
+        _lib.call('recnow_star_dense_fwd', _lib.ptr(x), _host_ptr_array(ps), len(ps), mode, float(weight), _lib.ptr(kernel), _lib.ptr(bias),
+                  B, D, U, act_code, _lib.ptr(y), _lib.stream())
+        ctx.save_for_backward(x, kernel, y, *ps)
+        ctx.meta = (B, D, U, mode, float(weight), act_code, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kernel, y, *ps = ctx.saved_tensors
+        B, D, U, mode, weight, act_code, has_bias = ctx.meta
+        dy = _lib.f32c(dy, 'grad')
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None
+        dk = torch.empty_like(kernel) if need[1] else None
+        db = torch.empty((U,), dtype=torch.float32, device=x.device) if has_bias and need[2] else None
+        dps = [torch.empty_like(p) if need[6 + k] else None for k, p in enumerate(ps)]       # an unrequested dP_k is never written
+        lib = _lib.load()
+        ws = _lib.workspace(lib.recnow_star_dense_workspace_bytes(B, D, U) if (dk is not None or db is not None) else 0, x.device)
+        dptrs = (ctypes.c_void_p * len(ps))(*[d.data_ptr() if d is not None else None for d in dps])
+        _lib.call('recnow_star_dense_bwd', _lib.ptr(x), _host_ptr_array(ps), len(ps), mode, weight, _lib.ptr(kernel), _lib.ptr(y), _lib.ptr(dy),
+                  B, D, U, act_code, _lib.ptr(dx), dptrs, _lib.ptr(dk), _lib.ptr(db), _lib.ptr(ws), ws.numel(), _lib.stream())
+        return (dx, dk, db, None, None, None) + tuple(dps)
+
+
+def star_dense(x, kernel, bias, params, mode, weight, act_code):
+    return StarDenseFunction.apply(x, kernel, bias, mode, weight, act_code, *params)

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,ipnn,senet,attn,focal,embed]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,ipnn,senet,attn,focal,embed]"""
 import os
 import sys
 
@@ -287,8 +287,77 @@ def embed():
           % (B, C, T, D, V, ms_f, (pooled * 4 * D + 16.0 * B * C + 4.0 * B * T * D) / ms_f / 1e6, ms, B * C / ms / 1e3))
 
 
+def star_ref_eager(mode, x, kernel, bias, ps, w):
+    """The reference algorithm (star_dense_layer.py:118-163, stacked_dense_layer.py:116-155) in torch eager: a (B, D, U) kernel."""
+    B, D = x.shape
+    U = kernel.shape[1]
+    ks = [p[:, :D * U].view(B, D, U) for p in ps]
+    bs = [p[:, D * U:] for p in ps]
+    if mode == 'star':
+        kf = kernel.unsqueeze(0)
+        for k in ks:
+            kf = kf * k
+        bf = sum(bs) + bias - len(ps)
+    else:
+        kf = kernel.unsqueeze(0) + w * sum(ks)
+        bf = bias + w * sum(bs)
+    return torch.bmm(x.unsqueeze(1), kf).squeeze(1) + bf
+
+
+def star(mode):
+    """StarDense / StackedDense at B = 8192, D = 256, U = 128, K = 1 and 2: forward and backward time each, as GB/s of algorithmic bytes
+    (forward: K*B*(DU+U)*4 + x + y; backward: the P_k read and the dP_k written, x, dx, y, dy), and the speedup and forward peak-memory
+    ratio over the reference algorithm in torch eager."""
+    from rec_now_amd.layers.stacked_dense_layer import StackedDenseLayer
+    from rec_now_amd.layers.star_dense_layer import StarDenseLayer
+    B, D, U = 8192, 256, 128
+    R = D * U + U
+    for K in (1, 2):
+        x = torch.rand(B, D, device=dev, requires_grad=True)
+        ps = [(torch.rand(B, R, device=dev) + 0.5).requires_grad_(True) for _ in range(K)]
+        gy = torch.randn(B, U, device=dev)
+        layer = (StarDenseLayer if mode == 'star' else StackedDenseLayer)(U)
+        run = (lambda: layer(x, ps)) if mode == 'star' else (lambda: layer(x, ps, resnet_weight=0.5))
+        run()
+
+        def ref():
+            return star_ref_eager(mode, x, layer.kernel, layer.bias, ps, 0.5)
+
+        def peak_rise(fn):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            y = fn()
+            torch.cuda.synchronize()
+            del y
+            return torch.cuda.max_memory_allocated() - base
+
+        def bwd_of(fn):
+            y = fn()
+
+            def step():
+                x.grad = None
+                layer.zero_grad(set_to_none=True)
+                for p in ps:
+                    p.grad = None
+                y.backward(gy, retain_graph=True)
+            return step
+
+        fwd_bytes = 4.0 * (K * B * R + B * D + B * U)
+        bwd_bytes = 4.0 * (2 * K * B * R + 2 * B * D + 2 * B * U)
+        ms_f, ms_b = timeit(run), timeit(bwd_of(run))
+        rf, rb = timeit(ref), timeit(bwd_of(ref))
+        mem, rmem = peak_rise(run), peak_rise(ref)
+        print('%s K=%d B=%d D=%d U=%d : fwd %.3f ms %.0f GB/s, bwd %.3f ms %.0f GB/s (algorithmic) | reference in torch eager: fwd %.3f ms, '
+              'bwd %.3f ms -> speedup fwd %.1fx bwd %.1fx | forward peak rise %.1f MB vs %.1f MB (%.0fx less)'
+              % ('StarDenseLayer' if mode == 'star' else 'StackedDenseLayer', K, B, D, U, ms_f, fwd_bytes / ms_f / 1e6, ms_b,
+                 bwd_bytes / ms_b / 1e6, rf, rb, rf / ms_f, rb / ms_b, mem / 2 ** 20, rmem / 2 ** 20, rmem / max(mem, 1)))
+        del x, ps, layer
+        torch.cuda.empty_cache()
+
+
 if __name__ == '__main__':
-    which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'ipnn', 'senet', 'attn', 'focal', 'embed']
+    which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'ipnn', 'senet', 'attn', 'focal', 'embed']
     if 'fm' in which:
         fm()
     if 'dcn' in which:
@@ -304,6 +373,9 @@ if __name__ == '__main__':
         cin()
     if 'ple' in which:
         ple()
+    for mode in ('star', 'stacked'):
+        if mode in which:
+            star(mode)
     for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('focal', focal), ('embed', embed)):
         if name in which:
             fn()
