@@ -254,8 +254,7 @@ extern "C" int recnow_cin_bwd(const float* const* weights_host, const float* dou
         // Data gradients.  Fused (csrc/cin_bwd.hip, round 4): T = dX_k W_k is formed ONCE on the matrix cores and both reductions -- over f with x0
         // for dX_{k-1}, over h with X_{k-1} for dx0 -- run on the accumulator tile: one forward-sized product instead of two.  Other shapes
         // (rows not a multiple of 128, H_{k-1} not 64 / 128, ...) keep the two products with generated outer-product operands.
-        static const bool fused_on = []() { const char* e = getenv("RECNOW_CIN_FUSED"); return !e || e[0] != '0'; }();      // A/B switch
-        if (fused_on && rn_cin_bwd_fused_supported(c.M, Hk, Hp, F)) {
+        if (rn_cin_bwd_fused_supported(c.M, Hk, Hp, F)) {
             float* dst = (k == 0) ? dx0t : dXp;
             if (k > 0) seed(dst, Hp, coffs[k - 1]);          // X_{k-1}'s own share of the output gradient, then accumulate
             if ((rc = rn_cin_bwd_fused(dXk, weights_host[k], x0t, Xp, dst, dx0t, c.M, Hk, Hp, F, st))) return rc;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/recnow.h"
 
 #define RN_WAVE 64
@@ -17,6 +18,12 @@
 
 static inline size_t rn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int rn_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// Environment switch `name` as an integer, `def` when it is unset.  INTEGRATION.md lists every switch the library reads.
+static inline int rn_env_int(const char* name, int def) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : def;
+}
 
 // Workspace carving: every carve is 256-B aligned so vector accesses stay aligned.
 // internal flag bits of rn_pair_bpr_onepass (pairwise.hip; set by the step's loss stage, dcnmix.hip; never part of the C ABI's flags):

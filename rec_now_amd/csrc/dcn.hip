@@ -790,8 +790,7 @@ extern "C" int recnow_dcn_fwd(const float* x, const float* kernels, const float*
         RN_LAUNCH_CHECK();
         return RECNOW_OK;
     }
-    static const bool dcn_fast = []() { const char* e = getenv("RECNOW_DCN_FAST"); return !e || e[0] != '0'; }();      // A/B switch
-    if (dcn_fast && cfg.vec == 4 && cfg.tpr == 64 && D == 256 * cfg.nv && B % 4 == 0 && L <= DCN_MAX_L && (size_t)2 * L * D * sizeof(float) <= 48 * 1024) {
+    if (cfg.vec == 4 && cfg.tpr == 64 && D == 256 * cfg.nv && B % 4 == 0 && L <= DCN_MAX_L && (size_t)2 * L * D * sizeof(float) <= 48 * 1024) {
         const int G = dcn_grid(B, 64);
         const size_t shm = (size_t)2 * L * D * sizeof(float);
 #define FWD_FAST(NV_, L_)                                                                                                          \
@@ -861,14 +860,11 @@ extern "C" int recnow_dcn_bwd(const float* x, const float* kernels, const float*
     }
     // D = 1024: a wave per row up to three cross layers (row sums are shuffles, no barrier in the row loop: the two-waves-per-row form
     // waits on a workgroup barrier per layer and row: 176 vs 166 us at B = 65 536, L = 3, both on one resident wave of workgroups); deeper: 2 waves per row, half the
-    // accumulator registers per lane.  RECNOW_DCN_WAVE_ROW=0 is the A/B switch.
-    static const bool wave_row = []() { const char* e = getenv("RECNOW_DCN_WAVE_ROW"); return !e || e[0] != '0'; }();
-    if (csave && cfg.tpr == 64 && cfg.vec == 4 && cfg.nv == 4 && !(wave_row && L <= 3)) cfg = {128, 4, 2};
-    static const bool dcn_fast = []() { const char* e = getenv("RECNOW_DCN_FAST"); return !e || e[0] != '0'; }();      // A/B switch
-    static const bool dcn_resident = []() { const char* e = getenv("RECNOW_DCN_RESIDENT"); return !e || e[0] != '0'; }();      // A/B switch
+    // accumulator registers per lane.
+    if (csave && cfg.tpr == 64 && cfg.vec == 4 && cfg.nv == 4 && L > 3) cfg = {128, 4, 2};
     bool fast_done = false;
     int G = dcn_grid(B, cfg.tpr);
-    if (dcn_fast && csave && cfg.vec == 4 && D == cfg.tpr * 4 * cfg.nv && B % (256 / cfg.tpr) == 0 && (cfg.tpr == 64 || cfg.tpr == 128)) {
+    if (csave && cfg.vec == 4 && D == cfg.tpr * 4 * cfg.nv && B % (256 / cfg.tpr) == 0 && (cfg.tpr == 64 || cfg.tpr == 128)) {
         const size_t shm = ((size_t)(256 / cfg.tpr) * D + (size_t)2 * L * D) * sizeof(float);
 #define BWD_FAST(TPR_, NV_, L_)                                                                                                    \
         if (!fast_done && shm <= 48 * 1024 && cfg.tpr == TPR_ && cfg.nv == NV_ && L == L_) {                                       \
@@ -876,11 +872,11 @@ extern "C" int recnow_dcn_bwd(const float* x, const float* kernels, const float*
                and a 2*L*D slab that the column sum reads back (2048 slabs = 50 MB at D = 1024, L = 3) */                        \
             if (act == RECNOW_ACT_LINEAR) {                                                                                        \
                 static const int occ = dcn_occupancy((const void*)k_dcn_bwd_fast<TPR_, NV_, L_, RECNOW_ACT_LINEAR>, shm);          \
-                if (dcn_resident && G > 256 * occ) G = 256 * occ;                                                                  \
+                if (G > 256 * occ) G = 256 * occ;                                                                                  \
                 hipLaunchKernelGGL((k_dcn_bwd_fast<TPR_, NV_, L_, RECNOW_ACT_LINEAR>), G, 256, shm, st, x, kernels, biases, dy, csave, B, act, dx, part); \
             } else {                                                                                                               \
                 static const int occ = dcn_occupancy((const void*)k_dcn_bwd_fast<TPR_, NV_, L_, -1>, shm);                         \
-                if (dcn_resident && G > 256 * occ) G = 256 * occ;                                                                  \
+                if (G > 256 * occ) G = 256 * occ;                                                                                  \
                 hipLaunchKernelGGL((k_dcn_bwd_fast<TPR_, NV_, L_, -1>), G, 256, shm, st, x, kernels, biases, dy, csave, B, act, dx, part);  \
             }                                                                                                                      \
             fast_done = true;                                                                                                      \

@@ -189,8 +189,7 @@ static inline char* mix_plane(const MixDims& m, const void* saved, int l, int wh
 // by the row-block forward of the same call, which then skips its own pack launch.  Per host thread: a step is enqueued by one thread.
 static thread_local const void* tl_step_tile_packed = nullptr;      // the `saved` buffer whose tile packs are current, or NULL
 static bool mix_tile_on(const MixDims& m, bool maybe = false) {
-    const char* e = getenv("RECNOW_TILE");            // read per call (tests switch the route inside one process)
-    const int mode = e ? atoi(e) : -1;
+    const int mode = rn_env_int("RECNOW_TILE", -1);            // read per call (tests switch the route inside one process)
     if (mode == 0 || !mix_tile_shape(m) || (!maybe && rn_gemm_precision() != 0)) return false;
     return mode == 1 || m.B <= MIX_TILE_MAX_B;
 }
@@ -201,8 +200,7 @@ static bool mix_tile_on(const MixDims& m, bool maybe = false) {
 #define MIX_TILE_SPLIT_MIN_B (1ll << 62)
 static bool mix_tile_split_on(const MixDims& m) {
     if (rn_gemm_precision() != 1 || !mix_tile_shape(m)) return false;
-    const char* e = getenv("RECNOW_TILE_SPLIT");          // read per call (tests switch the route inside one process)
-    const int mode = e ? atoi(e) : -1;
+    const int mode = rn_env_int("RECNOW_TILE_SPLIT", -1);          // read per call (tests switch the route inside one process)
     if (mode == 0) return false;
     return mode == 1 || m.B >= MIX_TILE_SPLIT_MIN_B;
 }
@@ -211,8 +209,7 @@ static bool mix_tile_split_on(const MixDims& m) {
 // ping-pong gradient buffers of the workspace hold g_1 and g_2, i.e. at most three layers (deeper stacks take the product-route backward, which
 // consumes g_l layer by layer).  RECNOW_TILE_BWD=0: the product-route backward behind the row-block forward (A/B switch, read per call).
 static bool mix_tile_bwd_on(const MixDims& m) {
-    const char* e = getenv("RECNOW_TILE_BWD");
-    return m.L <= 3 && !(e && e[0] == '0');
+    return m.L <= 3 && rn_env_int("RECNOW_TILE_BWD", 1) != 0;
 }
 
 // Which weight packs the forward that filled a `saved` buffer left in it, and which route the top piece of the backward took.
@@ -255,7 +252,6 @@ extern "C" size_t recnow_dcn_mix_saved_bytes(int64_t B, int D, int S, int N, int
 // x0 * O_l in their operand loads (RECNOW_OPMODE_MUL), where the extra stream rides under MFMA-bound k-loops (+7 us per launch measured on the
 // products that already do this for x0 * g).  Same values bit for bit: one fp32 multiply either way.  RECNOW_XLESS=0 switches it off (A/B).
 static bool mix_xless(const MixDims& m) {
-    static const bool on = []() { const char* e = getenv("RECNOW_XLESS"); return !e || e[0] != '0'; }();
     // measured (tools/ab_xless.sh, one box): 8192 rows 0.768 -> 0.758 ms, 16 384 rows 1.176 -> 1.156 ms per step; at 65 536 rows NEUTRAL (3.445 vs 3.450 ms:
     // the short-K launches lose 13 us on average, the nine long-K launches with a second operand stream gain 5 us each) -- so only below the batch at
     // which GEMM1 carries the sub-space forward in its epilogue (512 row blocks)
@@ -263,8 +259,8 @@ static bool mix_xless(const MixDims& m) {
     // consumers of x_{l+1} pay 34 + 16 us for their second operand stream: 65 536 rows 2.843 / 2.858 -> 2.825 / 2.811 ms per step (one box, alternating),
     // 0.5 GB less HBM traffic per step.  RECNOW_XLESS=2 forces it for the exact products too, =1 keeps the round-4 rule (A/B).  The rule is read by the FORWARD;
     // a backward follows what its forward did (the MIX_XLESS stamp of `saved`), whatever the precision switch says by then.
-    static const int mode = []() { const char* e = getenv("RECNOW_XLESS"); return e ? atoi(e) : -1; }();
-    return on && m.exact && m.N <= 2 && m.L > 1 && (mode == 2 || m.B / 128 < 512 || (mode != 1 && rn_gemm_precision() == 1));
+    static const int mode = rn_env_int("RECNOW_XLESS", -1);
+    return mode != 0 && m.exact && m.N <= 2 && m.L > 1 && (mode == 2 || m.B / 128 < 512 || (mode != 1 && rn_gemm_precision() == 1));
 }
 static bool mix_xless_saved(const MixDims& m, const void* sv) {      // what the forward that filled `saved` did (unknown buffer: the rule)
     const int have = mix_stamp_get(sv);
@@ -579,9 +575,8 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
             return rc;
         rn_prof_end(pr_pack, st);
     }
-    // split precision: the piece planes of every layer's packed weights, one launch (RECNOW_SPLIT_PLANES_ONCE=0: each product splits its own, A/B switch)
-    static const bool planes_once = []() { const char* e = getenv("RECNOW_SPLIT_PLANES_ONCE"); return !e || e[0] != '0'; }();
-    const bool planes_on = planes_once && pack_product && rn_gemm_precision() == 1 && mix_planes_shape(m);
+    // split precision: the piece planes of every layer's packed weights, one launch
+    const bool planes_on = pack_product && rn_gemm_precision() == 1 && mix_planes_shape(m);
     if (planes_on) {
         RnSplitJobs jobs;
         jobs.n = 0;
@@ -643,7 +638,7 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
             const bool absorb = rn_mix_mid_absorbs_slabs(B, S, N, m.LDT);
             // GEMM1 with the sub-space forward in its epilogue (recnow_gemm_desc.mid_V): two experts of 64, a batch large enough that the
             // product is not split over K (512 batch tiles), exact-fp32 products; T1, T2 and T2g leave the one kernel, `k_mix_mid_fwd` is gone
-            static const int midf_on = []() { const char* e = getenv("RECNOW_MIDF"); return e ? atoi(e) : 1; }();      // A/B switch: 0 off, 2 any batch (tests)
+            static const int midf_on = rn_env_int("RECNOW_MIDF", 1);      // A/B switch: 0 off, 2 any batch (tests)
             if (midf_on && N == 2 && S == 64 && m.LDT == 144 && B % 128 == 0 && (B / 128 >= 512 || midf_on == 2) && rn_gemm_precision() == 0 &&
                 rn_mix_mid_supported(S, N, m.LDT)) {
                 recnow_gemm_desc d = rn_gemm_desc_zero();
@@ -1033,7 +1028,7 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     if (!two) st2 = st;
     // RECNOW_TWO_STREAMS=2 ("paired"): BOTH weight-gradient products of a layer (MFMA-bound) are held back until the sub-space
     // backward is done, so that they run beside the layer's dx product (HBM-bound) instead of beside the MFMA-bound dT2g product
-    static const bool paired = []() { const char* e = getenv("RECNOW_TWO_STREAMS"); return e && e[0] == '2'; }();
+    static const bool paired = rn_env_int("RECNOW_TWO_STREAMS", 0) == 2;
     RnCarver c(ws, ws_bytes);
     float* Wc1_all = c.take<float>((size_t)L * D * m.LDT);        // per-layer packs (L > MIX_PACK_MAX_L only: otherwise the forward's, in `saved`)
     float* dWc1 = c.take<float>((size_t)D * m.LDT);
@@ -1091,10 +1086,9 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
             RN_LAUNCH_CHECK();
         }
     }
-    // the input gradient in one go (c2_mode 5 / 6 of the short-K kernel: two experts of 64, K = 144): fused head, 2 or 3 layers.  RECNOW_DX_ONCE=0: the
-    // read-modify-write chain of rounds 1-4 (A/B switch, read per call).  A pass cut into layer pieces decides the same way in every piece.
-    const char* dx_once_env = getenv("RECNOW_DX_ONCE");
-    const bool dx_once = hd && dx && (L == 2 || L == 3) && m.KP == 144 && !(dx_once_env && dx_once_env[0] == '0');
+    // the input gradient in one go (c2_mode 5 / 6 of the short-K kernel: two experts of 64, K = 144): fused head, 2 or 3 layers; other shapes take the
+    // read-modify-write chain.  A pass cut into layer pieces decides the same way in every piece.
+    const bool dx_once = hd && dx && (L == 2 || L == 3) && m.KP == 144;
     hipEvent_t e_g = nullptr;        // "g of this layer (and the packs) are ready" -> side stream may start the layer
     MIX_SIGNAL(e_g, st);
     hipEvent_t e_side_prev = nullptr;   // side stream finished the previous (higher) layer: dT1/dC/g buffers reusable
@@ -1537,7 +1531,7 @@ extern "C" int recnow_dcn_mix_step(const recnow_dcn_mix_step_desc* d, int phases
         // small shards (<= 8192 rows, float32 / int32 ids): keys, solo flags, sort and segments in ONE launch straight from the id tensor
         // ... and, when the forward pass of this call runs the row-block kernels, the packs of their weights on the launch's other workgroups
         // (RECNOW_STEP_FRONT=0: the pack stays a launch of its own in front of the forward kernel)
-        static const bool front = []() { const char* e = getenv("RECNOW_STEP_FRONT"); return !e || e[0] != '0'; }();
+        static const bool front = rn_env_int("RECNOW_STEP_FRONT", 1) != 0;
         RnTileFwd pk;
         const RnTileFwd* pack = nullptr;
         if (front && (phases & RECNOW_STEP_FORWARD) && mix_tile_on(m) && d->U_host && d->V_host && d->W_host && d->bias_host && d->gate_host) {
@@ -1574,10 +1568,9 @@ extern "C" int recnow_dcn_mix_step(const recnow_dcn_mix_step_desc* d, int phases
     }
     if (phases & RECNOW_STEP_LOSS) {
         if (!d->scores || !d->labels || !d->loss || !d->n_pair) return RECNOW_EINVAL;
-        // no pack launch: the pair walk fills its LDS stages from the inputs (RN_PAIR_UNPACKED); RECNOW_STEP_PACK=1 keeps the packed form (A/B)
-        static const bool packed = []() { const char* e = getenv("RECNOW_STEP_PACK"); return e && e[0] == '1'; }();
-        const int flags = RECNOW_PAIR_LABEL_GT | (d->only_use_wrong_order_pair ? RECNOW_PAIR_WRONG_ORDER : 0) |
-                          (packed ? 0 : (RN_PAIR_UNPACKED | (npair_zeroed ? RN_PAIR_NPAIR_ZEROED : 0)));
+        // no pack launch: the pair walk fills its LDS stages from the inputs (RN_PAIR_UNPACKED)
+        const int flags = RECNOW_PAIR_LABEL_GT | (d->only_use_wrong_order_pair ? RECNOW_PAIR_WRONG_ORDER : 0) | RN_PAIR_UNPACKED |
+                          (npair_zeroed ? RN_PAIR_NPAIR_ZEROED : 0);
         RnProfRecord* pr = rn_prof_on() ? rn_prof_begin(RN_TAG_STEP_LOSS, 0.0, 16.0 * B + 8.0 * BP * m.LDT, st) : nullptr;
         const double* loss_part = nullptr;
         int n_loss_part = 0;

@@ -35,9 +35,8 @@ bool rn_mix_mid_supported(int S, int N, int LDT) {
 }
 
 static inline int mid_grid(int64_t B) {
-    static const int cap = []() { const char* e = getenv("RECNOW_MID_BWD_GRID"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 512 ? v : 512; }();      // experiments: <= 512 (the workspace is sized for 512 partials)
     const int64_t tiles = (B + MID_ROWS - 1) / MID_ROWS;
-    return (int)(tiles < cap ? (tiles > 0 ? tiles : 1) : cap);
+    return (int)(tiles < 512 ? (tiles > 0 ? tiles : 1) : 512);
 }
 
 // forward: as many workgroups as the LDS footprint lets a CU hold (the kernel is latency-bound per workgroup)
@@ -604,10 +603,6 @@ __device__ __forceinline__ void mid_bwd_fast_body(const float* __restrict__ dT2g
     // re-read last tile again, which nobody uses).
     prefetch((int64_t)blockIdx.x * MID_ROWS);
     __syncthreads();                       // VTs complete
-    if (sl.stagger > 0 && (int)blockIdx.x >= (int)gridDim.x / 2) {      // experiment: de-phase the two workgroups of a CU (every wave leaves the bounded loop)
-        const long long t0 = wall_clock64();
-        while (wall_clock64() - t0 < (long long)sl.stagger && wall_clock64() - t0 < 2000) __builtin_amdgcn_s_sleep(8);
-    }
     stage();
     MT_STAMP(0, 0);
     int mt_k = 0;
@@ -734,25 +729,22 @@ static int mid_allow_lds(K kernel, size_t bytes) {
     return RECNOW_OK;
 }
 
-static const bool g_mid_fast = []() { const char* e = getenv("RECNOW_MID_FAST"); return !e || e[0] != '0'; }();      // A/B switch
 bool rn_mix_mid_absorbs_slabs(int64_t B, int S, int N, int LDT) {
-    static const bool on = []() { const char* e = getenv("RECNOW_MID_SLABS"); return !e || e[0] != '0'; }();            // A/B switch
-    return on && g_mid_fast && B % MID_ROWS == 0 && ((S == 64 && N == 2) || (S == 32 && N == 4)) && LDT == S * N + 16;
+    return B % MID_ROWS == 0 && ((S == 64 && N == 2) || (S == 32 && N == 4)) && LDT == S * N + 16;
 }
 int rn_mix_mid_fwd(const float* T1, const float* V, float* T2, float* T2g, int64_t B, int S, int N, int LDT, int act_outer, hipStream_t st,
                    const RnSlabs* slabs, int act_inner) {
     if (!rn_mix_mid_supported(S, N, LDT)) return RECNOW_EUNSUPPORTED;
     if (slabs && (!rn_mix_mid_absorbs_slabs(B, S, N, LDT) || (slabs->n != 2 && slabs->n != 4))) return RECNOW_EUNSUPPORTED;
     RnSlabs sl;
-    sl.p = nullptr; sl.n = 0; sl.ld = 0; sl.stride = 0; sl.stagger = 0;
+    sl.p = nullptr; sl.n = 0; sl.ld = 0; sl.stride = 0;
     if (slabs) sl = *slabs;
     const size_t lds = mid_fwd_lds(S, N);
     int rc;
     // measurement hook: read T1, write T2 and T2g (12 * B * LDT bytes)
     RnProfRecord* pr = rn_prof_on() ? rn_prof_begin(RN_TAG_MIX_MID_FWD, 4.0 * B * N * S * S, 12.0 * B * LDT, st) : nullptr;
-    const bool mid_fast = g_mid_fast;
 #define MID_FWD_FAST(SS, NN)                                                                                                  \
-    if (mid_fast && B % MID_ROWS == 0 && S == SS && N == NN && LDT == SS * NN + 16) {                                         \
+    if (B % MID_ROWS == 0 && S == SS && N == NN && LDT == SS * NN + 16) {                                         \
         if (slabs && sl.n == 4) {                                                                                             \
             if ((rc = mid_allow_lds(k_mix_mid_fwd_fast<SS, NN, 4>, lds))) return rc;                                          \
             hipLaunchKernelGGL((k_mix_mid_fwd_fast<SS, NN, 4>), mid_fwd_grid(B, lds), 256, lds, st, T1, V, T2, T2g, B, LDT, act_outer, sl, act_inner); \
@@ -788,10 +780,8 @@ int rn_mix_mid_bwd(const float* dT2g, const float* T2, const float* T1, const fl
     if (!rn_mix_mid_supported(S, N, LDT)) return RECNOW_EUNSUPPORTED;
     if (slabs && (!rn_mix_mid_absorbs_slabs(B, S, N, LDT) || (slabs->n != 2 && slabs->n != 4))) return RECNOW_EUNSUPPORTED;
     RnSlabs sl;
-    sl.p = nullptr; sl.n = 0; sl.ld = 0; sl.stride = 0; sl.stagger = 0;
+    sl.p = nullptr; sl.n = 0; sl.ld = 0; sl.stride = 0;
     if (slabs) sl = *slabs;
-    static const int stagger = []() { const char* e = getenv("RECNOW_MID_STAGGER"); return e ? atoi(e) : 0; }();      // experiment, 10 ns ticks
-    sl.stagger = stagger;
     if (ws_bytes < rn_mix_mid_bwd_ws_bytes(B, S, N)) return RECNOW_EWORKSPACE;
     const size_t lds = mid_bwd_lds(S, N);
     const int grid = mid_grid(B);
@@ -805,10 +795,9 @@ int rn_mix_mid_bwd(const float* dT2g, const float* T2, const float* T1, const fl
         if ((rc = mid_allow_lds(k_mix_mid_bwd<SS, VV>, lds))) return rc;                                                      \
         hipLaunchKernelGGL((k_mix_mid_bwd<SS, VV>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, N, LDT, act_inner, act_outer, rscale); \
     } while (0)
-    const bool mid_fast = g_mid_fast;
     bool done = false;
 #define MID_BWD_FAST(SS, NN)                                                                                                  \
-    if (!done && mid_fast && B % MID_ROWS == 0 && S == SS && N == NN && LDT == SS * NN + 16) {                                                    \
+    if (!done && B % MID_ROWS == 0 && S == SS && N == NN && LDT == SS * NN + 16) {                                        \
         const int slv = slabs ? sl.n : 0;                                                                                     \
         if (rscale && slv == 4) { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, true, 4>, lds))) return rc;               \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, true, 4>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \

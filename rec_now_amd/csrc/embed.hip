@@ -264,10 +264,9 @@ extern "C" int recnow_embed_pool_fwd(const float* table, int D, int64_t V, const
     if (rc) return rc;
     int64_t g = (B + waves - 1) / waves;
     if (g > 4096) g = 4096;
-    static const bool v4_on = []() { const char* e = getenv("RECNOW_EMBED_V4"); return !e || e[0] != '0'; }();      // A/B switch
     const int gs4 = D / 4;
     // the accumulator tile of a wave starts at w * (T*D + T) floats: 16-byte aligned for every wave iff T is a multiple of 4
-    const bool v4 = v4_on && D % 4 == 0 && gs4 >= 1 && gs4 <= 16 && (gs4 & (gs4 - 1)) == 0 && T % 4 == 0 && (((uintptr_t)table | (uintptr_t)out) & 15) == 0;
+    const bool v4 = D % 4 == 0 && gs4 >= 1 && gs4 <= 16 && (gs4 & (gs4 - 1)) == 0 && T % 4 == 0 && (((uintptr_t)table | (uintptr_t)out) & 15) == 0;
     if (v4) hipLaunchKernelGGL(k_embed_pool_fwd_v4, (int)g, waves * 64, lds, (hipStream_t)stream, table, D, V, rows, seg, weights, B, C, T, mean, out, cnt);
     else hipLaunchKernelGGL(k_embed_pool_fwd, (int)g, waves * 64, lds, (hipStream_t)stream, table, D, V, rows, seg, weights, B, C, T, mean, out, cnt);
     RN_LAUNCH_CHECK();

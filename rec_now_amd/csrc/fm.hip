@@ -271,8 +271,7 @@ extern "C" int recnow_fm_fwd(const float* const* fields, int F, int64_t B, int D
     hipStream_t st = (hipStream_t)stream;
     if (fm_vec_ok(D)) {
         const int64_t nchunk = B * D / 4;
-        static const int wide = []() { const char* e = getenv("RECNOW_FM_WIDE"); return e ? atoi(e) : 1; }();      // A/B switch: 0 = one chunk per thread
-        if (wide && nchunk >= 256 * 4 * 512) {          // enough chunks for 512 workgroups of 4 per thread
+        if (nchunk >= 256 * 4 * 512) {          // enough chunks for 512 workgroups of 4 per thread
             const int g = fm_grid((nchunk + 3) / 4);
             if (S) hipLaunchKernelGGL((k_fm_fwd_wide<true, 4, 4>), g, 256, 0, st, fields, F, nchunk, D / 4, y, S);
             else hipLaunchKernelGGL((k_fm_fwd_wide<false, 4, 4>), g, 256, 0, st, fields, F, nchunk, D / 4, y, S);
@@ -295,8 +294,7 @@ extern "C" int recnow_fm_bwd(const float* const* fields, float* const* dfields, 
     hipStream_t st = (hipStream_t)stream;
     if (fm_vec_ok(D)) {
         const int64_t nchunk = B * D / 4;
-        static const int wide = []() { const char* e = getenv("RECNOW_FM_WIDE"); return e ? atoi(e) : 1; }();
-        if (wide && nchunk >= 256 * 4 * 512 && nchunk % (256 * 4) == 0)
+        if (nchunk >= 256 * 4 * 512 && nchunk % (256 * 4) == 0)
             hipLaunchKernelGGL((k_fm_bwd_wide<4, 4>), fm_grid(nchunk / 4), 256, 0, st, fields, dfields, F, nchunk, D / 4, S, gy);
         else hipLaunchKernelGGL(k_fm_bwd_vec4, fm_grid(nchunk), 256, 0, st, fields, dfields, F, nchunk, D / 4, S, gy);
     } else {

@@ -149,13 +149,13 @@ k_layer_end_reduce(const GemmK pa, int va, int na, const GemmK pb, int vb, int n
 #include "gemm_split.hpp"
 int rn_gemm_precision();
 static inline RnDispatchEnv dispatch_env() {
-    static const int bm64 = []() { const char* e = getenv("RECNOW_GEMM_BM64"); return e ? atoi(e) : 256; }();        // A/B: 0 = off, N = tile bound
-    static const int kb = []() { const char* e = getenv("RECNOW_GEMM_BM64_KB"); return e ? atoi(e) : -1; }();       // A/B: 0 = only to fill the chip, 1 = always
+    static const int bm64 = rn_env_int("RECNOW_GEMM_BM64", 256);        // A/B: 0 = off, N = tile bound
+    static const int kb = rn_env_int("RECNOW_GEMM_BM64_KB", -1);       // A/B: 0 = only to fill the chip, 1 = always
     return RnDispatchEnv{bm64, kb, rn_gemm_precision()};
 }
 static inline GemmCfg pick_cfg(const recnow_gemm_desc* d) { return pick_cfg(d, dispatch_env()); }
 
-static std::atomic<int> g_gemm_staging{[]() { const char* e = getenv("RECNOW_GEMM_GLDS"); return (e && e[0] == '1') ? 1 : 0; }()};      // recnow_set_gemm_staging
+static std::atomic<int> g_gemm_staging{rn_env_int("RECNOW_GEMM_GLDS", 0) == 1 ? 1 : 0};      // recnow_set_gemm_staging
 static int g_gemm_precision = []() {
     const char* e = getenv("RECNOW_GEMM_PRECISION");
     return (e && (!strcmp(e, "bf16x3") || !strcmp(e, "1"))) ? 1 : 0;
@@ -171,7 +171,7 @@ int rn_gemm_set_precision(int mode) {
 // (round 6: also the (K, 128) activation operand of the K = B weight-gradient products, [k][n] rows of ldb floats -- each of the eight row-tile
 // workgroups that read a k-tile of it split it again before)
 static inline bool split_planes_shape(const recnow_gemm_desc* d) {
-    static const bool kb = []() { const char* e = getenv("RECNOW_SPLIT_LEAN"); return e && e[0] == '2'; }();      // A/B switch, see rn_gemm_launch_split
+    static const bool kb = rn_env_int("RECNOW_SPLIT_LEAN", 0) == 2;      // A/B switch, see rn_gemm_launch_split
     return d->sp_r > 0 && d->N == 128 && d->K % 16 == 0 && d->batch == 1 && ((!d->a_trans && d->K <= 4096) || (kb && d->a_trans && !d->b_trans));
 }
 
@@ -179,7 +179,6 @@ static inline bool split_planes_shape(const recnow_gemm_desc* d) {
 static inline bool shortk_planes_shape(const recnow_gemm_desc* d) {
     return d->K == 144 && d->N % 128 == 0 && d->M % 128 == 0 && d->batch == 1 && !d->a_trans && d->sp_r == 0 && d->eu_r == 0;
 }
-static inline void tag_used_split_shortk() {}
 
 // workgroup slots the K split of the NEXT launches of this host thread aims at (0 = the default); see pick_split
 static thread_local int g_split_slots = 0;
@@ -254,16 +253,12 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
         k.perm_s = d->c_perm_s;
     }
     k.trace = nullptr;
-    k.cu_slots = nullptr; k.stagger_ticks = 0;
     k.tail_pairs = 8;
-    static const int direct = []() { const char* e = getenv("RECNOW_GEMM_DIRECT"); return e ? atoi(e) : 1; }();      // A/B switch
-    k.direct_store = direct;
-    static const int gemm_prio = []() { const char* e = getenv("RECNOW_GEMM_PRIO"); return e ? atoi(e) : 0; }();     // A/B switch
-    k.prio = gemm_prio;
+    k.prio = 0;
+    k.direct_store = 1;
     if (d->c_perm_s < 0 || (d->c_perm_s > 0 && (d->N % d->c_perm_s || d->batch != 1 || d->c_trans || d->accumulate))) return RECNOW_EINVAL;
     if (d->k_valid < 0 || d->k_valid > d->K) return RECNOW_EINVAL;
-    static const bool sk_tail = []() { const char* e = getenv("RECNOW_SK_TAIL"); return !e || e[0] != '0'; }();      // A/B switch
-    if (sk_tail && d->k_valid > 0 && d->K % 16 == 0 && d->k_valid > d->K - 16) k.tail_pairs = (d->k_valid - (d->K - 16) + 1) / 2;      // pairs of the last 16-deep tile
+    if (d->k_valid > 0 && d->K % 16 == 0 && d->k_valid > d->K - 16) k.tail_pairs = (d->k_valid - (d->K - 16) + 1) / 2;      // pairs of the last 16-deep tile
     k.C2 = d->C2; k.E2 = d->E2; k.ldc2 = d->ldc2; k.lde2 = d->lde2;
     k.as_in = d->as_in; k.as_out = d->as_out;
     if ((d->as_in != nullptr) != (d->as_out != nullptr)) return RECNOW_EINVAL;
@@ -321,7 +316,7 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
                             d->b_mode == 0 && !d->bias && d->act == RECNOW_ACT_LINEAR && !d->c_trans &&
                             (!d->emul || d->e_mode == RECNOW_OPMODE_MUL);
     if (use_shortk) tag = RN_TAG_GEMM_SHORTK;
-    static const bool split_longk = []() { const char* e = getenv("RECNOW_SPLIT_LONGK"); return !e || e[0] != '0'; }();      // A/B switch (diagnostics: which family an error comes from)
+    static const bool split_longk = rn_env_int("RECNOW_SPLIT_LONGK", 1) != 0;      // A/B switch (diagnostics: which family an error comes from)
     const bool split_ok = g_gemm_precision == 1 && split_longk && xf == 1 && !d->as_out && !edge && !bk16 && c.BM == 128 && c.BN == 128 && d->b_mode == 0 &&
                           (d->a_mode == RECNOW_OPMODE_NONE || d->a_mode == RECNOW_OPMODE_MUL) &&
                           ((a_kc && !b_kc && (d->a_mode == 0 || planes_ready != nullptr)) || (a_kc && b_kc) || (!a_kc && !b_kc));      // (x0 * O_{l-1}) U: the lean kernel on the caller's planes only
@@ -360,9 +355,8 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
             }
             rc = rn_gemm_launch_split(k, a_kc, b_kc, d->a_mode, planes, grid, st, planes_ready);
         }
-        static const bool sp_narrow = []() { const char* e = getenv("RECNOW_SP_NARROW"); return !e || e[0] != '0'; }();      // A/B switch
         if (d->mid_V) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, 32, 0, d->b_mode, 25, grid, st);      // XF 16 | 8 | 1: the fused sub-space forward
-        else if (rc == RECNOW_EUNSUPPORTED && sp_narrow && xf == 1 && d->sp_r <= 2 && !bk16) {
+        else if (rc == RECNOW_EUNSUPPORTED && xf == 1 && d->sp_r <= 2 && !bk16) {
             const bool glds = g_gemm_staging.load(std::memory_order_relaxed) == 1;      // A/B switch: LDS-DMA operand staging (XF | 32)
             if (glds && !a_kc && !b_kc && d->a_mode == 0 && d->b_mode == 0) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, 32, 0, 0, 41, grid, st);
             if (rc == RECNOW_EUNSUPPORTED) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, 32, d->a_mode, d->b_mode, 9, grid, st);
@@ -374,11 +368,9 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
         // C = (A B) [* emul] [+ C] with a short K: persistent kernel, no per-tile prologue, pipelined epilogue (gemm_shortk.hip)
         if (d->c2_mode && d->c2_mode < 5 && ((d->C2 && !host_aligned(d->C2, d->ldc2, 0)) || ((d->c2_mode == 2 || d->c2_mode == 4) && !host_aligned(d->E2, d->lde2, 0)))) return RECNOW_EUNSUPPORTED;
         rc = RECNOW_EUNSUPPORTED;
-        static const bool sk_split = []() { const char* e = getenv("RECNOW_SPLIT_SHORTK"); return !e || e[0] != '0'; }();      // A/B switch
-        if (g_gemm_precision == 1 && sk_split && shortk_planes_shape(d) && (planes_ready || (ws && ws_bytes >= rn_gemm_shortk_planes_bytes(d->K, d->N)))) {
+        static const bool sk_split = rn_env_int("RECNOW_SPLIT_SHORTK", 1) != 0;      // A/B switch
+        if (g_gemm_precision == 1 && sk_split && shortk_planes_shape(d) && (planes_ready || (ws && ws_bytes >= rn_gemm_shortk_planes_bytes(d->K, d->N))))
             rc = rn_gemm_launch_shortk_split(k, b_kc, (d->emul ? 1 : 0) | (d->accumulate ? 2 : 0), d->c2_mode, ws, st, planes_ready);
-            if (rc == RECNOW_OK) tag_used_split_shortk();
-        }
         if (rc == RECNOW_EUNSUPPORTED) rc = rn_gemm_launch_shortk(k, b_kc, (d->emul ? 1 : 0) | (d->accumulate ? 2 : 0), d->c2_mode, st);
         if (rc) return rc;
     } else if (d->c2_mode) {
@@ -396,11 +388,10 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
         const int64_t total = (int64_t)d->M * k.npart * d->batch;
         int g = rn_cdiv(total, 256);
         if (g > 2048) g = 2048;
-        static const bool quad_reduce = []() { const char* e = getenv("RECNOW_REDUCE_QUAD"); return !e || e[0] != '0'; }();      // A/B switch
         int variant = 0, blocks = g;
         // four lanes per output (each a quarter of the slabs) only where one lane per output would leave the chip idle: with eight slabs in
         // flight per lane the one-lane form reads faster from 96 workgroups on (c3 layer-end reduction: 19.3 vs 24.1 us)
-        if (d->N % 4 == 0 && quad_reduce && k.splitk >= 16 && (total / 4) % 64 == 0 && rn_cdiv(total / 4, 256) < 96) {      // whole quads per wave: the shuffles need all four lanes in the loop
+        if (d->N % 4 == 0 && k.splitk >= 16 && (total / 4) % 64 == 0 && rn_cdiv(total / 4, 256) < 96) {      // whole quads per wave: the shuffles need all four lanes in the loop
             variant = 2;
             blocks = rn_cdiv(total, 256) > 4096 ? 4096 : rn_cdiv(total, 256);
         } else if (d->N % 4 == 0) {

@@ -50,12 +50,12 @@ struct GemmK {
     const float* hv;           // c2_mode 3: column vector of the fused row-dot (the scoring head's kernel)
     float* hp;                 // c2_mode 3: partials hp[m][hp_ld], entry 2 * column tile + wave column
     int hp_ld;
-    int prio;                  // short-K kernel: raise the wave priority inside the k-loop (experiment)
-    int direct_store;          // lean epilogue: plain outputs straight from the accumulators (RECNOW_GEMM_DIRECT=0: staged through LDS)
+    int prio;                  // wave priority inside the k-loop: 1 in the short-K kernel (launch_sk), 0 in the lean kernels
+    int direct_store;          // lean epilogue: 1 = plain outputs straight from the accumulators
+                               // (prio and direct_store are fixed by the host; as kernel arguments rather than constants, the kernels that
+                               // read them compile to fewer VGPRs and higher occupancy, so their branches stay)
     int perm_s;                // split-K reduce: > 0 stores C[row][c] at C[((c / perm_s) * M + row) * perm_s + c % perm_s] (see recnow_gemm_desc.c_perm_s)
     int tail_pairs;            // short-K kernel: k-pairs of the LAST k-tile that hold data (8 = all; fewer: a zero-padded depth)
-    int* cu_slots;             // short-K kernel: per-CU arrival counters of the phase stagger (NULL: no stagger)
-    int stagger_ticks;         // delay per arrival slot, in 10 ns ticks of the constant 100 MHz clock
     long long* trace;          // RN_GEMM_TRACE builds only: 8 int64 per workgroup (phase timestamps, HW id)
     // XF & 16 -- fused sub-space forward of DCNMixLayer behind a TRANSPOSED GEMM1 (see recnow_gemm_desc.mid_V)
     const float* mid_V;

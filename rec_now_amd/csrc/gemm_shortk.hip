@@ -18,7 +18,6 @@
 #define SK_BM 128
 #define SK_BN 128
 #define SK_BK 16
-#define SK_STAGGER_US_DEFAULT 0      // phase stagger of the co-resident workgroups of a CU (see the kernel); 0 = off
 
 // EP: bit 0 = C *= emul, bit 1 = C += C_old.   DUAL: 0 none, 1: C2 = acc, 2: C2 += acc * E2,
 // 3 (scoring head folded into the last cross layer): C2 = acc, C = acc * emul is NOT stored, its row-dot with hv leaves as
@@ -109,24 +108,6 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
     tb.init(p.ldb);
     int slot = blockIdx.x;
     if (slot >= ntiles) return;
-    // Phase stagger.  The co-resident workgroups of a CU run identical work, so without it they move in lockstep: all of them in
-    // the k-loop (sharing the MFMA pipe), then all of them in the epilogue (the pipe idle, HBM hit by every CU at once).  Each
-    // workgroup takes an arrival number on its CU (XCC id + SE/SH/CU id of HW_ID) and starts that many delay units late; the
-    // counter is given back at exit, so the buffer stays zero between launches.  Every wave leaves the bounded wait loop.
-    int cu_key = -1;
-    if (p.cu_slots != nullptr && p.stagger_ticks > 0) {
-        __shared__ int s_arrival;
-        if (threadIdx.x == 0) {
-            const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | ((32 - 1) << 11));        // HW_ID
-            const unsigned xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11));       // XCC_ID
-            cu_key = (int)(((xcc & 15u) << 8) | ((hw >> 8) & 255u));                                 // CU_ID[11:8], SH_ID[12], SE_ID[15:13]
-            s_arrival = atomicAdd(&p.cu_slots[cu_key], 1);
-        }
-        __syncthreads();
-        const int arrival = s_arrival & 7;
-        const long long t0 = wall_clock64(), wait = (long long)arrival * p.stagger_ticks;
-        while (wall_clock64() - t0 < wait && wall_clock64() - t0 < 20000) __builtin_amdgcn_s_sleep(16);     // <= 200 us, always ends
-    }
     int m0, n0;
     tile_of(slot, m0, n0);
     // ring schedule: operand registers of the three sets (set s = k-tile % 3)
@@ -484,7 +465,6 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
         m0 = m0n;
         n0 = n0n;
     }
-    if (cu_key >= 0) atomicSub(&p.cu_slots[cu_key], 1);          // thread 0 only (cu_key stays -1 elsewhere)
 }
 
 template <bool B_KC, int EP, int DUAL, bool PRE = false, int NK = 0, bool SPL = false>
@@ -497,21 +477,7 @@ static int launch_sk(const GemmK& k, hipStream_t st, const char* planes = nullpt
     int grid = rt * ct < resident ? rt * ct : resident;
     const int xcd = (rt % 8 == 0 && grid % 8 == 0) ? 1 : 0;
     GemmK kk = k;
-    // stagger unit (microseconds, RECNOW_SK_STAGGER_US; 0 = off) and the per-CU arrival counters (allocated once, zero between launches)
-    static const int stagger_us = []() { const char* e = getenv("RECNOW_SK_STAGGER_US"); return e ? atoi(e) : SK_STAGGER_US_DEFAULT; }();
-    static int* cu_slots = nullptr;
-    kk.cu_slots = nullptr;
-    kk.stagger_ticks = 0;
-    static const int prio = []() { const char* e = getenv("RECNOW_SK_PRIO"); return e ? atoi(e) : 1; }();     // 0 = off (A/B switch)
-    kk.prio = prio;
-    if (stagger_us > 0 && grid >= 512) {
-        if (!cu_slots) {
-            if (hipMalloc((void**)&cu_slots, 4096 * sizeof(int)) != hipSuccess) return RECNOW_EINVAL;
-            RN_HIP(hipMemset(cu_slots, 0, 4096 * sizeof(int)));
-        }
-        kk.cu_slots = cu_slots;
-        kk.stagger_ticks = stagger_us * 100;
-    }
+    kk.prio = 1;
     const int64_t pb = (int64_t)(k.K / 8) * k.N * 16;
     hipLaunchKernelGGL((k_gemm_shortk<B_KC, EP, DUAL, PRE, NK, SPL>), grid, GEMM_THREADS, lds, st, kk, rt, ct, xcd, planes, pb);
     RN_LAUNCH_CHECK();
@@ -551,39 +517,30 @@ int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, 
 // guarantees: M, N multiples of 128, K a multiple of 16, A k-contiguous, every operand 16-byte aligned, batch == 1, no
 // bias / activation / transposed store.  Second outputs are instantiated for the two products DCN-v2 uses them in.
 int rn_gemm_launch_shortk(const GemmK& k, bool b_kc, int ep, int c2_mode, hipStream_t st) {
-    static const bool pre = []() { const char* e = getenv("RECNOW_SK_PRE"); return !e || e[0] != '0'; }();     // A/B switch of the whole-tile emul prefetch
-    // nine k-tiles (DCN-v2: K = N*S + N = 130 stored as 144): the ring schedule; RECNOW_SK_RING=0 is the A/B switch
-    static const int ring = []() { const char* e = getenv("RECNOW_SK_RING"); return e ? atoi(e) : 31; }();
-    if (k.K == 9 * SK_BK && (ring & 1) && pre && !b_kc && ep == 1) {
+    // nine k-tiles (DCN-v2: K = N*S + N = 130 stored as 144): the ring schedule
+    if (k.K == 9 * SK_BK && !b_kc && ep == 1) {
         if (c2_mode == 1) return launch_sk<false, 1, 1, true, 9>(k, st);
         if (c2_mode == 3) return launch_sk<false, 1, 3, true, 9>(k, st);
         if (c2_mode == 0) return launch_sk<false, 1, 0, true, 9>(k, st);
     }
-    if (k.K == 9 * SK_BK && (ring & 1) && !pre && !b_kc && ep == 1) {      // RECNOW_SK_PRE=0: the ring without the whole-tile prefetch, 3 workgroups per CU
-        if (c2_mode == 1) return launch_sk<false, 1, 1, false, 9>(k, st);
-        if (c2_mode == 3) return launch_sk<false, 1, 3, false, 9>(k, st);
-        if (c2_mode == 0) return launch_sk<false, 1, 0, false, 9>(k, st);
-    }
-    if (k.K == 9 * SK_BK && (ring & 1) && !b_kc && ep == 0 && c2_mode == 0) return launch_sk<false, 0, 0, false, 9>(k, st);      // O_l = T2g [W; b] alone (mix_xless)
-    if (k.K == 9 * SK_BK && (ring & 4) && b_kc && ep == 2 && c2_mode == 0)
-        return pre ? launch_sk<true, 2, 0, true, 9>(k, st) : launch_sk<true, 2, 0, false, 9>(k, st);
+    if (k.K == 9 * SK_BK && !b_kc && ep == 0 && c2_mode == 0) return launch_sk<false, 0, 0, false, 9>(k, st);      // O_l = T2g [W; b] alone (mix_xless)
+    if (k.K == 9 * SK_BK && b_kc && ep == 2 && c2_mode == 0) return launch_sk<true, 2, 0, true, 9>(k, st);
     if (k.K == 9 * SK_BK && b_kc && ep == 0) {
-        if (c2_mode == 2 && (ring & 2)) return launch_sk<true, 0, 2, false, 9>(k, st);
-        if (c2_mode == 4 && (ring & 8)) return launch_sk<true, 0, 4, false, 9>(k, st);
+        if (c2_mode == 2) return launch_sk<true, 0, 2, false, 9>(k, st);
+        if (c2_mode == 4) return launch_sk<true, 0, 4, false, 9>(k, st);
         if (c2_mode == 5) return launch_sk<true, 0, 5, false, 9>(k, st);
         if (c2_mode == 6) return launch_sk<true, 0, 6, false, 9>(k, st);
-        if (c2_mode == 0 && (ring & 16)) return launch_sk<true, 0, 0, false, 9>(k, st);      // g_l alone (the input gradient is accumulated once, c2_mode 5 / 6)
+        if (c2_mode == 0) return launch_sk<true, 0, 0, false, 9>(k, st);      // g_l alone (the input gradient is accumulated once, c2_mode 5 / 6)
     }
     if (c2_mode >= 5) return RECNOW_EUNSUPPORTED;
-    if (pre && !b_kc && ep == 1) {
+    if (!b_kc && ep == 1) {
         if (c2_mode == 1) return launch_sk<false, 1, 1, true>(k, st);
         if (c2_mode == 3) return launch_sk<false, 1, 3, true>(k, st);
         if (c2_mode == 0) return launch_sk<false, 1, 0, true>(k, st);
     }
-    if (c2_mode == 1) return (!b_kc && ep == 1) ? launch_sk<false, 1, 1>(k, st) : RECNOW_EUNSUPPORTED;
     if (c2_mode == 2) return (b_kc && ep == 0) ? launch_sk<true, 0, 2>(k, st) : RECNOW_EUNSUPPORTED;
-    if (c2_mode == 3) return (!b_kc && ep == 1) ? launch_sk<false, 1, 3>(k, st) : RECNOW_EUNSUPPORTED;
     if (c2_mode == 4) return (b_kc && ep == 0) ? launch_sk<true, 0, 4>(k, st) : RECNOW_EUNSUPPORTED;
+    if (c2_mode) return RECNOW_EUNSUPPORTED;      // c2_mode 1 / 3: the EP == 1 forward above only
     if (b_kc) {
         switch (ep) {
             case 0: return launch_sk<true, 0, 0>(k, st);
@@ -594,8 +551,8 @@ int rn_gemm_launch_shortk(const GemmK& k, bool b_kc, int ep, int c2_mode, hipStr
     }
     switch (ep) {
         case 0: return launch_sk<false, 0, 0>(k, st);
-        case 1: return launch_sk<false, 1, 0>(k, st);
         case 2: return launch_sk<false, 2, 0>(k, st);
-        default: return launch_sk<false, 3, 0>(k, st);
+        case 3: return launch_sk<false, 3, 0>(k, st);
+        default: return RECNOW_EUNSUPPORTED;      // (EP == 1: the prefetching kernel above)
     }
 }

@@ -627,7 +627,7 @@ template <bool A_KC, int A2K>
 static int s3_launch(const GemmK& k, const char* planes, int64_t pb, dim3 grid, hipStream_t st, int slot) {
     const size_t lds = S3_LDS(k.kchunk);
     // paired A loads (see the kernel): k-contiguous operands, whole groups of four k-tiles, rows that start on a 128-byte line; RECNOW_S3_PAIR=0: A/B switch
-    static const bool pair_on = []() { const char* e = getenv("RECNOW_S3_PAIR"); return !e || e[0] != '0'; }();
+    static const bool pair_on = rn_env_int("RECNOW_S3_PAIR", 1) != 0;
     if constexpr (A_KC) {
         if (pair_on && k.kchunk % (4 * SPL_BK) == 0 && k.lda % 32 == 0 && ((uintptr_t)k.A & 127) == 0 && (A2K == RECNOW_OPMODE_NONE || ((uintptr_t)k.A2 & 127) == 0)) {
             if (lds > 64 * 1024 && !g_s3_lds_ready[4 + slot].load(std::memory_order_acquire)) {
@@ -656,11 +656,11 @@ int rn_gemm_launch_split(const GemmK& k, bool a_kc, bool b_kc, int a2k, void* pl
     // element offsets inside a tile are 32-bit
     if ((int64_t)128 * k.lda >= (1ll << 31) || (int64_t)128 * k.ldb >= (1ll << 31)) return RECNOW_EUNSUPPORTED;
     const int64_t pb = (int64_t)(k.K / 8) * k.N * 16;
-    static const bool s3_on = []() { const char* e = getenv("RECNOW_SPLIT_LEAN"); return !e || e[0] != '0'; }();      // A/B switch: 0 = k_gemm_split of rounds 2-5
+    static const bool s3_on = rn_env_int("RECNOW_SPLIT_LEAN", 1) != 0;      // A/B switch: 0 = k_gemm_split of rounds 2-5
     // [k][row] operands (the K = B weight-gradient products) with a pre-split activation operand: built and measured in the step -- 103 / 130 us
     // (A / A * A2) + 18 us for the split of the (B, 128) operand against 111 / 126 us for k_gemm_split, which splits B in every workgroup: the
     // pre-pass costs what the leaner loop gains, so these products stay on k_gemm_split (RECNOW_SPLIT_LEAN=2 routes them here: A/B switch)
-    static const bool s3_kb = []() { const char* e = getenv("RECNOW_SPLIT_LEAN"); return e && e[0] == '2'; }();
+    static const bool s3_kb = rn_env_int("RECNOW_SPLIT_LEAN", 0) == 2;
     // ready != NULL: the caller holds the planes of this product's B already (the packed weights of a step are split once, dcnmix.hip)
     if (ready && s3_on && s3_shape(k, a2k) && a_kc)
         return a2k == 0 ? s3_launch<true, 0>(k, (const char*)ready, pb, grid, st, 0) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)ready, pb, grid, st, 1);

@@ -149,7 +149,7 @@ __device__ __forceinline__ void bpr_term(const Member& me, const Member& o, bool
 // lying strictly inside them is shorter than 64 rows, so only the first and the last row's segment can be long, and looking at
 // those two decides block-uniformly whether there is anything to do: batches without long groups pay one empty launch.
 #define PW_LONG 512
-template <int FLAGS, int MODE>                     // MODE 0: pair counts;  1: BPR loss and gradient terms;  2: both in one walk
+template <int FLAGS, int MODE>                     // MODE 0: pair counts;  1: BPR loss and gradient terms
 __global__ void __launch_bounds__(256)
 k_pair_long(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first, int64_t B,
             float factor, int32_t* __restrict__ long_cnt, float* __restrict__ long_la, float* __restrict__ long_ga) {
@@ -306,11 +306,10 @@ k_pair_bpr(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, c
 // instructions per member (two transcendentals), and with one lane per row a 64-member group made the launch 64 such steps long whatever the grid --
 // 12.6 us at 8192 rows, where the grid is 32 workgroups.  The lanes' gradient terms meet by two fixed-order butterfly steps (the same bits on every
 // lane and run), their loss terms and counts go into the block sum as they are.  A block owns 256 / LPR consecutive sorted rows.
-// SKIP_LONG: rows of long segments contribute nothing here and their dscores entry is not written (the long-row workgroups of k_pair_all do both).
-template <int FLAGS, int LPR, bool SKIP_LONG = false, typename SRC = const Member*>
+// Rows of long segments contribute nothing here and their dscores entry is not written (the long-row workgroups of k_pair_all do both).
+template <int FLAGS, int LPR, typename SRC>
 __device__ __forceinline__ void pair_one_body(const SRC mem, const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first,
-                                              int64_t B, float factor, const int32_t* __restrict__ long_cnt, const float* __restrict__ long_la,
-                                              const float* __restrict__ long_ga, double* __restrict__ block_loss, unsigned long long* __restrict__ n_pair,
+                                              int64_t B, float factor, double* __restrict__ block_loss, unsigned long long* __restrict__ n_pair,
                                               float* __restrict__ dscores, Member* staged, double* red, long long* redc) {
     int sbase;
     const bool in_lds = stage_members(mem, seg_id, seg_first, B, staged, &sbase, 256 / LPR);
@@ -323,7 +322,7 @@ __device__ __forceinline__ void pair_one_body(const SRC mem, const int32_t* __re
         const Member me = in_lds ? staged[k - sbase] : mem[k];          // (the staged range covers every row of the block)
         const int g = seg_id[k];
         const int s = seg_first[g], e = seg_first[g + 1];
-        const bool is_long = e - s > PW_LONG;       // walked by k_pair_long
+        const bool is_long = e - s > PW_LONG;       // walked by the long-row workgroups of k_pair_all
         int cc = 0;
         float la = 0.f, ga = 0.f;
         if (in_lds) {
@@ -343,12 +342,7 @@ __device__ __forceinline__ void pair_one_body(const SRC mem, const int32_t* __re
         }
 #pragma unroll
         for (int o = 1; o < LPR; o <<= 1) ga += __shfl_xor(ga, o, 64);
-        if (is_long && !SKIP_LONG) {
-            cc = sub == 0 ? long_cnt[k] : 0;
-            la = sub == 0 ? long_la[k] : 0.f;
-            ga = long_ga[k];
-        }
-        if (kr < B && !(SKIP_LONG && is_long)) {
+        if (kr < B && !is_long) {
             if (sub == 0) dscores[me.row] = factor * ga;
             lsum = (double)la;
             c = cc;
@@ -361,27 +355,7 @@ __device__ __forceinline__ void pair_one_body(const SRC mem, const int32_t* __re
         if (c) atomicAdd(n_pair, (unsigned long long)c);      // integer atomics: order-independent
     }
 }
-template <int FLAGS>
-__global__ void __launch_bounds__(256)
-k_pair_one(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first, int64_t B, float factor,
-           const int32_t* __restrict__ long_cnt, const float* __restrict__ long_la, const float* __restrict__ long_ga,
-           double* __restrict__ block_loss, unsigned long long* __restrict__ n_pair, float* __restrict__ dscores) {
-    __shared__ double red[16];
-    __shared__ long long redc[16];
-    __shared__ Member staged[PW_STAGE];
-    pair_one_body<FLAGS, 1>(mem, seg_id, seg_first, B, factor, long_cnt, long_la, long_ga, block_loss, n_pair, dscores, staged, red, redc);
-}
-template <int FLAGS>
-__global__ void __launch_bounds__(256)
-k_pair_one4(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first, int64_t B, float factor,
-            const int32_t* __restrict__ long_cnt, const float* __restrict__ long_la, const float* __restrict__ long_ga,
-            double* __restrict__ block_loss, unsigned long long* __restrict__ n_pair, float* __restrict__ dscores) {
-    __shared__ double red[16];
-    __shared__ long long redc[16];
-    __shared__ Member staged[PW_STAGE];
-    pair_one_body<FLAGS, 4>(mem, seg_id, seg_first, B, factor, long_cnt, long_la, long_ga, block_loss, n_pair, dscores, staged, red, redc);
-}
-// Round 5 (second session): the loss walk as ONE launch.  Workgroups [0, g_one) are k_pair_one / k_pair_one4 with the rows of long segments left out;
+// Round 5 (second session): the loss walk as ONE launch.  Workgroups [0, g_one) walk the rows of short segments, LPR lanes per row (pair_one_body);
 // workgroup g_one + b is k_pair_long's workgroup b (64 consecutive sorted rows, a wave per row of a long segment) -- but instead of parking (count, loss
 // term, gradient term) per sorted row for a second kernel it writes the row's dscores entry, adds the counts to n_pair and leaves its loss terms as
 // block_loss[g_one + b] (0 for the usual workgroup without a long segment).  No workgroup reads what another one writes: the batch without long groups no
@@ -394,8 +368,7 @@ k_pair_all(const MemberSrc<UNP> mem, const int32_t* __restrict__ seg_id, const i
     __shared__ long long redc[16];
     __shared__ Member staged[PW_STAGE];
     if ((int)blockIdx.x < g_one) {
-        pair_one_body<FLAGS, LPR, true, MemberSrc<UNP>>(mem, seg_id, seg_first, B, factor, nullptr, nullptr, nullptr, block_loss, n_pair, dscores, staged, red,
-                                                         redc);
+        pair_one_body<FLAGS, LPR>(mem, seg_id, seg_first, B, factor, block_loss, n_pair, dscores, staged, red, redc);
         return;
     }
     const int64_t k0 = (int64_t)((int)blockIdx.x - g_one) * 64;
@@ -603,7 +576,7 @@ __global__ void k_seg_empty2(int32_t* seg_first, int32_t* n_seg, unsigned long l
 
 // ---- host side ---------------------------------------------------------------------------------------
 #define RN_PW_T 256
-#define RN_PW_LPR 4        // lanes per row of k_pair_one4
+#define RN_PW_LPR 4        // lanes per row of the quad form of k_pair_all
 #define RN_VEC_BLOCKS 1024
 
 extern "C" size_t recnow_pairwise_workspace_bytes(int64_t B) {
@@ -764,11 +737,9 @@ int rn_pair_bpr_onepass(const float* scores, const float* labels, const uint8_t*
     if ((flags & (RECNOW_PAIR_LABEL_GT | RECNOW_PAIR_WRONG_ORDER)) == 0) return RECNOW_EINVAL;      // as recnow_pair_bpr_fwdbwd
     if (ws_bytes < recnow_pairwise_workspace_bytes(B)) return RECNOW_EWORKSPACE;
     const PairWs pw = pair_ws(ws, ws_bytes, B);
-    const int G = rn_cdiv(B, RN_PW_T);
-    static const bool one_launch = []() { const char* e = getenv("RECNOW_PAIR_ALL"); return !e || e[0] != '0'; }();      // A/B switch: 0 = k_pair_long + k_pair_one(4)
     // RN_PAIR_UNPACKED (internal: the step's loss stage): no pack launch -- the walk's workgroups fill their LDS stages from the inputs through `order`;
     // RN_PAIR_NPAIR_ZEROED: an earlier launch of the caller has cleared *n_pair (the step's grouping launch), else a fill does it here.
-    const bool unpacked = one_launch && (flags & RN_PAIR_UNPACKED) != 0 && !(flags & RECNOW_PAIR_MEMBERS_PACKED);
+    const bool unpacked = (flags & RN_PAIR_UNPACKED) != 0 && !(flags & RECNOW_PAIR_MEMBERS_PACKED);
     // RECNOW_PAIR_MEMBERS_PACKED: recnow_group_pack_small has packed the members into `ws` and cleared *n_pair
     int rc = RECNOW_OK;
     if (unpacked) {
@@ -779,13 +750,9 @@ int rn_pair_bpr_onepass(const float* scores, const float* labels, const uint8_t*
     if (rc) return rc;
     // Four lanes per row while the one-lane grid would leave most of the chip idle (B <= 32 768: at most 128 workgroups).  Measured (tools/layer_bench.py, GPU
     // time of the loss fwd+bwd, one box): B = 8192 / 128 groups 66 -> 62 us, Zipf-skewed 130 -> 117 us, the 8192-row step 0.609 -> 0.602 ms; B = 65 536 / 1024 groups
-    // 81 -> 86 us (four times the block sums and staging for a grid that already fills the chip): one lane per row stays there.  RECNOW_PAIR_LPR=1 / =4 force a form.
-    static const int lpr_env = []() { const char* e = getenv("RECNOW_PAIR_LPR"); return e ? atoi(e) : 0; }();
-    const bool quad = lpr_env == 4 || (lpr_env != 1 && B <= 32768);
-    int nparts = G;
-    if (one_launch) {
-        const int g_one = rn_cdiv(B, quad ? RN_PW_T / RN_PW_LPR : RN_PW_T), g_all = g_one + rn_cdiv(B, 64);
-        nparts = g_all;
+    // 81 -> 86 us (four times the block sums and staging for a grid that already fills the chip): one lane per row stays there.
+    const bool quad = B <= 32768;
+    const int g_one = rn_cdiv(B, quad ? RN_PW_T / RN_PW_LPR : RN_PW_T), g_all = g_one + rn_cdiv(B, 64);
 #define RN_PAIR_ALL(F)                                                                                                                              \
     do {                                                                                                                                            \
         if (unpacked) {                                                                                                                             \
@@ -802,30 +769,18 @@ int rn_pair_bpr_onepass(const float* scores, const float* labels, const uint8_t*
                                     (unsigned long long*)n_pair, dscores_unnorm, g_one);                                                             \
         }                                                                                                                                           \
     } while (0)
-        switch (flags & 3) {
-            case 0: RN_PAIR_ALL(0); break;
-            case 1: RN_PAIR_ALL(1); break;
-            case 2: RN_PAIR_ALL(2); break;
-            default: RN_PAIR_ALL(3); break;
-        }
-#undef RN_PAIR_ALL
-    } else {
-        RN_DISPATCH_LONG(2, pw.mem, seg_id, seg_first, B, factor, pw.long_cnt, pw.long_la, pw.long_ga);
-        if (quad) {
-            const int G = rn_cdiv(B, RN_PW_T / RN_PW_LPR);          // (shadows the one-lane grid inside the dispatch macro)
-            nparts = G;
-            RN_DISPATCH_FLAGS(k_pair_one4, pw.mem, seg_id, seg_first, B, factor, pw.long_cnt, pw.long_la, pw.long_ga, pw.part,
-                              (unsigned long long*)n_pair, dscores_unnorm);
-        } else {
-            RN_DISPATCH_FLAGS(k_pair_one, pw.mem, seg_id, seg_first, B, factor, pw.long_cnt, pw.long_la, pw.long_ga, pw.part,
-                              (unsigned long long*)n_pair, dscores_unnorm);
-        }
+    switch (flags & 3) {
+        case 0: RN_PAIR_ALL(0); break;
+        case 1: RN_PAIR_ALL(1); break;
+        case 2: RN_PAIR_ALL(2); break;
+        default: RN_PAIR_ALL(3); break;
     }
+#undef RN_PAIR_ALL
     if (part_out) {
         *part_out = pw.part;
-        *nparts_out = nparts;
+        *nparts_out = g_all;
     } else {
-        hipLaunchKernelGGL(k_loss_finalize, 1, 1024, 0, st, pw.part, nparts, (const unsigned long long*)n_pair, (int64_t)0, reduce_mean, loss);
+        hipLaunchKernelGGL(k_loss_finalize, 1, 1024, 0, st, pw.part, g_all, (const unsigned long long*)n_pair, (int64_t)0, reduce_mean, loss);
     }
     RN_LAUNCH_CHECK();
     return RECNOW_OK;

@@ -1132,8 +1132,6 @@ static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t 
                          int32_t* seg_first, int32_t* super_id, int32_t* n_seg, void* ws, size_t ws_bytes, hipStream_t st, const RnTileFwd* pack = nullptr,
                          unsigned long long* zero1 = nullptr, int* zeroed = nullptr, int* packed = nullptr) {
     if (packed) *packed = 0;
-    static const bool coop = []() { const char* e = getenv("RECNOW_GROUP_COOP"); return !e || e[0] != '0'; }();      // A/B switch
-    if (!coop) return RECNOW_EUNSUPPORTED;
     const int nblk = rn_cdiv(B, RN_TILE);
     RnCarver c(ws, ws_bytes);
     c.take<SortPlan>(1);
@@ -1152,7 +1150,7 @@ static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t 
     // B = 65 536 on 128 workgroups of 512 keys 114 us against 89 us on 32 of 2048, B = 262 144 on 256 of 1024 keys 207 against 147 us per fused
     // loss -- every digit pass makes each thread scan one histogram row over ALL workgroups, and a barrier costs more the more arrive.
     const int maxg = gm_max_coresident() < GM_MAXG ? gm_max_coresident() : GM_MAXG;
-    static const int tile_env = []() { const char* e = getenv("RECNOW_GROUP_TILE"); return e ? atoi(e) : 0; }();      // A/B switch: 512 / 1024 / 2048
+    static const int tile_env = rn_env_int("RECNOW_GROUP_TILE", 0);      // A/B switch: 512 / 1024 / 2048
     int tile = RN_TILE;
     if (raw == 0 && (tile_env == 512 || tile_env == 1024) && rn_cdiv(B, tile_env) <= maxg) tile = tile_env;
     if (tile_env == 4096 || (tile_env == 0 && B >= GM_TILE4096_FROM)) tile = 4096;
@@ -1162,7 +1160,7 @@ static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t 
     GroupMidCtl* ctl = (GroupMidCtl*)tail;
     int* headcnt = (int*)(tail + rn_align(sizeof(GroupMidCtl)));
     RN_HIP(hipMemsetAsync(ctl, 0, sizeof(GroupMidCtl), st));
-    static const bool dbg_timeout = []() { const char* e = getenv("RECNOW_DEBUG_GROUP_TIMEOUT"); return e && e[0] == '1'; }();
+    static const bool dbg_timeout = rn_env_int("RECNOW_DEBUG_GROUP_TIMEOUT", 0) == 1;
     if (dbg_timeout) RN_HIP(hipMemsetAsync(&ctl->err, 1, sizeof(int), st));      // tests: every barrier reports the time-out at once
     const int g = rn_cdiv(B, tile);
 #define GM_LAUNCH(T, R)                                                                                                                          \
@@ -1196,8 +1194,7 @@ static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t 
 int rn_group_mid_raw(const void* group, int dtype, int64_t B, uint8_t* solo, int32_t* order, int32_t* seg_id, int32_t* seg_first, int32_t* super_id,
                      int32_t* n_seg, void* ws, size_t ws_bytes, hipStream_t st, const RnTileFwd* pack, unsigned long long* zero1, int* zeroed, int* packed) {
     if (packed) *packed = 0;
-    static const bool on = []() { const char* e = getenv("RECNOW_GROUP_RAW"); return !e || e[0] != '0'; }();      // A/B switch
-    if (!on || B <= GS_MAXB || (dtype != RECNOW_KEY_F32 && dtype != RECNOW_KEY_I32) || !solo || !ws) return RECNOW_EUNSUPPORTED;
+    if (B <= GS_MAXB || (dtype != RECNOW_KEY_F32 && dtype != RECNOW_KEY_I32) || !solo || !ws) return RECNOW_EUNSUPPORTED;
     if (ws_bytes < recnow_group_segments_workspace_bytes(B, 1)) return RECNOW_EWORKSPACE;
     return rn_group_coop(dtype == RECNOW_KEY_F32 ? 1 : 2, (const uint32_t*)group, solo, B, 1, 1, order, seg_id, seg_first, super_id, n_seg, ws, ws_bytes, st, pack,
                          zero1, zeroed, packed);

@@ -389,8 +389,7 @@ extern "C" int recnow_senet_fused_fwd(const float* const* fields, int F, int D, 
     if (B == 0) return RECNOW_OK;
     if (!fields || !W1 || !W2 || !out || !sq_save || !h_save || !w_save) return RECNOW_EINVAL;
     const SfDims dm = {F, D, M, act1, act2, (b1 || b2) ? 1 : 0};
-    static const bool tile8 = []() { const char* e = getenv("RECNOW_SENET_TILE8"); return !e || e[0] != '0'; }();      // A/B switch
-    if (tile8 && sf8_ok(F, D, M) && ((uintptr_t)out & 15) == 0) {
+    if (sf8_ok(F, D, M) && ((uintptr_t)out & 15) == 0) {
         const size_t lds = sf8_lds_floats(F, M) * sizeof(float);
         if (lds > 64 * 1024) {
             static std::atomic<bool> raised[64];
@@ -440,14 +439,11 @@ extern "C" int recnow_senet_fused_bwd(const float* const* fields, float* const* 
     const size_t lds = ((size_t)F * (M + 1) + (size_t)M * (F + 1) + 7 * SF_R * SF_RS) * sizeof(float);
     const int nacc = (nout + 255) / 256;
     // one resident wave of workgroups (rows are grid-strided): every further workgroup costs a weight fill and a slab of partial sums that
-    // the column sum reads back (as the DCNLayer backward); RECNOW_SENET_RESIDENT=0 is the A/B switch: 0.85 -> 0.78 ms for the layer's step at B = 131 072; the forward measured the same either way
-    static const bool resident = []() { const char* e = getenv("RECNOW_SENET_RESIDENT"); return !e || e[0] != '0'; }();
+    // the column sum reads back (as the DCNLayer backward): 0.85 -> 0.78 ms for the layer's step at B = 131 072; the forward measured the same either way
 #define SF_BWD(NA) do {                                                                                                            \
-        if (resident) {                                                                                                            \
-            int occ = 0;                                                                                                           \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_senet_fused_bwd<NA>, 256, lds) != hipSuccess || occ < 1) occ = 1; \
-            if (nb > 256 * occ) nb = 256 * occ;                                                                                    \
-        }                                                                                                                          \
+        int occ = 0;                                                                                                               \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_senet_fused_bwd<NA>, 256, lds) != hipSuccess || occ < 1) occ = 1; \
+        if (nb > 256 * occ) nb = 256 * occ;                                                                                        \
         hipLaunchKernelGGL(k_senet_fused_bwd<NA>, nb, 256, lds, st, fields, dfields, dm, B, W1, W2, dout, sq_save, h_save, w_save, part); \
     } while (0)
     if (nacc <= 3) SF_BWD(3);

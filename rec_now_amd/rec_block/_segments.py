@@ -41,8 +41,7 @@ class Segments(object):
         time-out (n_seg = -1; it leaves the identity grouping behind, so nothing downstream walks out of bounds)."""
         n = int(self.n_seg[0].item())
         if n < 0:
-            raise RuntimeError('rec_now_amd: the cooperative grouping kernel timed out at a grid barrier (workgroups not co-resident); '
-                               'set RECNOW_GROUP_COOP=0 to use the multi-launch route')
+            raise RuntimeError('rec_now_amd: the cooperative grouping kernel timed out at a grid barrier (workgroups not co-resident)')
         return n
 
 
