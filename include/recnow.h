@@ -262,7 +262,7 @@ typedef struct recnow_gemm_desc {
      * operand mode).  DCN-v2 uses it for the N gate columns so that N*S + N = 130 runs as exactly 128 MFMA columns. */
     const float* sp_bx; float* sp_cx; int64_t sp_bx_ks, sp_bx_rs, sp_cx_ms, sp_cx_rs; int sp_r; int sp_pad;
     /* Rank-R epilogue update (lean 128x128 kernels, batch 1): before bias-activation / emul,
-     *   v[m][n] += sum_{r < eu_r <= 4} eu_p[m*eu_pms + r] * eu_q[r*eu_qrs + n*eu_qns]  (K = 128 + 2 as exactly 128). */
+     *   v[m][n] += sum_{r < eu_r <= 4} eu_p[m*eu_pms + r] * eu_q[r*eu_qrs + n*eu_qns]  (K = 128 + 2 as exactly 128).  Never split over K. */
     const float* eu_p; const float* eu_q; int64_t eu_pms, eu_qrs, eu_qns; int eu_r; int eu_pad;
     double prof_flops;                /* algorithmic flops of this product for the measurement hook (0: 2*M*N*K*batch);
                                          callers that zero-pad K or move columns to a side product state the true count */

@@ -56,7 +56,9 @@ static inline GemmCfg pick_cfg(const recnow_gemm_desc* d, const RnDispatchEnv& e
 static inline void pick_split(const recnow_gemm_desc* d, const GemmCfg& c, int* splitk, int* kchunk, int slots = 512) {
     const long long tiles = (long long)rnd_cdiv(d->M, c.BM) * rnd_cdiv(d->N, c.BN) * d->batch;
     int s = 1;
-    if (tiles < slots && !d->as_out && !d->c2_mode && !d->mid_V) {      // fused side / second outputs need the whole K in one workgroup
+    // fused side / second outputs and the rank-R update need the whole K in one workgroup (the slab reduce applies neither)
+    const bool whole_k = d->as_out || d->c2_mode || d->mid_V || d->eu_r > 0;
+    if (tiles < slots && !whole_k) {
         s = (int)((slots + tiles - 1) / tiles);          // 256 CUs x 2 resident workgroups (256..511 tiles left half the slots empty until round 2)
         const int maxs = d->K / (8 * 32);      // at least 8 k-tiles per slice
         if (s > maxs) s = maxs;
@@ -64,7 +66,7 @@ static inline void pick_split(const recnow_gemm_desc* d, const GemmCfg& c, int* 
     }
     // accuracy, not occupancy: an fp32 accumulator that walks K >= 16384 terms in sequence carries ~sqrt(K) roundings (the K = 32768
     // weight gradients of PLE sat at 0.95 of the 1e-5 parity bound); slabs of <= 8192 terms, summed in fp64 by the reduce, halve that
-    if (s == 1 && d->K >= 16384 && !d->as_out && !d->c2_mode && !d->mid_V && d->c_perm_s == 0) s = d->K / 8192;
+    if (s == 1 && d->K >= 16384 && !whole_k && d->c_perm_s == 0) s = d->K / 8192;
     int kc = rnd_cdiv(rnd_cdiv(d->K, s), 32) * 32;
     if (kc < 32) kc = 32;
     s = rnd_cdiv(d->K, kc);

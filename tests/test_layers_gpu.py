@@ -595,6 +595,10 @@ def _act_np(v, act):
     return [v, np.maximum(v, 0), np.tanh(v), 1 / (1 + np.exp(-v))][act]
 
 
+FUZZ_C_ELEM = 1e-6          # per-element product bound, derived in tests/test_gemm_routes_gpu.py (C_ELEM)
+FUZZ_TANH_ABS = 1.5e-7      # rn_tanh, |x| >= 0.25 (tests/test_gemm_routes_gpu.py TANH_ABS)
+
+
 def _actgrad_np(y, act):
     return [np.ones_like(y), (y > 0).astype(np.float64), 1 - y * y, y * (1 - y)][act]
 
@@ -661,6 +665,20 @@ def test_gemm_fuzz(dev, seed):
         out = out.transpose(0, 2, 1)
     bound = 3e-7 * mag.max() + 2e-6
     assert np.abs(out - ref).max() <= bound, (M, N, K, batch, ta, tb, a_mode, b_mode, act, use_bias, use_emul, accum, c_trans)
+    # per element (tests/test_gemm_routes_gpu.py C_ELEM): the product's C_ELEM |A'||B'|, carried through the activation (Lipschitz factor and
+    # its absolute error, csrc/common.hpp rn_act), the emul factor |E| and one rounding each of the bias, emul and accumulate steps
+    u = 2.0 ** -23
+    z = (A64 @ B64) + (bias[:, None, :] if use_bias else 0.0)
+    y = _act_np(z, act)
+    err = FUZZ_C_ELEM * mag + u * np.abs(z)
+    err = [1.0, 1.0, 1.0, 0.25][act] * err + [0.0, 0.0, FUZZ_TANH_ABS, 0.0][act] + (2.0 ** -21 * np.abs(y) if act in (2, 3) else 0.0)
+    if use_emul:
+        f = E if use_emul == 1 else _actgrad_np(E.astype(np.float64), e_act)
+        err = err * np.abs(f) + 3 * u * np.abs(y * f)
+    if accum:
+        err = err + u * (np.abs(ref) + np.abs(C0.transpose(0, 2, 1) if c_trans else C0))
+    worst = np.abs(out - ref) / err
+    assert worst.max() <= 1.0, ('per-element error %.3g of its bound' % worst.max(), M, N, K, batch, ta, tb, a_mode, b_mode, act, use_emul, accum)
 
 
 # ---- layer shape sweeps at sizes that reach the lean / split-K / head kernels (the small cases above mostly run the general
