@@ -602,6 +602,25 @@ int recnow_attention_dot_fwd(const float* user, const float* doc, int64_t B, int
 int recnow_attention_dot_bwd(const float* user, const float* doc, const float* dmat, const float* dsum, int64_t B, int L,
                              int D, int filter_neg, float* duser, float* ddoc, void* stream);
 
+/* attention_by_dnn (DIN attention unit, ABI 8): rec_now/rec_block/attention.py:41-82.  user (B,L,D), doc (B,D), nl Dense
+ * layers of widths dims_host[0..nl) (a HOST array; dims_host[nl-1] must be 1), kernels_host / biases_host: HOST arrays of nl
+ * DEVICE pointers, kernel 0 (2D, dims[0]) with the user rows first, kernel i (dims[i-1], dims[i]), row-major (Keras (in, out));
+ * every bias present.  act (RECNOW_ACT_*) on all Dense layers but the last:
+ *   logit[b,l] = Dense stack([user[b,l] | doc[b]]),  s = sigmoid(logit),  mat[b] = sum_l s user[b,l],  score_sum[b] = sum_l s
+ * No (B,L,H) or (B,L,2D) tensor is formed.  Backward recomputes s; dmat (B,D) / dsum (B) may be NULL (no gradient from that
+ * output); duser, ddoc required; dkernels_host / dbiases_host (HOST arrays of nl DEVICE pointers) may be NULL, and so may each
+ * entry.  The parameter gradients are sums over per-workgroup partials in a fixed order (bit-identical from run to run).
+ * ws: recnow_attention_dnn_workspace_bytes(..., backward) bytes for that direction, bounded independently of B and L
+ * (0 when B or L is 0).  D > 256, a width > 256 or nl > 4: RECNOW_EUNSUPPORTED. */
+size_t recnow_attention_dnn_workspace_bytes(int64_t B, int L, int D, int nl, const int* dims_host, int backward);
+int recnow_attention_dnn_fwd(const float* user, const float* doc, int64_t B, int L, int D, int nl, const int* dims_host,
+                             const float* const* kernels_host, const float* const* biases_host, int act, float* mat,
+                             float* score_sum, void* ws, size_t ws_bytes, void* stream);
+int recnow_attention_dnn_bwd(const float* user, const float* doc, int64_t B, int L, int D, int nl, const int* dims_host,
+                             const float* const* kernels_host, const float* const* biases_host, int act, const float* dmat,
+                             const float* dsum, float* duser, float* ddoc, float* const* dkernels_host,
+                             float* const* dbiases_host, void* ws, size_t ws_bytes, void* stream);
+
 /* focal_crossentropy_loss: rec_now/rec_block/focal_loss.py:12-66.  alpha <= 0 / gamma <= 0 switch the respective factor
  * off (the reference's `if alpha:` / `if gamma:`).  loss_elem (B) and/or loss_mean (1) may be NULL; the mean is summed in
  * double in a fixed order (ws: recnow_focal_loss_workspace_bytes).

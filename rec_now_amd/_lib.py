@@ -91,6 +91,9 @@ SIGNATURES = {
     'recnow_senet_fused_bwd': (_I, [_P, _P, _I, _I, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_attention_dot_fwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P]),
     'recnow_attention_dot_bwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
+    'recnow_attention_dnn_workspace_bytes': (_Z, [_L, _I, _I, _I, _P, _I]),
+    'recnow_attention_dnn_fwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    'recnow_attention_dnn_bwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_focal_loss_workspace_bytes': (_Z, [_L]),
     'recnow_focal_loss_fwd': (_I, [_P, _P, _L, _F, _F, _P, _P, _P, _Z, _P]),
     'recnow_focal_loss_bwd': (_I, [_P, _P, _L, _F, _F, _I, _P, _P, _F, _P, _P]),
@@ -136,7 +139,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 7      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 8      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -1,9 +1,13 @@
-"""attention_by_dot_product -- drop-in for rec_now/rec_block/attention.py:12-38
-(/root/reference/rec_now/rec_block/attention.py).  One fused HIP kernel per direction (HBM-bound: the (B,L,D) user
-embeddings are read once forward, once backward with the scores recomputed)."""
+"""attention_by_dot_product and attention_by_dnn -- drop-ins for rec_now/rec_block/attention.py:12-38 and :41-82
+(/root/reference/rec_now/rec_block/attention.py).  One fused HIP kernel per direction each: the dot product is HBM-bound (the
+(B,L,D) user embeddings are read once forward, once backward with the scores recomputed); the DIN unit runs its Dense stack per
+tile of positions on the exact-fp32 matrix cores without forming any (B,L,H) activation (csrc/attention_dnn.hip)."""
+import ctypes
+
 import torch
 
 from .. import _lib
+from ..layers._keras import Layer, activation_code
 
 
 class _AttnDotFunction(torch.autograd.Function):
@@ -46,3 +50,132 @@ def attention_by_dot_product(user_emb, doc_emb, filter_neg=False):
         attn_mat (B, D) = sum_l user_emb[:, l] * score_l,  attn_score_sum (B, 1) = sum_l score_l.
     """
     return _AttnDotFunction.apply(user_emb, doc_emb, filter_neg)
+
+
+_DIN_MAX_WIDTH = 256
+_DIN_MAX_HIDDEN = 3
+
+
+class _AttnDnnFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, user_emb, doc_emb, dims, act, *params):
+        u = _lib.f32c(user_emb, 'user_emb')
+        d = _lib.f32c(doc_emb, 'doc_emb')
+        B, L, D = u.shape
+        nl = len(dims)
+        ks = [_lib.f32c(p, 'kernel') for p in params[:nl]]
+        bs = [_lib.f32c(p, 'bias') for p in params[nl:]]
+        dims_c = (ctypes.c_int * nl)(*dims)
+        kp = (ctypes.c_void_p * nl)(*[k.data_ptr() for k in ks])
+        bp = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in bs])
+        mat = torch.empty((B, D), dtype=torch.float32, device=u.device)
+        ssum = torch.empty((B, 1), dtype=torch.float32, device=u.device)
+        ws = _lib.workspace(_lib.load().recnow_attention_dnn_workspace_bytes(B, L, D, nl, dims_c, 0), u.device)
+        _lib.call('recnow_attention_dnn_fwd', _lib.ptr(u), _lib.ptr(d), B, L, D, nl, dims_c, kp, bp, act, _lib.ptr(mat), _lib.ptr(ssum),
+                  _lib.ptr(ws), ws.numel(), _lib.stream())
+        ctx.save_for_backward(u, d, *ks, *bs)
+        ctx.dims, ctx.act = tuple(dims), act
+        return mat, ssum
+
+    @staticmethod
+    def backward(ctx, dmat, dsum):
+        u, d, *params = ctx.saved_tensors
+        dims, nl = ctx.dims, len(ctx.dims)
+        ks, bs = params[:nl], params[nl:]
+        B, L, D = u.shape
+        dmat = _lib.f32c(dmat, 'grad') if dmat is not None else None
+        dsum = _lib.f32c(dsum, 'grad').reshape(-1) if dsum is not None else None
+        du, dd = torch.empty_like(u), torch.empty_like(d)
+        dks = [torch.empty_like(k) for k in ks]
+        dbs = [torch.empty_like(b) for b in bs]
+        dims_c = (ctypes.c_int * nl)(*dims)
+        ptrs = lambda ts: (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts])       # noqa: E731
+        ws = _lib.workspace(_lib.load().recnow_attention_dnn_workspace_bytes(B, L, D, nl, dims_c, 1), u.device)
+        _lib.call('recnow_attention_dnn_bwd', _lib.ptr(u), _lib.ptr(d), B, L, D, nl, dims_c, ptrs(ks), ptrs(bs), ctx.act, _lib.ptr(dmat),
+                  _lib.ptr(dsum), _lib.ptr(du), _lib.ptr(dd), ptrs(dks), ptrs(dbs), _lib.ptr(ws), ws.numel(), _lib.stream())
+        return (du, dd, None, None, *dks, *dbs)
+
+
+class DinAttention(Layer):
+    """The weights of attention_by_dnn: Dense layers `layer{i}` (kernel (in, out), bias (out,)), the first taking [user | doc] (2D).
+
+    Unlike the reference's keras.Sequential, which maps the concatenated (B, L, 2D) input to logits, calling this module runs the
+    whole attention unit: `model(user_emb, doc_emb)` returns (attn_mat (B, D), attn_score_sum (B, 1)) with these weights, on one
+    fused HIP kernel per direction (csrc/attention_dnn.hip).  It builds lazily from the first user_emb's D."""
+
+    def __init__(self, dnn_dims, dnn_activation='relu', **kwargs):
+        super().__init__(**kwargs)
+        dims = [int(v) for v in dnn_dims]
+        if not dims or any(v < 1 for v in dims):
+            raise ValueError('dnn_dims must be a non-empty list of positive widths, got %r' % (list(dnn_dims),))
+        if dims[-1] != 1:
+            raise ValueError('the last of dnn_dims must be 1 (the attention logit), got %r' % (dims,))
+        if len(dims) - 1 > _DIN_MAX_HIDDEN:
+            raise NotImplementedError('attention_by_dnn kernels cover at most %d hidden layers (the reference has no limit); got %d'
+                                      % (_DIN_MAX_HIDDEN, len(dims) - 1))
+        if max(dims) > _DIN_MAX_WIDTH:
+            raise NotImplementedError('attention_by_dnn kernels cover Dense widths <= %d (the reference has no limit); got %r'
+                                      % (_DIN_MAX_WIDTH, dims))
+        code, fn = activation_code(dnn_activation)
+        if fn is not None:
+            raise NotImplementedError('attention_by_dnn fuses the activations linear, relu, tanh and sigmoid between its Dense layers; '
+                                      'a callable activation (%r) cannot run inside the fused kernel' % (dnn_activation,))
+        self.dnn_dims = dims
+        self.dnn_activation = dnn_activation
+        self.act_code = code
+
+    def build(self, input_shape):
+        """Creates `layer{i}/kernel` (in, dims[i]) and `layer{i}/bias` (dims[i],): glorot_uniform and zeros, as keras.layers.Dense."""
+        D = int(input_shape[0][-1]) if isinstance(input_shape[0], (list, tuple)) else int(input_shape[-1])
+        if D > _DIN_MAX_WIDTH:
+            raise NotImplementedError('attention_by_dnn kernels cover embedding_dim <= %d (the reference has no limit); got %d'
+                                      % (_DIN_MAX_WIDTH, D))
+        self.embedding_dim = D
+        self.kernels, self.biases = [], []
+        width = 2 * D
+        for i, dim in enumerate(self.dnn_dims):
+            self.kernels.append(self.add_weight('layer%d/kernel' % i, shape=[width, dim], initializer='glorot_uniform'))
+            self.biases.append(self.add_weight('layer%d/bias' % i, shape=[dim], initializer='zeros'))
+            width = dim
+        self.built = True
+
+    def forward(self, user_emb, doc_emb):
+        for t, what, nd in ((user_emb, 'user_emb', 3), (doc_emb, 'doc_emb', 2)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError('%s must be a torch.Tensor, got %s' % (what, type(t)))
+            if t.dim() != nd:
+                raise ValueError('user_emb must be (B, L, D) and doc_emb (B, D); got %s and %s'
+                                 % (tuple(user_emb.shape), tuple(doc_emb.shape)))
+        if user_emb.shape[0] != doc_emb.shape[0] or user_emb.shape[2] != doc_emb.shape[1]:
+            raise ValueError('user_emb must be (B, L, D) and doc_emb (B, D); got %s and %s' % (tuple(user_emb.shape), tuple(doc_emb.shape)))
+        if not self.built:
+            self._build_device = user_emb.device
+            self.build((tuple(user_emb.shape), tuple(doc_emb.shape)))
+        if user_emb.shape[2] != self.embedding_dim:
+            raise ValueError('this attention model was built for embedding_dim %d, got %d' % (self.embedding_dim, user_emb.shape[2]))
+        return self.call(user_emb, doc_emb)
+
+    def call(self, user_emb, doc_emb):
+        _lib.require_gpu(user_emb, 'user_emb')
+        _lib.require_gpu(doc_emb, 'doc_emb')
+        return _AttnDnnFunction.apply(user_emb, doc_emb, tuple(self.dnn_dims), self.act_code, *self.kernels, *self.biases)
+
+
+def attention_by_dnn(user_emb, doc_emb, dnn_dims, dnn_activation='relu', dnn_name='din'):
+    """DIN attention: a Dense stack scores each of the L user embeddings against the item embedding.
+
+    Args:
+        user_emb: (B, L, D);  doc_emb: (B, D);
+        dnn_dims: widths of the Dense layers; a 1 is appended to this list when its last entry is not 1 (as the reference does);
+        dnn_activation: 'relu' (default), 'tanh', 'sigmoid', 'linear' or None, on every Dense layer but the last;
+        dnn_name: name of the returned model (its weights are `layer{i}/kernel`, `layer{i}/bias`).
+    Returns:
+        attn_mat (B, D) = sum_l sigmoid(logit_l) user_emb[:, l],  attn_score_sum (B, 1) = sum_l sigmoid(logit_l),  and the model
+        (a DinAttention: `model(user_emb, doc_emb)` recomputes both outputs with the same weights).
+    Limits of the fused kernels (NotImplementedError): D and every width <= 256, at most 3 hidden layers, a named activation.
+    """
+    if dnn_dims[-1] != 1:
+        dnn_dims.append(1)
+    model = DinAttention(dnn_dims, dnn_activation=dnn_activation, name=dnn_name)
+    attn_mat, attn_score_sum = model(user_emb, doc_emb)
+    return attn_mat, attn_score_sum, model

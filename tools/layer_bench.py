@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,ipnn,senet,attn,focal,embed]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,ipnn,senet,attn,din,focal,embed]"""
 import os
 import sys
 
@@ -246,6 +246,56 @@ def attn():
         print('   replayed from a HIP graph (GPU time of the step): %.3f ms  %.0f GB/s' % (mg, 12.0 * B * L * D / mg / 1e6))
 
 
+def din_ref_eager(u, d, ks, bs):
+    """attention_by_dnn as the reference computes it (rec_block/attention.py:62-82): tile + cat, the Dense stack, sigmoid, sums."""
+    x = torch.cat([u, d.unsqueeze(1).expand(-1, u.shape[1], -1)], dim=-1)
+    for i, (k, b) in enumerate(zip(ks, bs)):
+        x = torch.nn.functional.linear(x, k.t(), b)
+        if i < len(ks) - 1:
+            x = torch.relu(x)
+    s = torch.sigmoid(x)
+    return (u * s).sum(1), s.squeeze(2).sum(1, keepdim=True)
+
+
+def din():
+    """attention_by_dnn at the attention row's B, L, D with dims [80, 40, 1], and at B 4096, L 100, D 64, dims [200, 80, 1]: forward and
+    backward time, TFLOP/s of algorithmic flops (forward 2 B L (D H1 + H1 H2 + H2) + 2 B D H1; backward twice that, the recomputed forward
+    not counted) and their fraction of the 157.3 TF exact-fp32 MFMA peak, next to the reference algorithm in torch eager."""
+    from rec_now_amd.rec_block.attention import attention_by_dnn
+    for B, L, D, dims in ((131072, 50, 16, [80, 40, 1]), (4096, 100, 64, [200, 80, 1])):
+        u = (torch.rand(B, L, D, device=dev) - 0.5).requires_grad_(True)
+        d = (torch.rand(B, D, device=dev) - 0.5).requires_grad_(True)
+        gm, gs = torch.randn(B, D, device=dev), torch.randn(B, 1, device=dev)
+        _, _, model = attention_by_dnn(u[:1], d[:1], list(dims))
+        ks = [model.named_weights()['layer%d/kernel' % i] for i in range(len(dims))]
+        bs = [model.named_weights()['layer%d/bias' % i] for i in range(len(dims))]
+        widths = [D] + dims
+        flops_f = 2.0 * B * L * sum(widths[i] * widths[i + 1] for i in range(len(dims))) + 2.0 * B * D * dims[0]
+        flops_b = 2.0 * flops_f
+
+        def bwd_of(fn):
+            mat, ssum = fn()
+            loss = (mat * gm).sum() + (ssum * gs).sum()
+
+            def step():
+                u.grad = d.grad = None
+                model.zero_grad(set_to_none=True)
+                loss.backward(retain_graph=True)
+            return step
+
+        fused = lambda: model(u, d)                               # noqa: E731
+        ref = lambda: din_ref_eager(u, d, ks, bs)                 # noqa: E731
+        ms_f, ms_b = timeit(fused), timeit(bwd_of(fused))
+        torch.cuda.empty_cache()
+        rf, rb = timeit(ref), timeit(bwd_of(ref))
+        tf_f, tf_b = flops_f / ms_f / 1e9, flops_b / ms_b / 1e9
+        print('attention_by_dnn B=%d L=%d D=%d dims=%s : fwd %.3f ms %.1f TFLOP/s (%.2f of 157.3), bwd %.3f ms %.1f TFLOP/s (%.2f) | '
+              'reference in torch eager: fwd %.3f ms, bwd %.3f ms -> speedup fwd %.1fx bwd %.1fx'
+              % (B, L, D, dims, ms_f, tf_f, tf_f / 157.3, ms_b, tf_b, tf_b / 157.3, rf, rb, rf / ms_f, rb / ms_b))
+        del u, d, model, ks, bs
+        torch.cuda.empty_cache()
+
+
 def focal():
     from rec_now_amd.rec_block.focal_loss import focal_crossentropy_loss
     B = 1 << 22
@@ -356,7 +406,7 @@ def star(mode):
 
 
 if __name__ == '__main__':
-    which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'ipnn', 'senet', 'attn', 'focal', 'embed']
+    which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'ipnn', 'senet', 'attn', 'din', 'focal', 'embed']
     if 'fm' in which:
         fm()
     if 'dcn' in which:
@@ -375,6 +425,6 @@ if __name__ == '__main__':
     for mode in ('star', 'stacked'):
         if mode in which:
             star(mode)
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('focal', focal), ('embed', embed)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed)):
         if name in which:
             fn()
