@@ -2,8 +2,13 @@
 """Headline benchmark (BASELINE.json): samples/sec, forward+backward, in-batch pairwise loss + 3-layer DCN-v2
 (DCNMixLayer, low-rank 64, 2 experts), global batch B = 65536, 64 fields x 16-dim = 1024 features, on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run does what its headline figure needs and nothing else: set-up, warm-up, the K timed steps, --dump-outputs, and the JSON line
+(`roofline` from the event hook of the timed steps; `parity` null).  `--full` adds, after the timed region and in this order, everything
+else the benchmark measures and checks: the host enqueue time, the exclusive-time account of the roofline, the collectives' price (N > 1),
+the other arithmetic of the products, the parity step against the fp64 oracle and the CPU baseline.  The timed steps are the same either way.
 
 A step = one forward + backward pass of the hot path over one resident batch (inputs already in HBM):
     x (B,1024) -> DCNMixLayer(dim_sub_space=64, num_layer=3, num_expert=2) -> MultiDenseLayer(1,1) head -> (B,) scores
@@ -20,12 +25,12 @@ roofline:     the dominant kernel is the exact-fp32 MFMA GEMM `k_gemm<128,128,..
               kernels `k_mix_mid_fwd/bwd` as achieved GB/s of their ALGORITHMIC bytes against the 8 TB/s HBM3E spec.
               `traffic` (PMC bytes per launch) is read from profiles/traffic.json only while that file's hash of the kernel
               sources matches this build; otherwise it is null and `traffic_stale` says so.
-parity:       after the timed region ONE more step runs on inputs scaled so that the scores are of O(1) (loss != ln 2; the
+parity:       (--full) after the timed region ONE more step runs on inputs scaled so that the scores are of O(1) (loss != ln 2; the
               timed inputs give scores ~1e-8, where a library returning zeros would print the same loss) and is held to 1e-5
               (north_star) against the fp64 oracle: (a) ~256 rows of whole groups, scores and d loss / d x; (b) unless
               --no-cpu-baseline: the WHOLE batch -- loss, pair count, scores, d loss / d x and every one of the 17 weight gradients
               against oracle/dense_ref.py evaluated chunk-wise in fp64.  The fp32 CPU port's figures are reported beside.
-cpu_baseline: rank 0, N = 1 only.  `value`: ONE step of the same workload at the full batch (B = 65536) by the CPU port:
+cpu_baseline: (--full) rank 0, N = 1 only.  `value`: ONE step of the same workload at the full batch (B = 65536) by the CPU port:
               oracle/dense_ref.py layers in row chunks (torch CPU fp32, two passes: scores, then forward + backward per chunk
               with the pair gradient) + the segment-based C pair loss (oracle/pairs_oracle.c, OpenMP); the reference's own dense
               (B,B) formulation cannot run at this B (>= 100 GB of temporaries), so its figure at B = 8192 is kept beside it in
@@ -591,9 +596,9 @@ def main_models(args, world, rank, dev, json_fd, use_dist):
         cnt, ms, fl, by = (ctypes.c_int * N_TAGS)(), (ctypes.c_double * N_TAGS)(), (ctypes.c_double * N_TAGS)(), (ctypes.c_double * N_TAGS)()
         _lib.check(lib.recnow_prof_collect(cnt, ms, fl, by), 'recnow_prof_collect')
         lib.recnow_prof_enable(0)
-    account = step_account(lib, run_step, sync, steps=4) if prof else None
+    account = step_account(lib, run_step, sync, steps=4) if prof and args.full else None
     comm = None
-    if use_dist:
+    if use_dist and args.full:
         def timed_ms(n=6):
             sync()
             c0 = time.perf_counter()
@@ -637,114 +642,116 @@ def main_models(args, world, rank, dev, json_fd, use_dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    # ---- the gate (untimed): one more step, every rank holds its rows to the fp64 oracle, the loss stage and the reduced gradients to the gathered batch
-    R, PO = _oracle()
-    loss_q = run_step()
-    torch.cuda.synchronize()
-    named_np = {k: v.detach().cpu().numpy() for k, v in named.items()}
-    out_gpu = last['out'].detach().cpu().numpy()
-    dx_gpu = (torch.cat([v.grad for v in xs], dim=1) if args.config == 'c4' else xs[0].grad).cpu().numpy()
-    count_glob = float(last['count'].item())
-    dx_gpu = dx_gpu / (np.float32(count_glob) + np.float32(1e-10) if denom == 'eps' else max(count_glob, 1.0))      # x is not a parameter: the loss SUM's gradient
-    full_gate = not args.no_cpu_baseline
+    # ---- --full: the gate (untimed): one more step, every rank holds its rows to the fp64 oracle, the loss stage and the reduced gradients to the
+    # gathered batch; then the CPU baseline
     world_n = dist.get_world_size() if use_dist else 1
+    parity, cpu = None, None
+    if args.full:
+        R, PO = _oracle()
+        loss_q = run_step()
+        torch.cuda.synchronize()
+        named_np = {k: v.detach().cpu().numpy() for k, v in named.items()}
+        out_gpu = last['out'].detach().cpu().numpy()
+        dx_gpu = (torch.cat([v.grad for v in xs], dim=1) if args.config == 'c4' else xs[0].grad).cpu().numpy()
+        count_glob = float(last['count'].item())
+        dx_gpu = dx_gpu / (np.float32(count_glob) + np.float32(1e-10) if denom == 'eps' else max(count_glob, 1.0))      # x is not a parameter: the loss SUM's gradient
+        full_gate = not args.no_cpu_baseline
 
-    def gather(a):
-        if not use_dist:
-            return np.ascontiguousarray(a)
-        a = np.ascontiguousarray(a)
-        tt = torch.from_numpy(a)
-        if args.backend == 'nccl':
-            tt = tt.to(dev)
-        parts = [torch.empty_like(tt) for _ in range(world_n)]
-        dist.all_gather(parts, tt)
-        return torch.cat(parts).cpu().numpy()
-
-    def allsum64(v):
-        tt = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
-        if use_dist:
+        def gather(a):
+            if not use_dist:
+                return np.ascontiguousarray(a)
+            a = np.ascontiguousarray(a)
+            tt = torch.from_numpy(a)
             if args.backend == 'nccl':
                 tt = tt.to(dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.SUM)
-        return tt.cpu().numpy()
-    chunk = 512 if args.config == 'c4' else 2048
-    parity = {'tolerance': PARITY_TOL, 'loss': float(loss_q.item()), 'ranks': world_n}
-    worst = 0.0
-    if args.config == 'c4':
-        g_all, y_all, s_all = gather(groups), gather(labels), gather(out_gpu)
-        o_loss, _, o_pairs = PO.pairwise_bpr(g_all, y_all, s_all, grouped=True)
-        parity['gathered_batch_pairs_oracle'] = {'loss': rel_err(float(loss_q.item()), o_loss), 'pairs_gpu': int(count_glob), 'pairs_oracle': int(o_pairs)}
-        worst = parity['gathered_batch_pairs_oracle']['loss']
-        ok = int(count_glob) == int(o_pairs)
-        if full_gate:
-            fwd, wl = _c4_oracle(named_np, torch.float64, 64, 16, 3)
-            s64 = _chunked_fwd(fwd, x, torch.float64, chunk)
-            s64_all = gather(s64)
-            f_loss, ds_all, f_pairs = PO.pairwise_bpr(g_all, y_all, s64_all, grouped=True)
-            lo = sum(rank_rows[:rank])
-            dx64 = _chunked_bwd(fwd, x, ds_all[lo:lo + rows], torch.float64, chunk)
-    else:
-        if full_gate:
-            fwd, wl = _c5_oracle(named_np, torch.float64, ple, [[512, 256], [256, 128]])
-            l64 = _chunked_fwd(fwd, x, torch.float64, chunk)
-        else:
-            l64 = out_gpu.T.astype(np.float64)
-        # the listwise stage on the GPU's own logits (fp64, dense (G, B) form of the reference): lists live on one rank, so the global mean is sum / sum
-        lsum_g, nv_l, _ = _listwise_fp(groups, labels, out_gpu.T.astype(np.float64), torch.float64)
-        tot = allsum64(np.array([lsum_g, nv_l]))
-        parity['listwise_stage_oracle'] = {'loss': rel_err(float(loss_q.item()), tot[0] / max(tot[1], 1.0)), 'lists_gpu': int(count_glob), 'lists_oracle': int(tot[1])}
-        worst = parity['listwise_stage_oracle']['loss']
-        ok = int(count_glob) == int(tot[1])
-        if full_gate:
-            lsum64, nv64, dl64 = _listwise_fp(groups, labels, l64, torch.float64)
-            tot64 = allsum64(np.array([lsum64, nv64]))
-            f_loss = tot64[0] / max(tot64[1], 1.0)
-            dx64 = _chunked_bwd(fwd, x, dl64 / max(tot64[1], 1.0), torch.float64, chunk)
-            s64 = l64
-    if full_gate:
-        names = sorted(named)
-        flat = allsum64(np.concatenate([(wl[k].grad.numpy() if wl[k].grad is not None else np.zeros(tuple(wl[k].shape))).reshape(-1) for k in names]))
-        full = {'loss': rel_err(float(loss_q.item()), f_loss), 'outputs': rel_err(out_gpu if args.config == 'c4' else out_gpu.T, s64), 'dx': rel_err(dx_gpu, dx64)}
-        loc = torch.tensor([full['outputs'], full['dx']], dtype=torch.float64, device=dev)
-        if use_dist:
-            loc = loc if args.backend == 'nccl' else loc.cpu()
-            dist.all_reduce(loc, op=dist.ReduceOp.MAX)
-        full['outputs'], full['dx'] = float(loc[0].item()), float(loc[1].item())
-        off = 0
-        gsum = float(np.abs(ds_all).sum()) if args.config == 'c4' else None
-        for k in names:
-            n = named[k].numel()
-            ref = flat[off:off + n].reshape(tuple(named[k].shape))
-            off += n
-            # a gradient that is a sum cancelling to ~0 (the head bias under a pairwise loss): on the scale of its terms
-            full[k] = rel_err(named[k].grad.cpu().numpy(), ref, scale=gsum if (k == 'head.bias' and args.config == 'c4') else None)
-        parity['oracle_fp64_all_ranks'] = full
-        worst = max([worst] + list(full.values()))
-    parity['parity_max_rel'] = worst
-    parity['ok'] = bool(ok and worst <= PARITY_TOL)
+            parts = [torch.empty_like(tt) for _ in range(world_n)]
+            dist.all_gather(parts, tt)
+            return torch.cat(parts).cpu().numpy()
 
-    # ---- CPU baseline (rank 0 at N = 1 only): the fp32 port on a bounded sample of the same workload
-    cpu = None
-    if full_gate and world == 1 and not use_dist:
-        n_s = min(rows, 2048 if args.config == 'c4' else 8192)
-        ids = np.unique(groups)
-        sel = np.nonzero(np.isin(groups, ids[:max(1, int(len(ids) * n_s / rows))]))[0]          # whole groups, ~n_s rows
-        xs_, gs_, ys_ = np.ascontiguousarray(x[sel]), groups[sel], labels[sel]
-        c0 = time.perf_counter()
+        def allsum64(v):
+            tt = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
+            if use_dist:
+                if args.backend == 'nccl':
+                    tt = tt.to(dev)
+                dist.all_reduce(tt, op=dist.ReduceOp.SUM)
+            return tt.cpu().numpy()
+        chunk = 512 if args.config == 'c4' else 2048
+        parity = {'tolerance': PARITY_TOL, 'loss': float(loss_q.item()), 'ranks': world_n}
+        worst = 0.0
         if args.config == 'c4':
-            fwd32, _w = _c4_oracle(named_np, torch.float32, 64, 16, 3)
-            sc = _chunked_fwd(fwd32, xs_, torch.float32, chunk)
-            _, ds, _ = PO.pairwise_bpr(gs_, ys_, sc, grouped=True)
-            _chunked_bwd(fwd32, xs_, ds, torch.float32, chunk)
+            g_all, y_all, s_all = gather(groups), gather(labels), gather(out_gpu)
+            o_loss, _, o_pairs = PO.pairwise_bpr(g_all, y_all, s_all, grouped=True)
+            parity['gathered_batch_pairs_oracle'] = {'loss': rel_err(float(loss_q.item()), o_loss), 'pairs_gpu': int(count_glob), 'pairs_oracle': int(o_pairs)}
+            worst = parity['gathered_batch_pairs_oracle']['loss']
+            ok = int(count_glob) == int(o_pairs)
+            if full_gate:
+                fwd, wl = _c4_oracle(named_np, torch.float64, 64, 16, 3)
+                s64 = _chunked_fwd(fwd, x, torch.float64, chunk)
+                s64_all = gather(s64)
+                f_loss, ds_all, f_pairs = PO.pairwise_bpr(g_all, y_all, s64_all, grouped=True)
+                lo = sum(rank_rows[:rank])
+                dx64 = _chunked_bwd(fwd, x, ds_all[lo:lo + rows], torch.float64, chunk)
         else:
-            fwd32, _w = _c5_oracle(named_np, torch.float32, ple, [[512, 256], [256, 128]])
-            lg = _chunked_fwd(fwd32, xs_, torch.float32, chunk)
-            _, nvs, dl = _listwise_fp(gs_, ys_, lg, torch.float32)
-            _chunked_bwd(fwd32, xs_, dl / max(nvs, 1), torch.float32, chunk)
-        c_sec = time.perf_counter() - c0
-        cpu = {'value': len(sel) / c_sec, 'unit': 'samples/s', 'cores': torch.get_num_threads(), 'kind': 'port',
-               'sample': '1 step of fwd+bwd on %d rows of whole groups of the same batch (%.1f s): oracle/dense_ref.py layers in %d-row chunks on torch-CPU fp32 + '
-                         'the loss stage of the oracle; TF2 itself is not installable here' % (len(sel), c_sec, chunk)}
+            if full_gate:
+                fwd, wl = _c5_oracle(named_np, torch.float64, ple, [[512, 256], [256, 128]])
+                l64 = _chunked_fwd(fwd, x, torch.float64, chunk)
+            else:
+                l64 = out_gpu.T.astype(np.float64)
+            # the listwise stage on the GPU's own logits (fp64, dense (G, B) form of the reference): lists live on one rank, so the global mean is sum / sum
+            lsum_g, nv_l, _ = _listwise_fp(groups, labels, out_gpu.T.astype(np.float64), torch.float64)
+            tot = allsum64(np.array([lsum_g, nv_l]))
+            parity['listwise_stage_oracle'] = {'loss': rel_err(float(loss_q.item()), tot[0] / max(tot[1], 1.0)), 'lists_gpu': int(count_glob), 'lists_oracle': int(tot[1])}
+            worst = parity['listwise_stage_oracle']['loss']
+            ok = int(count_glob) == int(tot[1])
+            if full_gate:
+                lsum64, nv64, dl64 = _listwise_fp(groups, labels, l64, torch.float64)
+                tot64 = allsum64(np.array([lsum64, nv64]))
+                f_loss = tot64[0] / max(tot64[1], 1.0)
+                dx64 = _chunked_bwd(fwd, x, dl64 / max(tot64[1], 1.0), torch.float64, chunk)
+                s64 = l64
+        if full_gate:
+            names = sorted(named)
+            flat = allsum64(np.concatenate([(wl[k].grad.numpy() if wl[k].grad is not None else np.zeros(tuple(wl[k].shape))).reshape(-1) for k in names]))
+            full = {'loss': rel_err(float(loss_q.item()), f_loss), 'outputs': rel_err(out_gpu if args.config == 'c4' else out_gpu.T, s64), 'dx': rel_err(dx_gpu, dx64)}
+            loc = torch.tensor([full['outputs'], full['dx']], dtype=torch.float64, device=dev)
+            if use_dist:
+                loc = loc if args.backend == 'nccl' else loc.cpu()
+                dist.all_reduce(loc, op=dist.ReduceOp.MAX)
+            full['outputs'], full['dx'] = float(loc[0].item()), float(loc[1].item())
+            off = 0
+            gsum = float(np.abs(ds_all).sum()) if args.config == 'c4' else None
+            for k in names:
+                n = named[k].numel()
+                ref = flat[off:off + n].reshape(tuple(named[k].shape))
+                off += n
+                # a gradient that is a sum cancelling to ~0 (the head bias under a pairwise loss): on the scale of its terms
+                full[k] = rel_err(named[k].grad.cpu().numpy(), ref, scale=gsum if (k == 'head.bias' and args.config == 'c4') else None)
+            parity['oracle_fp64_all_ranks'] = full
+            worst = max([worst] + list(full.values()))
+        parity['parity_max_rel'] = worst
+        parity['ok'] = bool(ok and worst <= PARITY_TOL)
+
+        # ---- CPU baseline (rank 0 at N = 1 only): the fp32 port on a bounded sample of the same workload
+        if full_gate and world == 1 and not use_dist:
+            n_s = min(rows, 2048 if args.config == 'c4' else 8192)
+            ids = np.unique(groups)
+            sel = np.nonzero(np.isin(groups, ids[:max(1, int(len(ids) * n_s / rows))]))[0]          # whole groups, ~n_s rows
+            xs_, gs_, ys_ = np.ascontiguousarray(x[sel]), groups[sel], labels[sel]
+            c0 = time.perf_counter()
+            if args.config == 'c4':
+                fwd32, _w = _c4_oracle(named_np, torch.float32, 64, 16, 3)
+                sc = _chunked_fwd(fwd32, xs_, torch.float32, chunk)
+                _, ds, _ = PO.pairwise_bpr(gs_, ys_, sc, grouped=True)
+                _chunked_bwd(fwd32, xs_, ds, torch.float32, chunk)
+            else:
+                fwd32, _w = _c5_oracle(named_np, torch.float32, ple, [[512, 256], [256, 128]])
+                lg = _chunked_fwd(fwd32, xs_, torch.float32, chunk)
+                _, nvs, dl = _listwise_fp(gs_, ys_, lg, torch.float32)
+                _chunked_bwd(fwd32, xs_, dl / max(nvs, 1), torch.float32, chunk)
+            c_sec = time.perf_counter() - c0
+            cpu = {'value': len(sel) / c_sec, 'unit': 'samples/s', 'cores': torch.get_num_threads(), 'kind': 'port',
+                   'sample': '1 step of fwd+bwd on %d rows of whole groups of the same batch (%.1f s): oracle/dense_ref.py layers in %d-row chunks on torch-CPU fp32 + '
+                             'the loss stage of the oracle; TF2 itself is not installable here' % (len(sel), c_sec, chunk)}
 
     if rank == 0:
         out = {'metric': 'samples/sec fwd+bwd, %s' % ('cin_layer + fm_layer + in-batch pairwise, data-parallel' if args.config == 'c4' else 'ple_layer 3-task + listwise_loss_from_batch, data-parallel'),
@@ -754,8 +761,8 @@ def main_models(args, world, rank, dev, json_fd, use_dist):
                           'global_batch': total_rows, 'parallelism': 'dp%d' % world, 'input_grad': True,
                           'route': 'drop-in layers through autograd; gradients all-reduced per bucket from post-accumulate hooks under the backward pass '
                                    '(dp.OverlappedGradientReducer), loss statistics in the first bucket',
-                          'loss': float(loss.item())},
-               'roofline': roofline, 'parity': parity, 'parity_max_rel': parity['parity_max_rel']}
+                          'loss': float(loss.item()), 'full': args.full},
+               'roofline': roofline, 'parity': parity, 'parity_max_rel': parity['parity_max_rel'] if parity else None}
         if cpu is not None:
             out['cpu_baseline'] = cpu
         if use_dist:
@@ -783,7 +790,10 @@ def main():
                     'data-parallel MODEL steps of configs[3] / configs[4] at their per-rank size (16 384 / 32 768 rows per GPU; --rows overrides), through dp.OverlappedGradientReducer')
     ap.add_argument('--steps', type=int, default=20, help='timed steps; ms_per_step is their wall time over this number')
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also run everything else the benchmark measures and checks (host enqueue time, '
+                    'exclusive-time account, price of the collectives, the other arithmetic of the products, the parity gate against the fp64 oracle, '
+                    'the CPU baseline); a plain run prints the headline line only, from the same timed steps')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the whole-batch fp64 gate and the CPU baseline')
     ap.add_argument('--no-prof', action='store_true', help='do not record per-launch HIP events in the timed region')
     ap.add_argument('--graph', action='store_true', help='replay the step from captured HIP graphs (SURVEY 8f.1; one graph per phase / backward piece) '
                     'instead of enqueueing it eagerly')
@@ -810,8 +820,8 @@ def main():
                     help="arithmetic of the 18 products of the step: 'f32' exact fp32 MFMA; 'bf16x3' the split-precision kernels (fp32 operands as three "
                          "bf16 pieces, six bf16 MFMA terms, fp32 accumulation: per-product error <= 2^-25, same 1e-5 parity gate, not bit-identical); "
                          "'auto' (default): whichever is faster at this shard size under that gate -- bf16x3 from 32 768 rows per GPU (product route), "
-                         "f32 below (row-block kernels).  The other mode's step time is measured in the same run and reported beside the headline "
-                         "(`exact_f32` / `split_precision` at the end of the JSON line)")
+                         "f32 below (row-block kernels).  With --full the other mode's step time is measured in the same run and reported beside the "
+                         "headline (`exact_f32` / `split_precision` at the end of the JSON line)")
     ap.add_argument('--no-other', action='store_true', help='do not time the other arithmetic of the products behind the headline (profiling runs: one kernel family per trace)')
     ap.add_argument('--force-dist', action='store_true', help='initialise the RCCL process group even at world size 1 (exercises the N>1 code path on one GPU)')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl', help="process-group backend: 'nccl' (= RCCL over xGMI, the product path); 'gloo' is a "
@@ -1114,6 +1124,7 @@ def main():
     elapsed = time.perf_counter() - t0
     gc.enable()
     mark('timed region done')
+    loss_timed = float(loss.item())      # the step route's loss is a view of storage that every later step (--full) overwrites
     if args.dump_outputs and rank == 0:
         outs = {'loss': loss, 'n_pair': last['n_pair'], 'scores': last['scores'], 'dx': pstep.dx if pstep is not None else xd.grad,
                 'grad.head.kernel': model.head.kernel.grad, 'grad.head.bias': model.head.bias.grad}
@@ -1133,13 +1144,15 @@ def main():
         by = (ctypes.c_double * N_TAGS)()
         _lib.check(lib.recnow_prof_collect(cnt, ms, fl, by), 'recnow_prof_collect')
         lib.recnow_prof_enable(0)
-    # diagnostic: host time to ENQUEUE a step (no synchronisation inside): well below ms_per_step = the step is GPU-bound
-    h0 = time.perf_counter()
-    for _ in range(5):
-        run_step()
-    host_ms = (time.perf_counter() - h0) * 1e3 / 5
-    sync()
-    mark('host enqueue loop done')
+    # diagnostic (--full): host time to ENQUEUE a step (no synchronisation inside): well below ms_per_step = the step is GPU-bound
+    host_ms = None
+    if args.full:
+        h0 = time.perf_counter()
+        for _ in range(5):
+            run_step()
+        host_ms = (time.perf_counter() - h0) * 1e3 / 5
+        sync()
+        mark('host enqueue loop done')
     if args.hostprof:
         import cProfile
         import pstats
@@ -1151,13 +1164,13 @@ def main():
         sync()
         with open(args.hostprof, 'w') as fh:
             pstats.Stats(pr, stream=fh).sort_stats('cumulative').print_stats(45)
-    # diagnostics of the step route (untimed, after the timed region): the exclusive-time account and, under a process group, what the
+    # diagnostics of the step route (--full; untimed, after the timed region): the exclusive-time account and, under a process group, what the
     # collectives add to a step (the same step with RECNOW_DP_SKIP_COLLECTIVE semantics switched on for ten steps on every rank)
     account, comm = None, None
-    if pstep is not None and graph is None and not args.no_prof:
+    if args.full and pstep is not None and graph is None and not args.no_prof:
         account = step_account(lib, run_step, sync)
         mark('step account done')
-    if use_dist and pstep is not None and graph is None:
+    if args.full and use_dist and pstep is not None and graph is None:
         def timed_ms(n=10):
             sync()
             c0 = time.perf_counter()
@@ -1218,9 +1231,9 @@ def main():
                 roofline['exclusive_covered_ms_per_step'] = account['covered_ms_per_step']
                 roofline['exclusive_note'] = account['what']
                 roofline['exclusive_truncated_records'] = account['truncated_records']
-    # ---- the OTHER arithmetic, same run, same buffers (untimed by the headline): `exact_f32` beside a split-precision headline and vice versa
+    # ---- --full: the OTHER arithmetic, same run, same buffers (untimed by the headline): `exact_f32` beside a split-precision headline and vice versa
     other = None
-    if pstep is not None and graph is None and not args.no_input_grad and not args.no_other:
+    if args.full and pstep is not None and graph is None and not args.no_input_grad and not args.no_other:
         other_mode = 'f32' if precision == 'bf16x3' else 'bf16x3'
         _lib.call('recnow_set_gemm_precision', 1 if other_mode == 'bf16x3' else 0)
         for _ in range(max(rewarm, 5)):
@@ -1257,10 +1270,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    # ---- parity step (untimed): same shapes and kernels, inputs scaled so that the scores are of O(1) ----------------------
+    # ---- --full: parity step (untimed): same shapes and kernels, inputs scaled so that the scores are of O(1) ---------------
     parity = None
     cpu = None
-    if not use_dist and (graph is None or pstep is not None) and not args.no_input_grad:      # under a process group: the cross-rank gate below
+    if args.full and not use_dist and (graph is None or pstep is not None) and not args.no_input_grad:      # under a process group: the cross-rank gate below
         xq = (xd.detach() * CHECK_SCALE).requires_grad_(True)
         loss_q = step(xq)
         torch.cuda.synchronize()
@@ -1309,12 +1322,12 @@ def main():
             parity['parity_max_rel'] = worst
             parity['ok'] = bool(worst <= PARITY_TOL and abs(parity['loss'] - float(np.log(2.0))) > 1e-3)
 
-    # ---- N > 1 (or --force-dist): the same gate, across the ranks -------------------------------------------------------------
+    # ---- --full, N > 1 (or --force-dist): the same gate, across the ranks ------------------------------------------------------
     # One more step on the scaled inputs; (scores, labels, groups) of every rank are all-gathered ONCE and the reduced loss and the
     # pair count are held to oracle/pairs_oracle.c on the gathered batch; every rank evaluates the fp64 oracle of the layers on ITS
     # rows (scores -> gathered -> the global pair gradient -> backward of its rows), the per-rank weight gradients are summed
     # (all-reduce of the fp64 oracle gradients) and the all-reduced GPU gradients are held to that sum.
-    if use_dist and (graph is None or pstep is not None) and not args.no_input_grad:
+    if args.full and use_dist and (graph is None or pstep is not None) and not args.no_input_grad:
         _, PO = _oracle()
         rccl_ranks = dist.get_world_size()
         torch.set_num_threads(max(1, min(os.cpu_count() or 1, 2 * cpu_share()) // max(world, 1)))
@@ -1415,7 +1428,7 @@ def main():
                                 'fused node dcn_mix_score through autograd + grouping on a side stream' if fused else ('drop-in layers' if args.unfused else 'drop-in layers (fused route not available)'),
                        'gemm_precision': precision, 'gemm_precision_rule': args.gemm_precision if args.gemm_precision != 'auto' else
                        'auto: bf16x3 from %d rows per GPU, f32 below (the faster one at each shard size, both under the 1e-5 gate)' % SPLIT_FROM_ROWS,
-                       'loss': float(loss.item()), 'host_enqueue_ms_per_step': host_ms, 'untimed_steps': args.warmup + rewarm,
+                       'loss': loss_timed, 'host_enqueue_ms_per_step': host_ms, 'untimed_steps': args.warmup + rewarm, 'full': args.full,
                        'grads_copied_into_buckets': getattr(layerwise, 'last_foreign', None) if layerwise is not None else None},
             'roofline': roofline,
             'parity': parity,

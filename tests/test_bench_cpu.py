@@ -41,3 +41,11 @@ def test_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
 def test_steps_below_one_is_refused():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode != 0 and '--steps must be at least 1' in out.stderr
+
+
+def test_full_is_an_option_off_by_default():
+    """--full (everything besides the headline figure) is parsed and documented (off unless given: tests/test_bench_gpu.py)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '0'], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode != 0 and '--steps must be at least 1' in out.stderr and 'unrecognized' not in out.stderr
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0 and '--full' in out.stdout

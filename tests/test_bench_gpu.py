@@ -1,6 +1,6 @@
-"""bench.py end to end on the GPU (as the driver runs it, with few steps): the default line carries every field of the contract, and the
-step captured into a HIP graph (`--graph`, SURVEY 8f.1 diagnostic) replays to the same loss as the eager step -- a guard for the capture
-itself (hipStreamEndCapture crashed when the warm-up had run on the legacy default stream)."""
+"""bench.py end to end on the GPU (as the driver runs it, with few steps): the `--full` line carries every field of the contract, the plain line
+the headline alone from the same timed steps, and the step captured into a HIP graph (`--graph`, SURVEY 8f.1 diagnostic) replays to the same loss
+as the eager step -- a guard for the capture itself (hipStreamEndCapture crashed when the warm-up had run on the legacy default stream)."""
 import json
 import os
 import subprocess
@@ -19,8 +19,9 @@ def _clean_env():
     return {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'LOCAL_WORLD_SIZE', 'GROUP_RANK')}
 
 
-def _bench(*flags):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline'] + list(flags),
+def _bench(*flags, full=True):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline']
+                         + (['--full'] if full else []) + list(flags),
                          capture_output=True, text=True, timeout=300, cwd=ROOT, env=_clean_env())
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
@@ -59,6 +60,27 @@ def test_bench_line_fields_and_graph_replay(dev, tmp_path):
         np.testing.assert_allclose(b, a, rtol=1e-5, atol=1e-5 * float(np.abs(a).max()), err_msg=n)
 
 
+def test_plain_line_is_the_headline_of_the_same_timed_steps(dev, tmp_path):
+    """Without --full the run stops after the headline: no parity step, CPU baseline, other arithmetic, exclusive-time account or host probe -- and
+    its timed steps return what those of a --full run return."""
+    plain = _bench('--dump-outputs', str(tmp_path / 'plain'), full=False)
+    for key in ('metric', 'value', 'unit', 'ms_per_step', 'higher_is_better', 'dtype', 'config', 'roofline'):
+        assert key in plain, key
+    assert plain['value'] > 0 and plain['ms_per_step'] > 0 and plain['higher_is_better'] is True and plain['config']['full'] is False
+    assert plain['parity'] is None and plain['parity_max_rel'] is None and plain['config']['host_enqueue_ms_per_step'] is None
+    assert not {'cpu_baseline', 'exact_f32', 'split_precision'} & set(plain) and 'exclusive_ms_per_step' not in plain['roofline']
+    assert plain['roofline']['bound'] == 'mfma' and plain['roofline']['launches'] > 0        # the event hook of the timed steps stays on
+    full = _bench('--no-other', '--dump-outputs', str(tmp_path / 'full'))
+    assert full['config']['full'] is True and full['parity']['ok'] and full['config']['host_enqueue_ms_per_step'] > 0
+    assert plain['config']['loss'] == full['config']['loss'] and plain['dtype'] == full['dtype']
+    names = sorted(p.name for p in (tmp_path / 'plain').iterdir())
+    assert len(names) == 4 + 17 and sorted(p.name for p in (tmp_path / 'full').iterdir()) == names
+    for n in names:
+        a, b = np.load(tmp_path / 'plain' / n), np.load(tmp_path / 'full' / n)
+        assert a.shape == b.shape, n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-5 * float(np.abs(b).max()), err_msg=n)
+
+
 def test_self_launch_one_rank_force_dist_is_self_verifying(dev):
     """`bench.py --gpus N` starts its own ranks (child processes through torch.distributed.run, the parent never touches the GPU).  Driven here
     with one rank over a real RCCL group: the line carries `rccl_ranks`, and the cross-rank gate -- the reduced loss and pair count against
@@ -66,7 +88,7 @@ def test_self_launch_one_rank_force_dist_is_self_verifying(dev):
     # 8177 rows: a RAGGED per-rank batch (whole groups per rank are never multiples of 256) on padded storage -- the same kernels as the 8192-row shard
     # (profiles/r05_bench_rows8177.json against rows8192.json: 0.642 vs 0.644 ms on one box), self-verifying like every N > 1 line
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--launch', '--rows', '8177',
-                          '--steps', '2', '--warmup', '1'], capture_output=True, text=True, timeout=600, cwd=ROOT, env=_clean_env())
+                          '--steps', '2', '--warmup', '1', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT, env=_clean_env())
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line['rccl_ranks'] == 1 and line['n_gpus'] == 1
@@ -106,7 +128,7 @@ def test_two_ranks_share_one_gpu_over_gloo_and_verify_across_ranks(dev):
     reducer's buckets, every bucket is all-reduced across the two processes, and the cross-rank gate holds the reduced loss / pair count to the C pair
     oracle on the ALL-GATHERED batch and all 17 all-reduced weight gradients to the sum of the two ranks' fp64 oracles."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--oversubscribe', '--rows', '4096',
-                          '--shard', 'hash', '--steps', '2', '--warmup', '1'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=_clean_env())
+                          '--shard', 'hash', '--steps', '2', '--warmup', '1', '--full'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=_clean_env())
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 2 and line['rccl_ranks'] == 2 and line['backend'] == 'gloo' and line['shard'] == 'hash'
@@ -130,7 +152,7 @@ def test_model_configs_two_ranks_over_gloo_verify_across_ranks(dev, config, tmp_
     oracle's loss stage on the gathered batch, outputs and d loss / d x per rank and every all-reduced weight gradient against the sum of the ranks' fp64
     oracles.  /root/reference/rec_now/layers/cin_layer.py:72-122, ple_layer.py:295-321, rec_block/listwise_loss_from_batch.py:89-173."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', config, '--gpus', '2', '--backend', 'gloo', '--oversubscribe',
-                          '--rows', '2048', '--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=900,
+                          '--rows', '2048', '--steps', '2', '--warmup', '1', '--full', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=900,
                          cwd=ROOT, env=_clean_env())
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
