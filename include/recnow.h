@@ -697,6 +697,36 @@ int recnow_star_dense_bwd(const float* x, const float* const* params_host, int K
                           float* dkernel, float* dbias, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * SparseGNNLayer (ABI 9): rec_now/layers/sparse_gnn_layer.py:227-236.  L layers  v <- act(v + W_l^T v)  on the F-vector v of every
+ * (row, channel) pair, W_l[src_e][dst_e] = w[l % n_sets][e] for the E edges e.  One launch per direction runs all L layers on tiles that
+ * stay in LDS: the forward reads x once and writes every requested layer output once; the backward reads x and the output gradients,
+ * RECOMPUTES the layer chain of its tile, and writes dx (it needs no saved activation).  F <= 64 and E <= 4096: else RECNOW_EUNSUPPORTED.
+ *   layouts: RECNOW_GNN_BFD x (B,F,D) contiguous (also (B,F*D)); RECNOW_GNN_BDF x (B,D,F) contiguous; RECNOW_GNN_LIST x_fields = DEVICE
+ *     array of F pointers to contiguous (B,D) tensors (x_aligned: every one of them is 16-byte aligned).  Outputs and their gradients
+ *     are BFD or BDF (out_layout).  dx has the layout of the input; for RECNOW_GNN_LIST it is one (F,B,D) block.
+ *   tab: DEVICE int32 array  Cd | Cs | 0 | 0 | dS (Cd x 8) | dG (Cd x 4) | sS (Cs x 8) | sG (Cs x 4) | ssrc (E) | sdst (E) | swid (E).
+ *     A pass over the graph walks a stream of CHUNKS of four edges of one node, in node order (a node without edges has one chunk; a short
+ *     chunk is padded with edges of weight index -1 that point at the node itself).  S: o0 o1 o2 o3 node flags 0 0 (flags: 1 first chunk of
+ *     the node | 2 last); G: the four weight indices.  dS / dG: by destination, o = the sources of the edges into `node` (Cd chunks, the
+ *     forward); sS / sG: by source, o = the destinations of the edges out of `node` (Cs chunks, the input gradient); ssrc / sdst / swid:
+ *     source, destination and weight index of every edge (the weight gradient).  Every index must be < F (fields) or < E (weights).
+ *   w (n_sets, E).  act: enum recnow_act.  y_last or NULL; y_all: NULL or a DEVICE array of L pointers, entry l (may be 0) receives
+ *     layer l's output (y_aligned: all 16-byte aligned).  dy_last / dy_all / dy_aligned likewise: every gradient given is added in.
+ *   dx, dw (n_sets, E) may be NULL.  dw is a fixed-order sum (no float atomics): ws of recnow_sparse_gnn_workspace_bytes, needed only
+ *     with dw; it is bounded by the backward's workgroups (<= 1024) x n_sets x E floats, independent of B.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define RECNOW_GNN_BFD 0
+#define RECNOW_GNN_BDF 1
+#define RECNOW_GNN_LIST 2
+size_t recnow_sparse_gnn_workspace_bytes(int64_t B, int F, int D, int E, int n_sets);
+int recnow_sparse_gnn_fwd(const float* x, const float* const* x_fields, int in_layout, int x_aligned, int out_layout, const int32_t* tab,
+                          const float* w, int64_t B, int F, int D, int E, int L, int n_sets, int act, float* y_last, float* const* y_all,
+                          int y_aligned, void* stream);
+int recnow_sparse_gnn_bwd(const float* x, const float* const* x_fields, int in_layout, int x_aligned, int out_layout, const int32_t* tab,
+                          const float* w, int64_t B, int F, int D, int E, int L, int n_sets, int act, const float* dy_last,
+                          const float* const* dy_all, int dy_aligned, float* dx, float* dw, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

@@ -107,6 +107,9 @@ SIGNATURES = {
     'recnow_star_dense_workspace_bytes': (_Z, [_L, _I, _I]),
     'recnow_star_dense_fwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _I, _I, _I, _P, _P]),
     'recnow_star_dense_bwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_sparse_gnn_workspace_bytes': (_Z, [_L, _I, _I, _I, _I]),
+    'recnow_sparse_gnn_fwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    'recnow_sparse_gnn_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _Z, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -139,7 +142,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 8      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 9      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

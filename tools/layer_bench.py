@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,ipnn,senet,attn,din,focal,embed]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed]"""
 import os
 import sys
 
@@ -405,8 +405,63 @@ def star(mode):
         torch.cuda.empty_cache()
 
 
+def gnn_ref_eager(x, indices, ws, L, F):
+    """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
+    from the weight vector, matmul, add, tanh; transpose back and flatten."""
+    o = x.transpose(1, 2).contiguous()                      # tf.transpose is a physical transpose
+    for i in range(L):
+        W = torch.zeros(F, F, device=x.device).index_put((indices[:, 0], indices[:, 1]), ws[i % len(ws)])
+        o = torch.tanh(o + torch.matmul(o, W))
+    return o.transpose(1, 2).reshape(x.shape[0], -1)
+
+
+def gnn():
+    """SparseGNNLayer at B = 65536, F = 32, D = 32 (F*D = 1024), L = 3, tanh, unshared weights, for a ring (E = 64), E = 256 and the complete
+    graph without self loops (E = 992): forward and backward time each, TB/s of algorithmic bytes (forward 2 B F D 4: x read, y written;
+    backward 3 B F D 4: x and dy read, dx written), and the same step for the reference algorithm in torch eager."""
+    from rec_now_amd.layers.sparse_gnn_layer import SparseGNNLayer
+    B, F, D, L = 65536, 32, 32, 3
+    graphs = (('ring', {i: [(i - 1) % F, (i + 1) % F] for i in range(F)}),
+              ('8 nearest', {i: [(i + k) % F for k in (-4, -3, -2, -1, 1, 2, 3, 4)] for i in range(F)}),
+              ('complete', {i: [j for j in range(F) if j != i] for i in range(F)}))
+    for name, nbrs in graphs:
+        x = (torch.randn(B, F, D, device=dev) * 0.5).requires_grad_(True)
+        gy = torch.randn(B, F * D, device=dev)
+        layer = SparseGNNLayer(list(range(F)), nbrs, num_layers=L, share_weights_between_layers=False, activation='tanh')
+        run = lambda: layer(x)                                  # noqa: E731
+        run()
+        E = len(layer.indices)
+        with torch.no_grad():
+            for v in layer.named_weights().values():
+                v.mul_(min(1.0, 8.0 / (E / F)))
+        ix = torch.tensor(layer.indices, device=dev)
+        ref = lambda: gnn_ref_eager(x, ix, layer.gnn_weights, L, F)      # noqa: E731
+
+        def bwd_of(fn):
+            y = fn()
+
+            def step():
+                x.grad = None
+                layer.zero_grad(set_to_none=True)
+                y.backward(gy, retain_graph=True)
+            return step
+
+        nbytes = 4.0 * B * F * D
+        # both orders: fused, reference, reference, fused; the two fused figures are averaged, and so are the two reference figures
+        f1, b1 = timeit(run), timeit(bwd_of(run))
+        r1, rb1 = timeit(ref), timeit(bwd_of(ref))
+        r2, rb2 = timeit(ref), timeit(bwd_of(ref))
+        f2, b2 = timeit(run), timeit(bwd_of(run))
+        ms_f, ms_b, rf, rb = (f1 + f2) / 2, (b1 + b2) / 2, (r1 + r2) / 2, (rb1 + rb2) / 2
+        print('SparseGNNLayer %-9s E=%-3d B=%d F=%d D=%d L=%d tanh unshared : fwd %.3f ms %.2f TB/s, bwd %.3f ms %.2f TB/s (algorithmic) | reference in '
+              'torch eager: fwd %.3f ms, bwd %.3f ms -> speedup fwd %.1fx bwd %.1fx | runs fwd %.3f / %.3f, bwd %.3f / %.3f ms'
+              % (name, E, B, F, D, L, ms_f, 2 * nbytes / ms_f / 1e9, ms_b, 3 * nbytes / ms_b / 1e9, rf, rb, rf / ms_f, rb / ms_b, f1, f2, b1, b2))
+        del x, gy, layer
+        torch.cuda.empty_cache()
+
+
 if __name__ == '__main__':
-    which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'ipnn', 'senet', 'attn', 'din', 'focal', 'embed']
+    which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'gnn', 'ipnn', 'senet', 'attn', 'din', 'focal', 'embed']
     if 'fm' in which:
         fm()
     if 'dcn' in which:
@@ -425,6 +480,8 @@ if __name__ == '__main__':
     for mode in ('star', 'stacked'):
         if mode in which:
             star(mode)
+    if 'gnn' in which:
+        gnn()
     for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed)):
         if name in which:
             fn()
