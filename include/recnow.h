@@ -673,6 +673,51 @@ int recnow_embed_rows_bwd(const int64_t* key, const int32_t* order, const int32_
 /* n_seg (ABI 4, optional DEVICE pointer: the segment count of recnow_group_segments): only the first n_seg[0] slots are read. */
 int recnow_embed_scatter_rows(const float* drows, const int64_t* row_ids, int64_t n_slots, int D, int64_t V, float* dtable,
                               const int32_t* n_seg, void* stream);
+/* (ABI 10) recnow_embed_rows_bwd for lookups whose every key is a row of ONE dense (V, D) gradient: dtable (zero-filled by the caller)
+ * receives dtable[key][:] = sum over the entries e with that key of w * dout[e / C][:], w = weights[e / w_div] (weights NULL: 1), straight from
+ * the sorted segments -- no slot buffer of N rows, no scatter pass.  A key outside [0, V) is dropped.  Same fixed summation order, same ws. */
+int recnow_embed_rows_bwd_direct(const int64_t* key, const int32_t* order, const int32_t* seg_id, const int32_t* seg_first,
+                                 const int32_t* n_seg, const float* weights, int w_div, const float* dout, int64_t N, int C, int D,
+                                 float* dtable, int64_t V, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * MultiHashLayer / FastMultiHashLayer (ABI 10): rec_now/layers/multi_hash_layer.py.  bucket_h(id) = hash_h(text of id) % num_bins (unsigned
+ * 64-bit), hash_h = SipHash-2-4 keyed (salts[h], salts[h]) -- keras Hashing(salt=(s, s)) -- or, for h = 0 with first_unsalted, FarmHash
+ * Fingerprint64 -- Hashing(salt=None).  The text of an integer id is its "%lld" decimal form.  salts: HOST array of num_hash values >= 0;
+ * 1 <= num_hash <= 16; num_bins >= 1; id_dtype RECNOW_KEY_I32 / RECNOW_KEY_I64.  Buckets are int64, out[i * num_hash + h].
+ *   recnow_hash_ids_host / recnow_hash_bytes_host: on the HOST, no GPU call (host pointers throughout).  bytes_host: string i is
+ *     bytes[offsets[i] .. offsets[i + 1]); with first_unsalted a string longer than 32 bytes returns RECNOW_EUNSUPPORTED (Fingerprint64 is
+ *     implemented for 0..32 bytes), never a wrong bucket.  SipHash takes any length.
+ *   recnow_hash_ids: the same on the device (ids, out DEVICE).
+ *   recnow_hash_embed_fwd: ids (B, L) -> hash, gather and reduce in one pass.  tables_host: HOST array of num_hash DEVICE pointers to (num_bins, D)
+ *     fp32 row blocks (one table per hash function, or slices h * num_bins of one table).  id_dtype RECNOW_HASH_BUCKETS: `ids` holds (B, L, num_hash)
+ *     int64 bucket numbers computed elsewhere (recnow_hash_bytes_host); a bucket outside [0, num_bins) reads as a zero row.  mode:
+ *       RECNOW_HASH_SUM / _MEAN  out (B, L, D)            sum (mean) over the hash functions
+ *       RECNOW_HASH_ROWS         out (B, L, num_hash, D)  the rows themselves (bit-identical copies)
+ *       RECNOW_HASH_POOLED       out (B, D) = sum_l weights[b][l] * sum_h row; weights (B, L) or NULL (other modes: must be NULL)
+ *     keys (B, L, num_hash) int64 / keys32 the same as int32, both optional: h * num_bins + bucket, the sort key of the table gradient
+ *     (recnow_embed_rows_bwd_direct over a (num_hash * num_bins, D) buffer) and what recnow_hash_embed_bwd_weights gathers from.
+ *     Fixed summation order, no atomics.  16-byte gathers when D % 4 == 0 and tables and out are 16-byte aligned, else element-wise (any D >= 1).
+ *     num_hash * num_bins or B * L * num_hash >= 2^31, or pooled with more than 256 gather elements per row (D > 1024, or D > 256 unaligned):
+ *     RECNOW_EUNSUPPORTED.
+ *   recnow_hash_embed_bwd_weights: dweights[b][l] = <dout[b][:], sum_h row> for the pooled mode, rows re-gathered from `keys`.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define RECNOW_HASH_BUCKETS 4
+#define RECNOW_HASH_SUM 0
+#define RECNOW_HASH_MEAN 1
+#define RECNOW_HASH_ROWS 2
+#define RECNOW_HASH_POOLED 3
+int recnow_hash_ids_host(const void* ids, int id_dtype, int64_t n, const int64_t* salts, int num_hash, int first_unsalted,
+                         int64_t num_bins, int64_t* out);
+int recnow_hash_bytes_host(const unsigned char* bytes, const int64_t* offsets, int64_t n, const int64_t* salts, int num_hash,
+                           int first_unsalted, int64_t num_bins, int64_t* out);
+int recnow_hash_ids(const void* ids, int id_dtype, int64_t n, const int64_t* salts_host, int num_hash, int first_unsalted,
+                    int64_t num_bins, int64_t* out, void* stream);
+int recnow_hash_embed_fwd(const void* ids, int id_dtype, int64_t B, int64_t L, const int64_t* salts_host, int num_hash,
+                          int first_unsalted, int64_t num_bins, const float* const* tables_host, int D, const float* weights,
+                          int mode, float* out, int64_t* keys, int32_t* keys32, void* stream);
+int recnow_hash_embed_bwd_weights(const int64_t* keys, const float* const* tables_host, int num_hash, int64_t num_bins, int D,
+                                  const float* dout, int64_t B, int64_t L, float* dweights, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * StarDenseLayer / StackedDenseLayer (ABI 7): rec_now/layers/star_dense_layer.py:118-163, stacked_dense_layer.py:116-155.

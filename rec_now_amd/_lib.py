@@ -103,7 +103,13 @@ SIGNATURES = {
     'recnow_embed_unique': (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _P, _P]),
     'recnow_embed_rows_bwd_workspace_bytes': (_Z, [_L, _I]),
     'recnow_embed_rows_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    'recnow_embed_rows_bwd_direct': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _L, _I, _I, _P, _L, _P, _Z, _P]),
     'recnow_embed_scatter_rows': (_I, [_P, _P, _L, _I, _L, _P, _P, _P]),
+    'recnow_hash_ids_host': (_I, [_P, _I, _L, _P, _I, _I, _L, _P]),
+    'recnow_hash_bytes_host': (_I, [_P, _P, _L, _P, _I, _I, _L, _P]),
+    'recnow_hash_ids': (_I, [_P, _I, _L, _P, _I, _I, _L, _P, _P]),
+    'recnow_hash_embed_fwd': (_I, [_P, _I, _L, _L, _P, _I, _I, _L, _P, _I, _P, _I, _P, _P, _P, _P]),
+    'recnow_hash_embed_bwd_weights': (_I, [_P, _P, _I, _L, _I, _P, _L, _L, _P, _P]),
     'recnow_star_dense_workspace_bytes': (_Z, [_L, _I, _I]),
     'recnow_star_dense_fwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _I, _I, _I, _P, _P]),
     'recnow_star_dense_bwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
@@ -142,7 +148,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 9      # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 10     # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

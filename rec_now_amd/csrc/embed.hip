@@ -330,7 +330,10 @@ __global__ void __launch_bounds__(256)
 k_embed_rows_chunks(const int64_t* __restrict__ key, const int32_t* __restrict__ order, const int32_t* __restrict__ seg_id,
                     const int32_t* __restrict__ seg_first, const int32_t* __restrict__ seg, const float* __restrict__ weights,
                     const float* __restrict__ cnt, const float* __restrict__ dout, int64_t N, int C, int T, int D, int mean,
-                    float* __restrict__ drows, float* __restrict__ part, int64_t* __restrict__ row_ids) {
+                    float* __restrict__ drows, float* __restrict__ part, int64_t* __restrict__ row_ids, int w_div, int64_t direct_V) {
+    // direct_V > 0 (hashed lookups, hash_embed.hip): `drows` IS the zero-filled (direct_V, D) table gradient and a finished segment goes to the row
+    // its key names instead of to slot s -- every key is a row of the table there, so no slot buffer of N rows and no scatter pass; seg may be NULL
+    // (every entry pooled into target 0) and entry e takes weights[e / w_div] (one weight per id, w_div entries per id).
     constexpr int G = 64 / LPE;                                   // chunks walked side by side in one wave
     constexpr int NQ = (EMB_CH + LPE - 1) / LPE;                  // entries described per lane
     const int lane = threadIdx.x & 63, g = lane / LPE, dl = lane % LPE;
@@ -350,11 +353,11 @@ k_embed_rows_chunks(const int64_t* __restrict__ key, const int32_t* __restrict__
             if (i < n) {
                 const int64_t k = k0 + i;
                 const int e = order[k];
-                const int t = seg[e];
+                const int t = seg ? seg[e] : 0;
                 const int sid = seg_id[k];
                 if (t >= 0) {                                     // entries of the unpooled (-1) segment carry no gradient
                     const int64_t b = e / C;
-                    float wt = weights ? weights[e] : 1.f;
+                    float wt = weights ? weights[w_div > 1 ? e / w_div : e] : 1.f;
                     if (mean) wt /= cnt[b * T + t];
                     m_wt[q] = wt;
                     m_off[q] = (b * T + t) * (int64_t)D;
@@ -364,7 +367,7 @@ k_embed_rows_chunks(const int64_t* __restrict__ key, const int32_t* __restrict__
                 const bool whole = first >= k0 && end <= k1;      // the run starts at max(k0, first)
                 m_sid[q] = sid;
                 m_flag[q] = (closes ? 1 : 0) | (whole ? 2 : 0) | (first > k0 ? 4 : 0);
-                if (row_ids && closes && whole) m_key[q] = key[e];          // all entries of a segment carry its id
+                if ((row_ids || direct_V > 0) && closes && whole) m_key[q] = key[e];          // all entries of a segment carry its id
             }
         }
         for (int d0 = 0; d0 < D; d0 += LPE) {                     // more than one slice only for D > 64
@@ -390,8 +393,12 @@ k_embed_rows_chunks(const int64_t* __restrict__ key, const int32_t* __restrict__
                         if (flag & 2) {
                             const int sid = __shfl(q ? m_sid[NQ - 1] : m_sid[0], srcl, LPE);
                             const int64_t id = __shfl(q ? m_key[NQ - 1] : m_key[0], srcl, LPE);
-                            if (d < D) drows[sid * (int64_t)D + d] = a;
-                            if (d == 0 && row_ids) row_ids[sid] = id;
+                            if (direct_V > 0) {
+                                if (d < D && id >= 0 && id < direct_V) drows[id * (int64_t)D + d] = a;
+                            } else {
+                                if (d < D) drows[sid * (int64_t)D + d] = a;
+                                if (d == 0 && row_ids) row_ids[sid] = id;
+                            }
                         } else if (d < D) {
                             // a cut run touches the chunk start, the chunk end, or both (then it is the whole chunk: slot 0)
                             part[(((flag & 4) ? nchunk : 0) + ch) * (int64_t)D + d] = a;     // slot-major: [2][nchunk][D]
@@ -406,7 +413,7 @@ k_embed_rows_chunks(const int64_t* __restrict__ key, const int32_t* __restrict__
 __global__ void __launch_bounds__(256)
 k_embed_rows_join(const int64_t* __restrict__ key, const int32_t* __restrict__ order, const int32_t* __restrict__ seg_id,
                   const int32_t* __restrict__ seg_first, int64_t N, int D, int DL, const float* __restrict__ part,
-                  float* __restrict__ drows, int64_t* __restrict__ row_ids) {
+                  float* __restrict__ drows, int64_t* __restrict__ row_ids, int64_t direct_V) {
     __shared__ float red[256];
     __shared__ int64_t own[256];
     __shared__ int nown;
@@ -426,10 +433,12 @@ k_embed_rows_join(const int64_t* __restrict__ key, const int32_t* __restrict__ o
                     const int64_t c0 = c - 1, c1 = (seg_first[s + 1] - 1) / EMB_CH;
                     if (c1 - c0 < EMB_JSHORT) {
                         const int64_t first_slot = f != c0 * EMB_CH ? 1 : 0;
+                        const int64_t slot = direct_V > 0 ? key[order[f]] : s;          // direct: the table row (see k_embed_rows_chunks)
+                        const bool keep = direct_V <= 0 || (slot >= 0 && slot < direct_V);
                         for (int d = dl; d < D; d += DL) {
                             float t = part[(first_slot * nchunk + c0) * (int64_t)D + d];
                             for (int64_t x = c0 + 1; x <= c1; ++x) t += part[x * (int64_t)D + d];
-                            drows[s * (int64_t)D + d] = t;
+                            if (keep) drows[slot * (int64_t)D + d] = t;
                         }
                         if (dl == 0 && row_ids) row_ids[s] = key[order[f]];
                     } else if (dl == 0) {
@@ -447,6 +456,8 @@ k_embed_rows_join(const int64_t* __restrict__ key, const int32_t* __restrict__ o
             const int64_t c0 = c - 1, c1 = l / EMB_CH;                      // chunks c0 .. c1 hold pieces of s
             // piece of chunk x: slot 1 in c0 unless the segment starts exactly at the chunk start, slot 0 in every later chunk
             const int64_t first_slot = f != c0 * EMB_CH ? 1 : 0;
+            const int64_t slot = direct_V > 0 ? key[order[f]] : s;
+            const bool keep = direct_V <= 0 || (slot >= 0 && slot < direct_V);
             for (int d0 = 0; d0 < D; d0 += DL) {
                 const int d = d0 + dl;
                 float acc[EMB_JU];                                          // EMB_JU loads in flight per thread (one hot id: 65 K pieces)
@@ -470,7 +481,7 @@ k_embed_rows_join(const int64_t* __restrict__ key, const int32_t* __restrict__ o
                 if (pl == 0 && d < D) {
                     float t = red[dl];
                     for (int u = 1; u < NPL; ++u) t += red[u * DL + dl];
-                    drows[s * (int64_t)D + d] = t;
+                    if (keep) drows[slot * (int64_t)D + d] = t;
                 }
             }
             if (threadIdx.x == 0 && row_ids) row_ids[s] = key[order[f]];
@@ -486,6 +497,26 @@ extern "C" size_t recnow_embed_rows_bwd_workspace_bytes(int64_t N, int D) {
     const int64_t nchunk = (N + EMB_CH - 1) / EMB_CH;
     return rn_align((size_t)(nchunk > 0 ? nchunk : 1) * 2 * (size_t)D * sizeof(float));
 }
+static int embed_rows_bwd_launch(const int64_t* key, const int32_t* order, const int32_t* seg_id, const int32_t* seg_first, const int32_t* n_seg,
+                                 const int32_t* seg, const float* weights, int w_div, const float* cnt, const float* dout, int64_t N, int C, int T, int D,
+                                 int mean, float* drows, int64_t* row_ids, int64_t direct_V, void* ws, hipStream_t st) {
+    const int64_t nchunk = (N + EMB_CH - 1) / EMB_CH;
+    const int LPE = D <= 16 ? 16 : D <= 32 ? 32 : 64;             // lanes per entry; also the dims lanes of the join
+    int64_t g = (nchunk + 4 * (64 / LPE) - 1) / (4 * (64 / LPE));
+    if (g > 16384) g = 16384;
+    if (LPE == 16) hipLaunchKernelGGL(k_embed_rows_chunks<16>, (int)g, 256, 0, st, key, order, seg_id, seg_first, seg, weights, cnt, dout, N, C, T, D, mean, drows, (float*)ws, row_ids, w_div, direct_V);
+    else if (LPE == 32) hipLaunchKernelGGL(k_embed_rows_chunks<32>, (int)g, 256, 0, st, key, order, seg_id, seg_first, seg, weights, cnt, dout, N, C, T, D, mean, drows, (float*)ws, row_ids, w_div, direct_V);
+    else hipLaunchKernelGGL(k_embed_rows_chunks<64>, (int)g, 256, 0, st, key, order, seg_id, seg_first, seg, weights, cnt, dout, N, C, T, D, mean, drows, (float*)ws, row_ids, w_div, direct_V);
+    if (nchunk > 1) {
+        const int64_t per = 256 / LPE;                            // boundaries per workgroup and step
+        int64_t gj = (nchunk - 1 + per - 1) / per;
+        if (gj > 16384) gj = 16384;
+        hipLaunchKernelGGL(k_embed_rows_join, (int)gj, 256, 0, st, key, order, seg_id, seg_first, N, D, LPE, (const float*)ws, drows, row_ids, direct_V);
+    }
+    if (row_ids) hipLaunchKernelGGL(k_embed_rows_tail, 64, 256, 0, st, n_seg, N, row_ids);
+    RN_LAUNCH_CHECK();
+    return RECNOW_OK;
+}
 extern "C" int recnow_embed_rows_bwd(const int64_t* key, const int32_t* order, const int32_t* seg_id, const int32_t* seg_first,
                                      const int32_t* n_seg, const int32_t* seg, const float* weights, const float* cnt, const float* dout,
                                      int64_t N, int C, int T, int D, int mean, float* drows, int64_t* row_ids, void* ws, size_t ws_bytes,
@@ -494,23 +525,19 @@ extern "C" int recnow_embed_rows_bwd(const int64_t* key, const int32_t* order, c
     if (N == 0) return RECNOW_OK;
     if (!key || !order || !seg_id || !seg_first || !n_seg || !seg || !dout || !drows || (mean && !cnt)) return RECNOW_EINVAL;
     if (!ws || ws_bytes < recnow_embed_rows_bwd_workspace_bytes(N, D)) return RECNOW_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t nchunk = (N + EMB_CH - 1) / EMB_CH;
-    const int LPE = D <= 16 ? 16 : D <= 32 ? 32 : 64;             // lanes per entry; also the dims lanes of the join
-    int64_t g = (nchunk + 4 * (64 / LPE) - 1) / (4 * (64 / LPE));
-    if (g > 16384) g = 16384;
-    if (LPE == 16) hipLaunchKernelGGL(k_embed_rows_chunks<16>, (int)g, 256, 0, st, key, order, seg_id, seg_first, seg, weights, cnt, dout, N, C, T, D, mean, drows, (float*)ws, row_ids);
-    else if (LPE == 32) hipLaunchKernelGGL(k_embed_rows_chunks<32>, (int)g, 256, 0, st, key, order, seg_id, seg_first, seg, weights, cnt, dout, N, C, T, D, mean, drows, (float*)ws, row_ids);
-    else hipLaunchKernelGGL(k_embed_rows_chunks<64>, (int)g, 256, 0, st, key, order, seg_id, seg_first, seg, weights, cnt, dout, N, C, T, D, mean, drows, (float*)ws, row_ids);
-    if (nchunk > 1) {
-        const int64_t per = 256 / LPE;                            // boundaries per workgroup and step
-        int64_t gj = (nchunk - 1 + per - 1) / per;
-        if (gj > 16384) gj = 16384;
-        hipLaunchKernelGGL(k_embed_rows_join, (int)gj, 256, 0, st, key, order, seg_id, seg_first, N, D, LPE, (const float*)ws, drows, row_ids);
-    }
-    if (row_ids) hipLaunchKernelGGL(k_embed_rows_tail, 64, 256, 0, st, n_seg, N, row_ids);
-    RN_LAUNCH_CHECK();
-    return RECNOW_OK;
+    return embed_rows_bwd_launch(key, order, seg_id, seg_first, n_seg, seg, weights, 1, cnt, dout, N, C, T, D, mean, drows, row_ids, 0, ws, (hipStream_t)stream);
+}
+// The same reduction for lookups whose every key is a row of ONE zero-filled dense (V, D) gradient (hash_embed.hip: key = h * num_bins + bucket):
+// dtable[key][:] = sum over the entries e of that key of w * dout[e / C][:], with w = weights[e / w_div] (weights may be NULL).  No slot buffer, no
+// scatter pass; a key outside [0, V) is dropped.
+extern "C" int recnow_embed_rows_bwd_direct(const int64_t* key, const int32_t* order, const int32_t* seg_id, const int32_t* seg_first,
+                                            const int32_t* n_seg, const float* weights, int w_div, const float* dout, int64_t N, int C, int D,
+                                            float* dtable, int64_t V, void* ws, size_t ws_bytes, void* stream) {
+    if (N < 0 || C < 1 || D < 1 || V < 1 || w_div < 1) return RECNOW_EINVAL;
+    if (N == 0) return RECNOW_OK;
+    if (!key || !order || !seg_id || !seg_first || !n_seg || !dout || !dtable) return RECNOW_EINVAL;
+    if (!ws || ws_bytes < recnow_embed_rows_bwd_workspace_bytes(N, D)) return RECNOW_EWORKSPACE;
+    return embed_rows_bwd_launch(key, order, seg_id, seg_first, n_seg, nullptr, weights, w_div, nullptr, dout, N, C, 1, D, 0, dtable, nullptr, V, ws, (hipStream_t)stream);
 }
 
 // dtable[row_ids[s]][:] = drows[s][:] for every used slot s (row ids are unique: one writer per table row)

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash]"""
 import os
 import sys
 
@@ -460,6 +460,49 @@ def gnn():
         torch.cuda.empty_cache()
 
 
+def hash():
+    """FastMultiHashLayer at B = 65536, L = 50, num_hash = 2, num_bins = 2^20, D = 8 and 32: `get` ((B, L, D)) and `get_pooling` ((B, D), weighted),
+    forward and forward + backward (d table, and d weights for the pooling).  Byte model: ids once (8 B each), num_hash table rows per id of 4 D
+    bytes rounded up to the 64 B a row fetch costs at least, the output once.  Baseline: the lookup half of the reference algorithm in torch eager
+    on PRECOMPUTED buckets -- table[buckets].sum(-2) (times weights, .sum(1)) -- which is handed what the reference hashes on the host and skips its
+    host-to-device copy."""
+    from rec_now_amd.layers.multi_hash_layer import FastMultiHashLayer
+    B, L, nh, nb = 65536, 50, 2, 1 << 20
+    for D in (8, 32):
+        ids = torch.randint(0, 1 << 40, (B, L), device=dev)
+        w = torch.randn(B, L, device=dev, requires_grad=True)
+        layer = FastMultiHashLayer(nb, D, num_hash=nh, embeddings_initializer='random_normal')
+        layer.get(ids[:4])
+        table = layer.tables[0]
+        plain = FastMultiHashLayer(nb, -1, num_hash=nh)
+        buckets = plain(ids, combiner=None).reshape(B, nh, L).permute(0, 2, 1).contiguous() + torch.arange(nh, device=dev) * nb      # (B, L, nh) rows
+        g_get, g_pool = torch.randn(B, L, D, device=dev), torch.randn(B, D, device=dev)
+        row = max(4 * D, 64)
+        cases = (('get', lambda: layer.get(ids), lambda: table[buckets].sum(-2), g_get, 8.0 * B * L + nh * row * B * L + 4.0 * B * L * D),
+                 ('get_pooling', lambda: layer.get_pooling(ids, w), lambda: (w[..., None] * table[buckets].sum(-2)).sum(1), g_pool,
+                  12.0 * B * L + nh * row * B * L + 4.0 * B * D))
+        for name, run, ref, gy, nbytes in cases:
+            def fb_of(fn):
+                def step():
+                    table.grad = None
+                    w.grad = None
+                    fn().backward(gy)
+                return step
+            # both orders: fused, reference, reference, fused; the two figures of each are averaged
+            f1, b1 = timeit(run), timeit(fb_of(run))
+            r1, rb1 = timeit(ref), timeit(fb_of(ref))
+            r2, rb2 = timeit(ref), timeit(fb_of(ref))
+            f2, b2 = timeit(run), timeit(fb_of(run))
+            ms_f, ms_b, rf, rb = (f1 + f2) / 2, (b1 + b2) / 2, (r1 + r2) / 2, (rb1 + rb2) / 2
+            print('FastMultiHashLayer.%-11s B=%d L=%d D=%d num_hash=%d num_bins=2^20 : fwd %.3f ms %.2f TB/s (byte model %.0f MB), fwd+bwd %.3f ms | torch eager on '
+                  'precomputed buckets: fwd %.3f ms, fwd+bwd %.3f ms -> ratio fwd %.2fx fwd+bwd %.2fx | runs fwd %.3f / %.3f, fwd+bwd %.3f / %.3f ms'
+                  % (name, B, L, D, nh, ms_f, nbytes / ms_f / 1e9, nbytes / 1e6, ms_b, rf, rb, rf / ms_f, rb / ms_b, f1, f2, b1, b2))
+        hs = timeit(lambda: plain(ids, combiner=None))
+        print('FastMultiHashLayer bucket numbers only (embedding_dim -1) B=%d L=%d num_hash=%d : %.3f ms, %.2f G ids/s' % (B, L, nh, hs, B * L / hs / 1e6))
+        del ids, w, layer, table, buckets, g_get, g_pool
+        torch.cuda.empty_cache()
+
+
 if __name__ == '__main__':
     which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'gnn', 'ipnn', 'senet', 'attn', 'din', 'focal', 'embed']
     if 'fm' in which:
@@ -482,6 +525,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash)):
         if name in which:
             fn()
