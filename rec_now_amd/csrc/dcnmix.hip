@@ -18,23 +18,8 @@
 // multiples of 128) and K of the (N*S+N)-deep products rounded up to 16/32, all zero padded, so every GEMM of the layer
 // takes the lean interior kernel (no bounds code) whenever B is a multiple of 256.  Zero columns/rows are inert.
 #include <mutex>
-#include "gemm.hpp"
-#include "dcnmix_mid.hpp"
-#include "dcnmix_tile.hpp"
+#include "dcnmix_layout.hpp"
 #include "prof.hpp"
-
-static inline int ldt_of(int S, int N) {
-    const int kc = N * S + N;
-    if (kc <= 32) return 32;
-    if (kc <= 64) return 64;
-    if (kc <= 128) return 128;
-    if (kc <= 160) return 160;
-    return (kc + 127) / 128 * 128;
-}
-static inline int kp_of(int S, int N) {            // padded depth of the K = N*S+N products
-    const int kc = N * S + N;
-    return kc <= 256 ? (kc + 15) / 16 * 16 : (kc + 31) / 32 * 32;
-}
 
 // Wc1[d][n*S+s] = U[n][d][s];  Wc1[d][NS+n] = K[d][n];  pad columns = 0
 __global__ void k_pack_w1(const float* __restrict__ U, const float* __restrict__ K, int D, int S, int N, int LDT, float* __restrict__ Wc1) {
@@ -128,61 +113,11 @@ k_dcnmix_gate_bwd(const float* __restrict__ dT2g, const float* __restrict__ T2, 
     }
 }
 
-struct MixDims {
-    int64_t B;
-    int D, S, N, L, NS, KC, LDT, KP;   // KC = NS + N; LDT/KP = padded width / depth
-    bool exact;                        // exact-128 formulation (side products + rank-N epilogue updates)
-};
-// Exact formulation: every D-sized product has exactly NS MFMA columns / NS-deep K; the N gate columns and the N
-// gate-weighted bias rows are VALU side products / rank-N epilogue updates of the lean 128x128 GEMM kernels.
-static inline bool mix_exact(int64_t B, int D, int S, int N) {
-    return (N * S) % 128 == 0 && D % 128 == 0 && B % 256 == 0 && N <= 4 && kp_of(S, N) <= 512;     // second outputs: K <= 512
-}
-static inline MixDims mix_dims(int64_t B, int D, int S, int N, int L) {
-    MixDims m;
-    m.B = B; m.D = D; m.S = S; m.N = N; m.L = L; m.NS = N * S; m.KC = N * S + N; m.LDT = ldt_of(S, N); m.KP = kp_of(S, N);
-    m.exact = mix_exact(B, D, S, N);
-    if (m.exact) m.LDT = m.KP;      // [NS main | N gate | zero pad to a multiple of 16]: N = NS products + side product, K = KP products
-    return m;
-}
-static inline size_t act_block(const MixDims& m) { return rn_align((size_t)m.B * m.LDT * sizeof(float)); }
-static inline size_t xbuf(const MixDims& m) { return rn_align((size_t)m.B * m.D * sizeof(float)); }
-#define MIX_PACK_MAX_L 8
-// exact path, L <= MIX_PACK_MAX_L: the packed weights of every layer -- Wc1_l = [U_l | K_l | 0] (D x LDT), Wc2_l = [W_l; b_l; 0]
-// (LDT x D) and one (LDT x D) block for the fused head's pre-scaled top-layer weights -- live at the end of `saved`: the forward
-// packs them ONCE per step (one launch) and the backward reads them there instead of packing again.
-static inline size_t mix_pack_one(const MixDims& m) { return rn_align((size_t)m.D * m.LDT * sizeof(float)); }
-static inline size_t mix_pack_bytes(const MixDims& m) { return (m.exact && m.L <= MIX_PACK_MAX_L) ? (size_t)(2 * m.L + 1) * mix_pack_one(m) : 0; }
-static inline size_t mix_pack_off(const MixDims& m) {       // byte offset of the pack region inside `saved`
-    return (size_t)m.L * 3 * act_block(m) + (size_t)(m.L - 1) * xbuf(m) + (m.exact ? (size_t)m.L * xbuf(m) : 0);
-}
-
-// Row-block persistent kernels (dcnmix_tile.hip): their fragment-ordered weight packs live behind the packs above.  RECNOW_TILE=0
+// Row-block persistent kernels (dcnmix_tile.hip).  RECNOW_TILE=0
 // switches the route off, =1 takes it for every supported batch (tests); default: batches up to MIX_TILE_MAX_B rows (the per-rank shards of the
 // 4- and 8-GPU rows), where the launch-per-product route is a chain of single-round launches (measured: 8192 rows 0.76 -> 0.67-0.69 ms per step,
 // 16 384 rows 1.13 -> 1.10-1.13; 32 768 rows 1.87 -> 1.93 and 65 536 rows 3.32 -> 3.85: off there).
 #define MIX_TILE_MAX_B 16384
-static inline bool mix_tile_shape(const MixDims& m) {
-    return m.exact && m.L <= MIX_PACK_MAX_L && m.L <= RN_TILE_MAX_L && rn_mix_tile_supported(m.B, m.D, m.S, m.N, m.L, m.LDT);
-}
-static inline size_t mix_tile_pack_bytes(const MixDims& m) { return mix_tile_shape(m) ? rn_mix_tile_pack_bytes(m.D, m.S, m.N, m.L, m.LDT) : 0; }
-static inline size_t mix_tile_pack_off(const MixDims& m) { return mix_pack_off(m) + mix_pack_bytes(m); }
-// Round 6: the split-precision piece planes of the packed weights, behind the tile packs: per layer P1 ([U | K] as the B operand of GEMM1),
-// P2 ([W; b] of the product that leaves the layer), P3 (W^T -- or the fused head's W * w_head -- of the dT2g product), P4 ([U | K]^T of the
-// product that forms g_{l-1}); written ONCE per step by the forward (rn_split_planes_multi behind k_pack_all) instead of by a split launch in
-// front of each of the 12 products that read them.
-static inline bool mix_planes_shape(const MixDims& m) { return m.exact && m.L <= MIX_PACK_MAX_L && 4 * m.L <= RN_SPLIT_MAX_JOBS && m.NS == 128 && m.KP == 144; }
-static inline size_t mix_plane_long(const MixDims& m) { return rn_gemm_split_planes_bytes(m.D, 128); }
-static inline size_t mix_plane_short(const MixDims& m) { return rn_gemm_split_planes_bytes(m.KP, m.D); }
-static inline size_t mix_planes_bytes(const MixDims& m) { return mix_planes_shape(m) ? (size_t)m.L * 2 * (mix_plane_long(m) + mix_plane_short(m)) : 0; }
-static inline size_t mix_planes_off(const MixDims& m) { return mix_tile_pack_off(m) + mix_tile_pack_bytes(m); }
-// Round 6, second session: the fragment-ordered piece planes of the split-precision row-block forward (dcnmix_tile_split.hip), behind the planes above
-static inline size_t mix_tile_split_bytes(const MixDims& m) { return mix_tile_shape(m) ? rn_mix_tile_split_pack_bytes(m.D, m.S, m.N, m.L, m.LDT) : 0; }
-static inline size_t mix_tile_split_off(const MixDims& m) { return mix_planes_off(m) + mix_planes_bytes(m); }
-static inline char* mix_plane(const MixDims& m, const void* saved, int l, int which) {      // which: 0 = P1, 1 = P2, 2 = P3, 3 = P4
-    char* base = (char*)saved + mix_planes_off(m) + (size_t)l * 2 * (mix_plane_long(m) + mix_plane_short(m));
-    return base + (which == 0 ? 0 : which == 1 ? mix_plane_long(m) : which == 2 ? mix_plane_long(m) + mix_plane_short(m) : 2 * mix_plane_long(m) + mix_plane_short(m));
-}
 // `maybe`: everything but the precision mode -- what a backward pass uses to decide whether the forward that filled `saved` MAY have run the
 // row-block kernels (and left the product-route weight packs out), whatever the precision switch says by now
 // Set by the GROUP phase of recnow_dcn_mix_step when its front kernel has written the tile packs of THIS call's weights into `saved`; taken (and cleared)
@@ -236,14 +171,9 @@ static int mix_stamp_get(const void* sv) {
     return -1;
 }
 
-// saved layout, per layer l: T1, T2, T2g (B x LDT each); then the L-1 intermediate layer outputs x_1..x_{L-1} (B x D);
-// exact path: then O_0..O_{L-1} (B x D)
 extern "C" size_t recnow_dcn_mix_saved_bytes(int64_t B, int D, int S, int N, int L) {
     if (B <= 0 || D <= 0 || S <= 0 || N <= 0 || L <= 0) return 256;
-    const MixDims m = mix_dims(B, D, S, N, L);
-    // exact path: O_l = T2g_l [W; b] of every layer is kept next to x_{l+1} = x * O_l (second output of GEMM3), so the
-    // backward forms dx = sum_l g_l * O_l inside kernels that stream g_l anyway instead of recomputing the products.
-    return (size_t)L * 3 * act_block(m) + (size_t)(L - 1) * xbuf(m) + (m.exact ? (size_t)L * xbuf(m) : 0) + mix_pack_bytes(m) + mix_tile_pack_bytes(m) + mix_planes_bytes(m) + mix_tile_split_bytes(m) + 256;
+    return MixSaved(mix_dims(B, D, S, N, L), nullptr).total + 256;      // a walk over a null base only adds up the sizes
 }
 
 // Round 4: x_{l+1} = x0 * O_l is NOT materialised between the cross layers of the exact path (two experts).  The product that leaves layer l
@@ -266,52 +196,6 @@ static bool mix_xless_saved(const MixDims& m, const void* sv) {      // what the
     const int have = mix_stamp_get(sv);
     return have >= 0 ? (have & MIX_XLESS) != 0 : mix_xless(m);
 }
-
-static size_t mix_gemm_ws(const MixDims& m) {
-    size_t best = 0;
-    recnow_gemm_desc d = rn_gemm_desc_zero();
-    const int shapes[6][3] = {{(int)m.B, m.LDT, m.D}, {(int)m.B, m.D, m.KP}, {m.LDT, m.D, (int)m.B}, {m.D, m.LDT, (int)m.B},
-                              {m.S, m.S, (int)m.B}, {(int)m.B, m.S, m.S}};
-    for (int i = 0; i < 6; ++i) {
-        d.M = shapes[i][0]; d.N = shapes[i][1]; d.K = shapes[i][2]; d.batch = (i >= 4) ? m.N : 1;
-        const size_t s = rn_gemm_ws_bytes(&d);
-        if (s > best) best = s;
-    }
-    if (m.exact) {           // exact-path split-K products carry 4 side columns per slab row
-        d.M = m.D; d.N = m.NS; d.K = (int)m.B; d.batch = 1; d.sp_r = m.N; d.a_trans = 1;
-        size_t s = rn_gemm_ws_bytes(&d);
-        if (s > best) best = s;
-        d.M = (int)m.B; d.N = m.NS; d.K = m.D; d.a_trans = 0;       // x_l U / (x*g) W^T: room for the split-precision planes of the weights
-        s = rn_gemm_ws_bytes(&d);
-        if (s > best) best = s;
-    }
-    return best;
-}
-
-extern "C" size_t recnow_dcn_mix_workspace_bytes(int64_t B, int D, int S, int N, int L) {
-    if (B <= 0 || D <= 0 || S <= 0 || N <= 0 || L <= 0) return 256;
-    const MixDims m = mix_dims(B, D, S, N, L);
-    size_t s = 0;
-    s += rn_align((size_t)D * m.LDT * sizeof(float));        // Wc1
-    s += rn_align((size_t)m.LDT * D * sizeof(float));        // Wc2 (rows >= KC are zero)
-    s += rn_align((size_t)D * m.LDT * sizeof(float));        // dWc1
-    s += rn_align((size_t)m.LDT * D * sizeof(float));        // dWc2
-    s += 3 * act_block(m);                                   // dT2g, dC, dT1
-    s += 2 * xbuf(m);                                        // inter-layer gradient ping-pong
-    s += 3 * rn_align(mix_gemm_ws(m));                       // split-K slabs: chain stream, dU and dW (the last two are reduced together at the layer's end)
-    s += rn_mix_mid_bwd_ws_bytes(B, S, N);                   // per-workgroup dV partials of the fused sub-space backward
-    s += (size_t)L * (rn_align((size_t)D * m.LDT * sizeof(float)) + rn_align((size_t)m.LDT * D * sizeof(float)));   // per-layer packs
-    s += rn_align(rn_colsum_ws_bytes(B, 1));                 // fused scoring head: d bias = sum of dscores
-    if (mix_tile_shape(m)) {                                 // row-block backward: dT1 of every layer, dV partials per layer and workgroup
-        s += (size_t)L * act_block(m);
-        s += rn_align((size_t)L * rn_mix_tile_bwd_grid(B) * N * S * S * sizeof(float));
-        // ... and one split-K slab buffer per weight-gradient product (2 L of them; three are carved above): behind the chain launch all six
-        // products are independent, and sharing slab buffers made each wait for an earlier layer's reduction (round 5, kernel trace at 8192 rows)
-        if (2 * L > 3) s += (size_t)(2 * L - 3) * rn_align(mix_gemm_ws(m));
-    }
-    return s + 4096;
-}
-
 
 // One launch packs the weights of ALL layers (exact path): Wc1_l = [U_l | K_l | 0] (D x LDT) and, when Wc2 != NULL,
 // Wc2_l = [W_l; b_l; 0] (LDT x D).  Replaces 4 tiny launches per layer in front of every product.
@@ -548,22 +432,11 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
     hipStream_t st = (hipStream_t)stream;
     const MixDims m = mix_dims(B, D, S, N, L);
     if (head && !mix_head_ok(m)) return RECNOW_EUNSUPPORTED;
-    RnCarver c(ws, ws_bytes);
-    float* Wc1 = c.take<float>((size_t)D * m.LDT);
-    float* Wc2 = c.take<float>((size_t)m.LDT * D);
-    c.take<float>((size_t)D * m.LDT);
-    c.take<float>((size_t)m.LDT * D);
-    float* hp = c.take<float>(3 * act_block(m) / sizeof(float));      // forward: free -> the head's row-dot partials (B x 2D/128)
-    c.take<float>(2 * xbuf(m) / sizeof(float));
+    const MixWs w = mix_ws(m, ws, ws_bytes, false);
+    if (!w.ok) return RECNOW_EWORKSPACE;
+    float* const hp = w.dT2g;      // the gradient activations are free in a forward pass: the head's row-dot partials (B x 2D/128)
+    const MixSaved sv(m, saved);
     const bool pack_once = m.exact && L <= MIX_PACK_MAX_L;          // all layers' packed weights in one launch, kept in `saved` for the backward
-    char* sv = (char*)saved;
-    float* Wc1_all = pack_once ? (float*)(sv + mix_pack_off(m)) : nullptr;
-    float* Wc2_all = pack_once ? Wc1_all + (size_t)L * D * m.LDT : nullptr;
-    float* Wh_saved = pack_once ? Wc2_all + (size_t)L * m.LDT * D : nullptr;      // fused head: [W; b]_{L-1} * w_head for the backward
-    void* gws = c.base + c.off;
-    const size_t gws_bytes = ws_bytes - c.off;
-    float* xmid = (float*)(sv + (size_t)L * 3 * act_block(m));
-    float* omid = xmid + (size_t)(L - 1) * (xbuf(m) / sizeof(float));        // exact path only
     int rc;
     const bool tile_fwd = mix_tile_on(m) && (y || head);
     // the [U | K] / [W; b] / head packs feed the launch-per-product kernels only: with the row-block kernels in both directions nobody reads them
@@ -571,7 +444,7 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
     const bool pack_product = pack_once && !(tile_fwd && mix_tile_bwd_on(m));
     {
         RnProfRecord* pr_pack = (pack_product && rn_prof_on()) ? rn_prof_begin(RN_TAG_LAYER_END, 0.0, 0.0, st) : nullptr;
-        if (pack_product && (rc = pack_all(m, U_host, W_host, bias_host, gate_host, Wc1_all, Wc2_all, head ? head->w : nullptr, Wh_saved, st)))
+        if (pack_product && (rc = pack_all(m, U_host, W_host, bias_host, gate_host, sv.Wc1(0), sv.Wc2(0), head ? head->w : nullptr, sv.Wh(), st)))
             return rc;
         rn_prof_end(pr_pack, st);
     }
@@ -581,12 +454,10 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
         RnSplitJobs jobs;
         jobs.n = 0;
         for (int l = 0; l < L; ++l) {
-            const float* wc1 = Wc1_all + (size_t)l * D * m.LDT;
-            const float* wc2 = Wc2_all + (size_t)l * m.LDT * D;
-            jobs.job[jobs.n++] = RnSplitJob{wc1, m.LDT, 0, D, 128, mix_plane(m, saved, l, 0)};
-            jobs.job[jobs.n++] = RnSplitJob{wc2, D, 0, m.KP, D, mix_plane(m, saved, l, 1)};
-            jobs.job[jobs.n++] = RnSplitJob{(head && l == L - 1) ? Wh_saved : W_host[l], D, 1, D, 128, mix_plane(m, saved, l, 2)};
-            jobs.job[jobs.n++] = RnSplitJob{wc1, m.LDT, 1, m.KP, D, mix_plane(m, saved, l, 3)};
+            jobs.job[jobs.n++] = RnSplitJob{sv.Wc1(l), m.LDT, 0, D, 128, sv.plane(l, 0)};
+            jobs.job[jobs.n++] = RnSplitJob{sv.Wc2(l), D, 0, m.KP, D, sv.plane(l, 1)};
+            jobs.job[jobs.n++] = RnSplitJob{(head && l == L - 1) ? sv.Wh() : W_host[l], D, 1, D, 128, sv.plane(l, 2)};
+            jobs.job[jobs.n++] = RnSplitJob{sv.Wc1(l), m.LDT, 1, m.KP, D, sv.plane(l, 3)};
         }
         RnProfRecord* pr_pl = rn_prof_on() ? rn_prof_begin(RN_TAG_LAYER_END, 0.0, 0.0, st) : nullptr;
         rc = rn_split_planes_multi(jobs, st);
@@ -602,36 +473,29 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
         RnTileFwd t;
         memset(&t, 0, sizeof(t));
         t.x = x; t.B = B; t.D = D; t.L = L; t.act_inner = act_inner; t.act_outer = act_outer;
-        t.packs = (float*)(sv + mix_tile_pack_off(m));
+        t.packs = sv.tile_packs();
         for (int l = 0; l < L; ++l) {
             t.U[l] = U_host[l]; t.Kg[l] = gate_host[l]; t.V[l] = V_host[l]; t.W[l] = W_host[l]; t.bias[l] = bias_host[l];
-            t.T1[l] = (float*)(sv + (size_t)(3 * l) * act_block(m));
-            t.T2[l] = (float*)(sv + (size_t)(3 * l + 1) * act_block(m));
-            t.T2g[l] = (float*)(sv + (size_t)(3 * l + 2) * act_block(m));
-            t.O[l] = (need_dx || (xless && l < L - 1)) ? omid + (size_t)l * (xbuf(m) / sizeof(float)) : nullptr;
-            t.xn[l] = l < L - 1 ? (xless ? nullptr : xmid + (size_t)l * (xbuf(m) / sizeof(float))) : (head ? nullptr : y);
+            t.T1[l] = sv.T1(l); t.T2[l] = sv.T2(l); t.T2g[l] = sv.T2g(l);
+            t.O[l] = (need_dx || (xless && l < L - 1)) ? sv.O(l) : nullptr;
+            t.xn[l] = l < L - 1 ? (xless ? nullptr : sv.x_next(l)) : (head ? nullptr : y);
         }
         if (head) { t.head_w = head->w; t.head_b = head->b; t.scores = head->scores; }
         t.packed = (tl_step_tile_packed != nullptr && tl_step_tile_packed == (const void*)saved) ? 1 : 0;
         tl_step_tile_packed = nullptr;
         if (tile_split) {
-            t.splanes = sv + mix_tile_split_off(m);
+            t.splanes = sv.tile_split_planes();
             return rn_mix_tile_fwd_split(t, st);
         }
         return rn_mix_tile_fwd(t, st);
     }
     for (int l = 0; l < L; ++l) {
-        float* T1 = (float*)(sv + (size_t)(3 * l) * act_block(m));
-        float* T2 = (float*)(sv + (size_t)(3 * l + 1) * act_block(m));
-        float* T2g = (float*)(sv + (size_t)(3 * l + 2) * act_block(m));
-        float* out = (l == L - 1) ? y : xmid + (size_t)l * (xbuf(m) / sizeof(float));
+        float *T1 = sv.T1(l), *T2 = sv.T2(l), *T2g = sv.T2g(l);
+        float* out = (l == L - 1) ? y : sv.x_next(l);
+        float* const Wc1 = pack_once ? sv.Wc1(l) : w.Wc1;      // packed per layer, unless the one launch above has left every layer's in `saved`
+        float* const Wc2 = pack_once ? sv.Wc2(l) : w.Wc2;
         if (m.exact) {
-            if (pack_once) {
-                Wc1 = Wc1_all + (size_t)l * D * m.LDT;
-                Wc2 = Wc2_all + (size_t)l * m.LDT * D;
-            } else if ((rc = pack_weights(m, U_host[l], V_host[l], W_host[l], bias_host[l], gate_host[l], Wc1, Wc2, st))) {
-                return rc;
-            }
+            if (!pack_once && (rc = pack_weights(m, U_host[l], V_host[l], W_host[l], bias_host[l], gate_host[l], Wc1, Wc2, st))) return rc;
             {
             RnDeferredReduce red1;
             red1.valid = 0;
@@ -644,14 +508,14 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 recnow_gemm_desc d = rn_gemm_desc_zero();
                 d.A = Wc1; d.lda = m.LDT; d.a_trans = 1;             // [U | K]^T: stored [K = D][M = 128 (+ gate columns, unused here)]
                 d.B = xl; d.ldb = D; d.b_trans = 1;                  // x_l^T: stored [N = B][K = D]
-                if (xless && l > 0) { d.B = x; d.B2 = omid + (size_t)(l - 1) * (xbuf(m) / sizeof(float)); d.b_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1}
+                if (xless && l > 0) { d.B = x; d.B2 = sv.O(l - 1); d.b_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1}
                 d.C = T1; d.ldc = m.LDT;                             // (not written: the epilogue stores T1 / T2 / T2g itself)
                 d.M = m.NS; d.N = (int)B; d.K = D;
                 d.prof_flops = 2.0 * (double)B * D * m.KC;
                 d.act = act_inner;
                 d.sp_bx = gate_host[l]; d.sp_bx_ks = N; d.sp_bx_rs = 1; d.sp_cx = T1 + m.NS; d.sp_cx_ms = m.LDT; d.sp_cx_rs = 1; d.sp_r = N;
                 d.mid_V = V_host[l]; d.mid_T1 = T1; d.mid_T2 = T2; d.mid_T2g = T2g; d.mid_ld = m.LDT; d.mid_act_outer = act_outer;
-                rc = rn_gemm(&d, gws, gws_bytes, st);
+                rc = rn_gemm(&d, w.gws, w.gws_bytes, st);
                 if (rc && rc != RECNOW_EUNSUPPORTED) return rc;
             } else {
                 rc = RECNOW_EUNSUPPORTED;
@@ -660,7 +524,7 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
             {   // GEMM1: T1[:, :NS] = act_inner(x_l U);  gate logits T1[:, NS:NS+N] = x_l K as the VALU side product
                 recnow_gemm_desc d = rn_gemm_desc_zero();
                 d.A = xl; d.lda = D; d.a_trans = 0;
-                if (xless && l > 0) { d.A = x; d.A2 = omid + (size_t)(l - 1) * (xbuf(m) / sizeof(float)); d.a_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1}
+                if (xless && l > 0) { d.A = x; d.A2 = sv.O(l - 1); d.a_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1}
                 d.B = Wc1; d.ldb = m.LDT; d.b_trans = 0;
                 d.C = T1; d.ldc = m.LDT;
                 d.M = (int)B; d.N = m.NS; d.K = D;
@@ -669,9 +533,9 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 d.sp_bx = gate_host[l]; d.sp_bx_ks = N; d.sp_bx_rs = 1; d.sp_cx = T1 + m.NS; d.sp_cx_ms = m.LDT; d.sp_cx_rs = 1; d.sp_r = N;
                 // a shard small enough for this product to be split over K: the sub-space kernel sums the slabs (and applies act_inner)
                 // on its way in -- no reduction launch
-                if (planes_on) rn_gemm_planes_hint(mix_plane(m, saved, l, 0));
-                if (absorb) rc = rn_gemm_deferred(&d, gws, gws_bytes, st, &red1);
-                else rc = rn_gemm(&d, gws, gws_bytes, st);
+                if (planes_on) rn_gemm_planes_hint(sv.plane(l, 0));
+                if (absorb) rc = rn_gemm_deferred(&d, w.gws, w.gws_bytes, st, &red1);
+                else rc = rn_gemm(&d, w.gws, w.gws_bytes, st);
                 if (rc) return rc;
             }
             RnSlabs sl;
@@ -684,8 +548,8 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 }
             }
             if (sl.n) {
-                if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, gws, gws_bytes, st, &sl, act_inner))) return rc;
-            } else if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, gws, gws_bytes, st))) return rc;
+                if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, w.gws, w.gws_bytes, st, &sl, act_inner))) return rc;
+            } else if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, w.gws, w.gws_bytes, st))) return rc;
             }      // (not the fused GEMM1)
             }
             {   // GEMM3: out = x * ([G*H2 | G | 0] [W; b; 0]): K zero-padded NS+N -> KP (a 16-deep k-tile more is cheaper
@@ -697,18 +561,18 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 d.M = (int)B; d.N = D; d.K = m.KP; d.k_valid = m.KC;
                 d.prof_flops = 2.0 * (double)B * D * m.KC;
                 d.emul = x; d.lde = D; d.e_mode = RECNOW_OPMODE_MUL;
-                if (need_dx) { d.C2 = omid + (size_t)l * (xbuf(m) / sizeof(float)); d.ldc2 = D; d.c2_mode = 1; }     // O_l only feeds dx
+                if (need_dx) { d.C2 = sv.O(l); d.ldc2 = D; d.c2_mode = 1; }     // O_l only feeds dx
                 if (xless && l < L - 1) {       // O_l alone: x_{l+1} = x0 * O_l is formed where it is consumed (mix_xless)
                     d.emul = nullptr; d.e_mode = RECNOW_OPMODE_NONE; d.C2 = nullptr; d.c2_mode = 0;
-                    d.C = omid + (size_t)l * (xbuf(m) / sizeof(float));
+                    d.C = sv.O(l);
                 }
                 if (head && l == L - 1) {       // the layer output only feeds the scoring head: row-dot partials instead of y
                     d.c2_mode = 3; d.ldc2 = D;
-                    d.C = omid + (size_t)l * (xbuf(m) / sizeof(float));      // not written (c2_mode 3); a valid aligned address for the checks
+                    d.C = sv.O(l);      // not written (c2_mode 3); a valid aligned address for the checks
                     d.hv = head->w; d.hp = hp; d.hp_ld = 2 * (D / 128);
                 }
-                if (planes_on) rn_gemm_planes_hint(mix_plane(m, saved, l, 1));
-                if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+                if (planes_on) rn_gemm_planes_hint(sv.plane(l, 1));
+                if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
                 if (head && l == L - 1) {
                     hipLaunchKernelGGL(k_head_scores, ew_grid(B), 256, 0, st, hp, 2 * (D / 128), head->b, B, head->scores);
                     RN_LAUNCH_CHECK();
@@ -725,9 +589,9 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
             d.C = T1; d.ldc = m.LDT;
             d.M = (int)B; d.N = m.LDT; d.K = D;
             d.act = act_inner; d.act_cols = m.NS;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
         }
-        if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, gws, gws_bytes, st))) return rc;
+        if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, w.gws, w.gws_bytes, st))) return rc;
         {   // GEMM3: out = x * (T2g [W; b])
             recnow_gemm_desc d = rn_gemm_desc_zero();
             d.A = T2g; d.lda = m.LDT; d.a_trans = 0;
@@ -735,7 +599,7 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
             d.C = out; d.ldc = D;
             d.M = (int)B; d.N = D; d.K = m.KP; d.k_valid = m.KC;
             d.emul = x; d.lde = D; d.e_mode = RECNOW_OPMODE_MUL;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
         }
         xl = out;
     }
@@ -825,7 +689,7 @@ struct MixEvents {
 // would run beside it: the products start when it ends.
 static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const* U_host, const float* const* V_host,
                            const float* const* W_host, const float* const* bias_host, const float* const* gate_host,
-                           const float* dy, const char* sv, int act_inner, int act_outer, float* dx, float* const* dU_host,
+                           const float* dy, const MixSavedC& sv, int act_inner, int act_outer, float* dx, float* const* dU_host,
                            float* const* dV_host, float* const* dW_host, float* const* dbias_host, float* const* dgate_host,
                            void* ws, size_t ws_bytes, hipStream_t st, hipStream_t st2, const MixHeadGrad* hd, void* const* layer_events,
                            int l_hi, int l_lo, const float* T2g_ds_ready, const float* ds_part, int ds_nparts) {
@@ -834,54 +698,30 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
     const bool top = l_hi == L - 1;
     const bool two = st2 != nullptr && st2 != st;
     if (!two) st2 = st;
-    RnCarver c(ws, ws_bytes);
-    c.take<float>((size_t)L * D * m.LDT);
-    float* dWc1 = c.take<float>((size_t)D * m.LDT);
-    c.take<float>(act_block(m) / sizeof(float));
-    float* dC = c.take<float>(act_block(m) / sizeof(float));
-    c.take<float>(act_block(m) / sizeof(float));
-    float* gbuf0 = c.take<float>(xbuf(m) / sizeof(float));
-    float* gbuf1 = c.take<float>(xbuf(m) / sizeof(float));
-    const size_t gemm_ws = mix_gemm_ws(m);
-    void* gws1 = c.take<char>(gemm_ws);
-    void* gws2 = c.take<char>(gemm_ws);
-    void* gws3 = c.take<char>(gemm_ws);
-    c.take<char>(rn_mix_mid_bwd_ws_bytes(B, S, N));
-    const size_t cs_ws_bytes = rn_colsum_ws_bytes(B, 1);
-    void* cs_ws = c.take<char>(cs_ws_bytes);
-    float* dT1_all = c.take<float>((size_t)L * act_block(m) / sizeof(float));
-    const int grid = rn_mix_tile_bwd_grid(B);
-    float* dvpart = c.take<float>((size_t)L * grid * N * S * S);
-    if (!c.ok()) return RECNOW_EWORKSPACE;
-    const float* xmid = (const float*)(sv + (size_t)L * 3 * act_block(m));
-    const float* omid = xmid + (size_t)(L - 1) * (xbuf(m) / sizeof(float));
-    const float* Wc1_all = (const float*)(sv + mix_pack_off(m));
-    (void)Wc1_all;
+    const MixWs w = mix_ws_exact(m, ws, ws_bytes, true);      // (every product owns its slabs: w.slab[2 l] dW_l, w.slab[2 l + 1] dU_l)
+    if (!w.ok) return RECNOW_EWORKSPACE;
     MixEvents evs;
     int rc;
-    const float* T2g_ds = dC;
+    const float* T2g_ds = w.dC;
     if (hd && top) {
-        const float* T2g_top = (const float*)(sv + (size_t)(3 * (L - 1) + 2) * act_block(m));
         if (T2g_ds_ready) {
             T2g_ds = T2g_ds_ready;
         } else {
-            hipLaunchKernelGGL(k_row_scale, ew_grid(B * (m.LDT / 4)), 256, 0, st, T2g_top, hd->dscores, B, m.LDT, dC);
+            hipLaunchKernelGGL(k_row_scale, ew_grid(B * (m.LDT / 4)), 256, 0, st, sv.T2g(L - 1), hd->dscores, B, m.LDT, w.dC);
             RN_LAUNCH_CHECK();
-            if (hd->db && (rc = rn_colsum(hd->dscores, nullptr, 0, 0, B, 1, 1, hd->db, 0, cs_ws, cs_ws_bytes, st))) return rc;
+            if (hd->db && (rc = rn_colsum(hd->dscores, nullptr, 0, 0, B, 1, 1, hd->db, 0, w.cs_ws, w.cs_ws_bytes, st))) return rc;
         }
     }
-    auto gbuf_of = [&](int l) { return (l & 1) ? gbuf0 : gbuf1; };          // g_l = d loss / d x_l, l >= 1 (the buffers of the product route)
+    auto gbuf_of = [&](int l) { return (l & 1) ? w.g0 : w.g1; };          // g_l = d loss / d x_l, l >= 1 (the buffers of the product route)
     {
         RnTileBwd t;
         memset(&t, 0, sizeof(t));
-        t.x = x; t.packs = (const float*)(sv + mix_tile_pack_off(m)); t.B = B; t.D = D; t.L = L; t.l_hi = l_hi; t.l_lo = l_lo;
-        t.act_inner = act_inner; t.act_outer = act_outer; t.dx = dx; t.dvpart = dvpart;
+        t.x = x; t.packs = sv.tile_packs(); t.B = B; t.D = D; t.L = L; t.l_hi = l_hi; t.l_lo = l_lo;
+        t.act_inner = act_inner; t.act_outer = act_outer; t.dx = dx; t.dvpart = w.dvpart;
         for (int l = 0; l < L; ++l) {
             t.Kg[l] = gate_host[l]; t.bias[l] = bias_host[l];
-            t.T1[l] = (const float*)(sv + (size_t)(3 * l) * act_block(m));
-            t.T2[l] = (const float*)(sv + (size_t)(3 * l + 1) * act_block(m));
-            t.O[l] = omid + (size_t)l * (xbuf(m) / sizeof(float));
-            t.dT1[l] = dT1_all + (size_t)l * (act_block(m) / sizeof(float));
+            t.T1[l] = sv.T1(l); t.T2[l] = sv.T2(l); t.O[l] = sv.O(l);
+            t.dT1[l] = w.dT1_of(l);
             t.gout[l] = l > 0 ? gbuf_of(l) : nullptr;
         }
         if (top) {
@@ -907,16 +747,6 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
     // reduction at 587-595 -- 217 us for 12.9 GFLOP.  Now every product owns its slabs, ALL products are issued first (dW_l on the second stream,
     // dU_l on the first: three concurrent pairs back to back), and the reductions follow: the top layer's (+ the head's post-processing) on the
     // first stream, the others on the second, each behind the events of its two products.
-    void* slab_w[RN_TILE_MAX_L];
-    void* slab_u[RN_TILE_MAX_L];
-    {
-        void* pool[2 * RN_TILE_MAX_L];
-        int np = 0;
-        pool[np++] = gws1; pool[np++] = gws2; pool[np++] = gws3;
-        for (int i = 3; i < 2 * L; ++i) pool[np++] = c.take<char>(gemm_ws);
-        if (!c.ok()) return RECNOW_EWORKSPACE;
-        for (int l = 0; l < L; ++l) { slab_w[l] = pool[2 * l]; slab_u[l] = pool[2 * l + 1]; }
-    }
     RnDeferredReduce red_dw[RN_TILE_MAX_L], red_du[RN_TILE_MAX_L];
     hipEvent_t e_dw[RN_TILE_MAX_L], e_du[RN_TILE_MAX_L];
     for (int l = 0; l < RN_TILE_MAX_L; ++l) { red_dw[l].valid = red_du[l].valid = 0; e_dw[l] = e_du[l] = nullptr; }
@@ -931,7 +761,7 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
         else MIX_WAIT(e_du[l], st2);
         RnProfRecord* pr_end = rn_prof_on() ? rn_prof_begin(RN_TAG_LAYER_END, 0.0, 0.0, sr) : nullptr;
         int rr;
-        if ((rr = rn_layer_end_reduce(&red_dw[l], &red_du[l], dvpart + (size_t)l * grid * N * S * S, grid, N * S * S, dV_host[l], sr))) return rr;
+        if ((rr = rn_layer_end_reduce(&red_dw[l], &red_du[l], w.dvpart_of(l), w.grid, N * S * S, dV_host[l], sr))) return rr;
         if (hd && l == L - 1) {
             hipLaunchKernelGGL(k_head_post, rn_cdiv(D, 32), 256, 0, sr, dW_host[l], dbias_host[l], W_host[l], bias_host[l], hd->w, m.NS, N, D, hd->dw,
                                ds_part, ds_nparts, ds_part ? hd->db : nullptr);
@@ -942,10 +772,10 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
         return RECNOW_OK;
     };
     for (int l = l_hi; l >= l_lo; --l) {
-        const float* T2g = (const float*)(sv + (size_t)(3 * l + 2) * act_block(m));
-        const float* xl = (l == 0) ? x : xmid + (size_t)(l - 1) * (xbuf(m) / sizeof(float));
+        const float* T2g = sv.T2g(l);
+        const float* xl = (l == 0) ? x : sv.x_next(l - 1);
         const float* g = (l == L - 1) ? dy : gbuf_of(l + 1);
-        const float* dT1 = dT1_all + (size_t)l * (act_block(m) / sizeof(float));
+        const float* dT1 = w.dT1_of(l);
         {   // dW^T = (x*g)^T T2g[:, :NS] stored transposed straight into dW (NS x D);  dbias[n][d] as the side product
             recnow_gemm_desc d = rn_gemm_desc_zero();
             const bool top_head = hd && l == L - 1;
@@ -959,24 +789,24 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
             d.M = D; d.N = m.NS; d.K = (int)B;
             d.prof_flops = 2.0 * (double)B * D * m.KC;
             d.sp_bx = d.B + m.NS; d.sp_bx_ks = m.LDT; d.sp_bx_rs = 1; d.sp_cx = dbias_host[l]; d.sp_cx_ms = 1; d.sp_cx_rs = D; d.sp_r = N;
-            if ((rc = rn_gemm_deferred(&d, slab_w[l], gemm_ws, st2, &red_dw[l]))) return rc;
+            if ((rc = rn_gemm_deferred(&d, w.slab[2 * l], w.slab_bytes, st2, &red_dw[l]))) return rc;
             MIX_SIGNAL(e_dw[l], st2);
         }
         {   // dWc1 = x_l^T dT1[:, :NS] -> dU;  dgate[d][n] = x_l^T dlogits as the side product
             recnow_gemm_desc d = rn_gemm_desc_zero();
             d.A = xl; d.lda = D; d.a_trans = 1;
-            if (mix_xless_saved(m, sv) && l > 0) { d.A = x; d.A2 = omid + (size_t)(l - 1) * (xbuf(m) / sizeof(float)); d.a_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1} (not stored)
+            if (mix_xless_saved(m, sv.base) && l > 0) { d.A = x; d.A2 = sv.O(l - 1); d.a_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1} (not stored)
             d.B = dT1; d.ldb = m.LDT; d.b_trans = 0;
-            d.C = dWc1; d.ldc = m.NS;
+            d.C = w.dWc1; d.ldc = m.NS;
             d.M = D; d.N = m.NS; d.K = (int)B;
             d.prof_flops = 2.0 * (double)B * D * m.KC;
             d.sp_bx = dT1 + m.NS; d.sp_bx_ks = m.LDT; d.sp_bx_rs = 1; d.sp_cx = dgate_host[l]; d.sp_cx_ms = N; d.sp_cx_rs = 1; d.sp_r = N;
             recnow_gemm_desc dq = d;
             dq.C = dU_host[l]; dq.c_perm_s = S;
-            rc = rn_gemm_deferred(&dq, slab_u[l], gemm_ws, st, &red_du[l]);
+            rc = rn_gemm_deferred(&dq, w.slab[2 * l + 1], w.slab_bytes, st, &red_du[l]);
             if (rc == RECNOW_EUNSUPPORTED) {       // no split: the product stores (D, N S) and is unpacked (dWc1 is reused in stream order)
-                if ((rc = rn_gemm(&d, slab_u[l], gemm_ws, st))) return rc;
-                hipLaunchKernelGGL(k_unpack_u, pg, 256, 0, st, dWc1, D, S, N, dU_host[l]);
+                if ((rc = rn_gemm(&d, w.slab[2 * l + 1], w.slab_bytes, st))) return rc;
+                hipLaunchKernelGGL(k_unpack_u, pg, 256, 0, st, w.dWc1, D, S, N, dU_host[l]);
                 RN_LAUNCH_CHECK();
             } else if (rc) {
                 return rc;
@@ -995,7 +825,7 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
 
 static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const* U_host, const float* const* V_host,
                             const float* const* W_host, const float* const* bias_host, const float* const* gate_host,
-                            const float* dy, const char* sv, int act_inner, int act_outer, float* dx, float* const* dU_host,
+                            const float* dy, const void* saved, int act_inner, int act_outer, float* dx, float* const* dU_host,
                             float* const* dV_host, float* const* dW_host, float* const* dbias_host, float* const* dgate_host,
                             void* ws, size_t ws_bytes, hipStream_t st, hipStream_t st2, const MixHeadGrad* hd = nullptr,
                             void* const* layer_events = nullptr, int l_hi = -1, int l_lo = 0, const float* T2g_ds_ready = nullptr,
@@ -1011,15 +841,16 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     // Measured on one box, ms per step at 8192 / 16 384 rows per GPU: product route 0.760-0.765 / 1.138-1.143, row-block forward alone 0.723-0.726 /
     // 1.135-1.154, forward and backward 0.699-0.708 / 1.128-1.129 (0.67-0.68 / 1.10 with the paired weight-gradient products at 256 slots).
     const bool top = l_hi == L - 1;
-    const int have = mix_stamp_get(sv);          // what the forward left in `saved` (-1: a forward this copy of the library did not see)
+    const MixSavedC sv(m, saved);
+    const int have = mix_stamp_get(saved);       // what the forward left in `saved` (-1: a forward this copy of the library did not see)
     bool want_tile = mix_tile_on(m) && mix_tile_bwd_on(m) && (l_hi < L - 1 || hd || dy);
     if (!top && have >= 0) want_tile = (have & MIX_BWD_TILE) != 0 && mix_tile_shape(m);      // a lower piece follows the top piece of its pass
     if (want_tile) {
         if (top && !(have >= 0 && (have & MIX_HAS_TILE_PACKS))) {      // product-route forward (or unknown): the fragment-ordered packs are made here
             int rc0;
-            if ((rc0 = rn_mix_tile_pack(U_host, gate_host, V_host, W_host, bias_host, D, L, (float*)(sv + mix_tile_pack_off(m)), st))) return rc0;
+            if ((rc0 = rn_mix_tile_pack(U_host, gate_host, V_host, W_host, bias_host, D, L, const_cast<float*>(sv.tile_packs()), st))) return rc0;
         }
-        if (top) mix_stamp_put(sv, (have < 0 ? 0 : have) | MIX_HAS_TILE_PACKS | MIX_BWD_TILE);
+        if (top) mix_stamp_put(saved, (have < 0 ? 0 : have) | MIX_HAS_TILE_PACKS | MIX_BWD_TILE);
         return dcnmix_bwd_tile(m, x, U_host, V_host, W_host, bias_host, gate_host, dy, sv, act_inner, act_outer, dx, dU_host, dV_host, dW_host,
                                dbias_host, dgate_host, ws, ws_bytes, st, st2, hd, layer_events, l_hi, l_lo, T2g_ds_ready, ds_part, ds_nparts);
     }
@@ -1029,43 +860,29 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     // RECNOW_TWO_STREAMS=2 ("paired"): BOTH weight-gradient products of a layer (MFMA-bound) are held back until the sub-space
     // backward is done, so that they run beside the layer's dx product (HBM-bound) instead of beside the MFMA-bound dT2g product
     static const bool paired = rn_env_int("RECNOW_TWO_STREAMS", 0) == 2;
-    RnCarver c(ws, ws_bytes);
-    float* Wc1_all = c.take<float>((size_t)L * D * m.LDT);        // per-layer packs (L > MIX_PACK_MAX_L only: otherwise the forward's, in `saved`)
-    float* dWc1 = c.take<float>((size_t)D * m.LDT);
-    float* dT2g = c.take<float>(act_block(m) / sizeof(float));
-    float* dC = c.take<float>(act_block(m) / sizeof(float));
-    float* dT1 = c.take<float>(act_block(m) / sizeof(float));
-    float* gbuf0 = c.take<float>(xbuf(m) / sizeof(float));
-    float* gbuf1 = c.take<float>(xbuf(m) / sizeof(float));
-    const size_t gemm_ws = mix_gemm_ws(m);
-    void* gws = c.take<char>(gemm_ws);                              // split-K slabs of the chain stream
-    void* gws2 = c.take<char>(gemm_ws);                             // ... of the dU product
-    void* gws3 = c.take<char>(gemm_ws);                             // ... of the dW product (kept until the layer-end reduction)
-    const size_t mid_ws_bytes = rn_mix_mid_bwd_ws_bytes(B, S, N);
-    void* mid_ws = c.take<char>(mid_ws_bytes);
-    const size_t cs_ws_bytes = rn_colsum_ws_bytes(B, 1);
-    void* cs_ws = c.take<char>(cs_ws_bytes);
-    if (!c.ok()) return RECNOW_EWORKSPACE;
-    const float* xmid = (const float*)(sv + (size_t)L * 3 * act_block(m));
-    const float* omid = xmid + (size_t)(L - 1) * (xbuf(m) / sizeof(float));
+    const MixWs w = mix_ws_exact(m, ws, ws_bytes, false);
+    if (!w.ok) return RECNOW_EWORKSPACE;
+    float *const dT2g = w.dT2g, *const dC = w.dC, *const dT1 = w.dT1, *const dWc1 = w.dWc1, *const gbuf0 = w.g0, *const gbuf1 = w.g1;
+    void *const gws = w.slab[0], *const gws2 = w.slab[1], *const gws3 = w.slab[2];      // split-K slabs: chain stream, dU product, dW product
+    const size_t gemm_ws = w.slab_bytes;
     MixEvents evs;
     int rc;
-    const float* Wh = nullptr;         // fused head: [W * w_head; bias * w_head] of the top layer, packed by the forward
-    if (L <= MIX_PACK_MAX_L) {         // [U | K | 0] of every layer: packed ONCE per step by the forward, kept behind the activations in `saved`
-        Wc1_all = (float*)(sv + mix_pack_off(m));
-        Wh = Wc1_all + (size_t)2 * L * D * m.LDT;
+    const bool saved_packs = L <= MIX_PACK_MAX_L;      // [U | K | 0] of every layer: packed ONCE per step by the forward, kept in `saved`; else in the workspace
+    const float* Wh = saved_packs ? sv.Wh() : nullptr;      // fused head: [W * w_head; bias * w_head] of the top layer, packed by the forward
+    if (saved_packs) {
         // ... unless the forward ran the row-block kernels in both directions and left them out (RECNOW_TILE_BWD=0 A/B pairing, or the precision /
         // RECNOW_TILE switched in between): packed here.  Unknown forward: packed whenever the shape may have taken the row-block route.
         if (top && (have >= 0 ? !(have & MIX_HAS_PRODUCT_PACKS) : mix_tile_on(m, true))) {
-            float* Wc2_all = Wc1_all + (size_t)L * D * m.LDT;
-            if ((rc = pack_all(m, U_host, W_host, bias_host, gate_host, Wc1_all, Wc2_all, hd ? hd->w : nullptr, const_cast<float*>(Wh), st))) return rc;
+            if ((rc = pack_all(m, U_host, W_host, bias_host, gate_host, const_cast<float*>(sv.Wc1(0)), const_cast<float*>(sv.Wc2(0)), hd ? hd->w : nullptr,
+                               const_cast<float*>(Wh), st)))
+                return rc;
         }
-        if (top && have >= 0) mix_stamp_put(sv, (have | MIX_HAS_PRODUCT_PACKS) & ~MIX_BWD_TILE);
+        if (top && have >= 0) mix_stamp_put(saved, (have | MIX_HAS_PRODUCT_PACKS) & ~MIX_BWD_TILE);
     } else if (top) {
         int pgw = rn_cdiv((int64_t)D * m.LDT, 256);
         if (pgw > 2048) pgw = 2048;
         for (int l = 0; l < L; ++l) {
-            hipLaunchKernelGGL(k_pack_w1, pgw, 256, 0, st, U_host[l], gate_host[l], D, S, N, m.LDT, Wc1_all + (size_t)l * D * m.LDT);
+            hipLaunchKernelGGL(k_pack_w1, pgw, 256, 0, st, U_host[l], gate_host[l], D, S, N, m.LDT, w.Wc1_of(l));
             RN_LAUNCH_CHECK();
         }
     }
@@ -1073,16 +890,15 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     const bool planes_bwd = rn_gemm_precision() == 1 && have >= 0 && (have & MIX_HAS_SPLIT_PLANES) && (have & MIX_HAS_PRODUCT_PACKS) && mix_planes_shape(m);
     const float* T2g_ds = dC;          // fused head: dscore * T2g of the top layer (dC is scratch of the unfused sub-space route only)
     if (hd && top) {
-        const float* T2g_top = (const float*)(sv + (size_t)(3 * (L - 1) + 2) * act_block(m));
         if (T2g_ds_ready) {            // the caller's loss stage has already formed dscore * T2g_top and d bias = sum of dscores (recnow_dcn_mix_step)
             T2g_ds = T2g_ds_ready;
         } else {
-            hipLaunchKernelGGL(k_row_scale, ew_grid(B * (m.LDT / 4)), 256, 0, st, T2g_top, hd->dscores, B, m.LDT, dC);
+            hipLaunchKernelGGL(k_row_scale, ew_grid(B * (m.LDT / 4)), 256, 0, st, sv.T2g(L - 1), hd->dscores, B, m.LDT, dC);
             RN_LAUNCH_CHECK();
-            if (hd->db && (rc = rn_colsum(hd->dscores, nullptr, 0, 0, B, 1, 1, hd->db, 0, cs_ws, cs_ws_bytes, st))) return rc;
+            if (hd->db && (rc = rn_colsum(hd->dscores, nullptr, 0, 0, B, 1, 1, hd->db, 0, w.cs_ws, w.cs_ws_bytes, st))) return rc;
         }
         if (dx && L == 1) {            // a single cross layer: its dx product accumulates on top of the head's term
-            hipLaunchKernelGGL(k_head_dx_top, ew_grid(B * (D / 4)), 256, 0, st, omid, hd->dscores, hd->w, B, D, dx);
+            hipLaunchKernelGGL(k_head_dx_top, ew_grid(B * (D / 4)), 256, 0, st, sv.O(0), hd->dscores, hd->w, B, D, dx);
             RN_LAUNCH_CHECK();
         }
     }
@@ -1096,12 +912,10 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     int pg = rn_cdiv((int64_t)D * m.NS, 256);
     if (pg > 2048) pg = 2048;
     for (int l = l_hi; l >= l_lo; --l) {
-        const float* T1 = (const float*)(sv + (size_t)(3 * l) * act_block(m));
-        const float* T2 = (const float*)(sv + (size_t)(3 * l + 1) * act_block(m));
-        const float* T2g = (const float*)(sv + (size_t)(3 * l + 2) * act_block(m));
-        const float* xl = (l == 0) ? x : xmid + (size_t)(l - 1) * (xbuf(m) / sizeof(float));
+        const float *T1 = sv.T1(l), *T2 = sv.T2(l), *T2g = sv.T2g(l);
+        const float* xl = (l == 0) ? x : sv.x_next(l - 1);
         float* gprev = (l == 0) ? nullptr : ((l & 1) ? gbuf0 : gbuf1);
-        const float* Wc1 = Wc1_all + (size_t)l * D * m.LDT;
+        const float* Wc1 = saved_packs ? sv.Wc1(l) : w.Wc1_of(l);
         RnDeferredReduce red_dw, red_du, red_t2g;
         red_dw.valid = red_du.valid = red_t2g.valid = 0;
         const bool absorb_bwd = defer_dv && rn_mix_mid_absorbs_slabs(B, S, N, m.LDT);
@@ -1142,12 +956,12 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
                 d.B = Wh;
                 d.sp_bx = Wh + (size_t)m.NS * D;
             } else if (l == L - 1 && dx) {      // top layer: this product streams g = dy anyway -> dx = dy * O_{L-1} written on the way
-                d.as_in = omid + (size_t)l * (xbuf(m) / sizeof(float));
+                d.as_in = sv.O(l);
                 d.as_out = dx;
             }
             // split over K at small shards: the sub-space kernel sums the slabs on its way in (no reduction launch)
             // (split precision: the planes of W^T / W * w_head that the forward left; the head's variant only behind a forward that had the head)
-            if (planes_bwd && (l < L - 1 || ((hd != nullptr) == ((have & MIX_PLANES_HEAD) != 0)))) rn_gemm_planes_hint(mix_plane(m, sv, l, 2));
+            if (planes_bwd && (l < L - 1 || ((hd != nullptr) == ((have & MIX_PLANES_HEAD) != 0)))) rn_gemm_planes_hint(sv.plane(l, 2));
             if (absorb_bwd) rc = rn_gemm_deferred(&d, gws, gemm_ws, st, &red_t2g);
             else rc = rn_gemm(&d, gws, gemm_ws, st);
             if (rc) return rc;
@@ -1162,14 +976,14 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
         MIX_WAIT(e_side_prev, st);          // dT1 (and the g buffer about to be rewritten) are free again
         // gate backward, dA_n = (dC_n V_n^T) * act_inner'(H1_n) and dV_n = H1_n^T dC_n
         if (hd && l == L - 1) {
-            if ((rc = rn_mix_mid_bwd(dT2g, T2, T1, V_host[l], dT1, dV_host[l], B, S, N, m.LDT, act_inner, act_outer, mid_ws, mid_ws_bytes, st, hd->dscores,
+            if ((rc = rn_mix_mid_bwd(dT2g, T2, T1, V_host[l], dT1, dV_host[l], B, S, N, m.LDT, act_inner, act_outer, w.mid_ws, w.mid_ws_bytes, st, hd->dscores,
                                      defer_dv, slp)))
                 return rc;
         } else if (defer_dv) {
-            if ((rc = rn_mix_mid_bwd(dT2g, T2, T1, V_host[l], dT1, dV_host[l], B, S, N, m.LDT, act_inner, act_outer, mid_ws, mid_ws_bytes, st, nullptr, true,
+            if ((rc = rn_mix_mid_bwd(dT2g, T2, T1, V_host[l], dT1, dV_host[l], B, S, N, m.LDT, act_inner, act_outer, w.mid_ws, w.mid_ws_bytes, st, nullptr, true,
                                      slp)))
                 return rc;
-        } else if ((rc = mix_mid_bwd(m, dT2g, T2, T1, V_host[l], dC, dT1, dV_host[l], act_inner, act_outer, mid_ws, mid_ws_bytes, gws, gemm_ws, st)))
+        } else if ((rc = mix_mid_bwd(m, dT2g, T2, T1, V_host[l], dC, dT1, dV_host[l], act_inner, act_outer, w.mid_ws, w.mid_ws_bytes, gws, gemm_ws, st)))
             return rc;
         hipEvent_t e_dT1 = nullptr;
         MIX_SIGNAL(e_dT1, st);
@@ -1190,18 +1004,18 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
                 if (l == 0) {
                     d.accumulate = 0;
                     d.c2_mode = (L == 3) ? 5 : 6;
-                    d.E2 = gbuf0; d.E3 = omid; d.lde2 = d.lde3 = D;                                       // g_1 (layer 1 writes gbuf0), O_0
-                    if (L == 3) { d.E4 = gbuf1; d.E5 = omid + (size_t)1 * (xbuf(m) / sizeof(float)); }    // g_2, O_1
-                    d.E6 = omid + (size_t)(L - 1) * (xbuf(m) / sizeof(float)); d.rv = hd->dscores; d.cv = hd->w;
+                    d.E2 = gbuf0; d.E3 = sv.O(0); d.lde2 = d.lde3 = D;      // g_1 (layer 1 writes gbuf0), O_0
+                    if (L == 3) { d.E4 = gbuf1; d.E5 = sv.O(1); }           // g_2, O_1
+                    d.E6 = sv.O(L - 1); d.rv = hd->dscores; d.cv = hd->w;
                 }
             } else {
-            if (l > 0 && dx) { d.C2 = dx; d.ldc2 = D; d.E2 = omid + (size_t)(l - 1) * (xbuf(m) / sizeof(float)); d.lde2 = D; d.c2_mode = 2; }
+            if (l > 0 && dx) { d.C2 = dx; d.ldc2 = D; d.E2 = sv.O(l - 1); d.lde2 = D; d.c2_mode = 2; }
             if (hd && l == L - 1 && l > 0 && dx) {       // first write of dx: g_{l-1} * O_{l-1} + dscore (x) w_head * O_{L-1}
                 d.c2_mode = 4;
-                d.E3 = omid + (size_t)l * (xbuf(m) / sizeof(float)); d.lde3 = D; d.rv = hd->dscores; d.cv = hd->w;
+                d.E3 = sv.O(l); d.lde3 = D; d.rv = hd->dscores; d.cv = hd->w;
             }
             }
-            if (planes_bwd) rn_gemm_planes_hint(mix_plane(m, sv, l, 3));
+            if (planes_bwd) rn_gemm_planes_hint(sv.plane(l, 3));
             if ((rc = rn_gemm(&d, gws, gemm_ws, st))) return rc;
         }
         if (l > 0) MIX_SIGNAL(e_g, st);
@@ -1211,7 +1025,7 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
         {   // dWc1 = x_l^T dT1[:, :NS] -> dU;  dgate[d][n] = x_l^T dlogits as the side product
             recnow_gemm_desc d = rn_gemm_desc_zero();
             d.A = xl; d.lda = D; d.a_trans = 1;
-            if (mix_xless_saved(m, sv) && l > 0) { d.A = x; d.A2 = omid + (size_t)(l - 1) * (xbuf(m) / sizeof(float)); d.a_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1} (not stored)
+            if (mix_xless_saved(m, sv.base) && l > 0) { d.A = x; d.A2 = sv.O(l - 1); d.a_mode = RECNOW_OPMODE_MUL; }      // x_l = x0 * O_{l-1} (not stored)
             d.B = dT1; d.ldb = m.LDT; d.b_trans = 0;
             d.C = dWc1; d.ldc = m.NS;
             d.M = D; d.N = m.NS; d.K = (int)B;
@@ -1231,7 +1045,7 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
         }
         // the layer's end: slab reductions of dW (+ dbias) and dU (+ dgate) and the dV partial sum in ONE launch
         RnProfRecord* pr_end = rn_prof_on() ? rn_prof_begin(RN_TAG_LAYER_END, 0.0, 0.0, st2) : nullptr;
-        if ((rc = rn_layer_end_reduce(&red_dw, &red_du, defer_dv ? (const float*)mid_ws : nullptr, rn_mix_mid_bwd_nparts(B), N * S * S, dV_host[l], st2)))
+        if ((rc = rn_layer_end_reduce(&red_dw, &red_du, defer_dv ? (const float*)w.mid_ws : nullptr, rn_mix_mid_bwd_nparts(B), N * S * S, dV_host[l], st2)))
             return rc;
         if (hd && l == L - 1) {      // dW = w_head * M^T, dbias likewise, d w_head = sum_k [W; b] * M^T (on the reduced M^T)
             hipLaunchKernelGGL(k_head_post, rn_cdiv(D, 32), 256, 0, st2, dW_host[l], dbias_host[l], W_host[l], bias_host[l], hd->w, m.NS, N, D, hd->dw,
@@ -1274,34 +1088,19 @@ extern "C" int recnow_dcn_mix_bwd(const float* x, const float* const* U_host, co
     if (ws_bytes < recnow_dcn_mix_workspace_bytes(B, D, S, N, L)) return RECNOW_EWORKSPACE;
     const MixDims m = mix_dims(B, D, S, N, L);
     if (m.exact)
-        return dcnmix_bwd_exact(m, x, U_host, V_host, W_host, bias_host, gate_host, dy, (const char*)saved, act_inner, act_outer, dx,
+        return dcnmix_bwd_exact(m, x, U_host, V_host, W_host, bias_host, gate_host, dy, saved, act_inner, act_outer, dx,
                                 dU_host, dV_host, dW_host, dbias_host, dgate_host, ws, ws_bytes, st, (hipStream_t)stream2);
-    RnCarver c(ws, ws_bytes);
-    float* Wc1 = c.take<float>((size_t)D * m.LDT);
-    float* Wc2 = c.take<float>((size_t)m.LDT * D);
-    float* dWc1 = c.take<float>((size_t)D * m.LDT);
-    float* dWc2 = c.take<float>((size_t)m.LDT * D);
-    float* dT2g = c.take<float>(act_block(m) / sizeof(float));
-    float* dC = c.take<float>(act_block(m) / sizeof(float));
-    float* dT1 = c.take<float>(act_block(m) / sizeof(float));
-    float* gbuf0 = c.take<float>(xbuf(m) / sizeof(float));
-    float* gbuf1 = c.take<float>(xbuf(m) / sizeof(float));
-    const size_t mid_ws_bytes = rn_mix_mid_bwd_ws_bytes(B, S, N);
-    void* mid_ws = c.take<char>(mid_ws_bytes);
-    if (!c.ok()) return RECNOW_EWORKSPACE;
-    void* gws = c.base + c.off;
-    const size_t gws_bytes = ws_bytes - c.off;
-    const char* sv = (const char*)saved;
-    const float* xmid = (const float*)(sv + (size_t)L * 3 * act_block(m));
+    const MixWs w = mix_ws(m, ws, ws_bytes, true);
+    if (!w.ok) return RECNOW_EWORKSPACE;
+    float *const Wc1 = w.Wc1, *const Wc2 = w.Wc2, *const dWc1 = w.dWc1, *const dWc2 = w.dWc2, *const dT2g = w.dT2g, *const dT1 = w.dT1;
+    const MixSavedC sv(m, saved);
     int rc;
     const float* g = dy;                     // gradient w.r.t. the current layer's output
     bool dx_started = false;                 // dx accumulates the x (= x0) contributions of every layer
     for (int l = L - 1; l >= 0; --l) {
-        const float* T1 = (const float*)(sv + (size_t)(3 * l) * act_block(m));
-        const float* T2 = (const float*)(sv + (size_t)(3 * l + 1) * act_block(m));
-        const float* T2g = (const float*)(sv + (size_t)(3 * l + 2) * act_block(m));
-        const float* xl = (l == 0) ? x : xmid + (size_t)(l - 1) * (xbuf(m) / sizeof(float));
-        float* gprev = (l == 0) ? nullptr : ((l & 1) ? gbuf0 : gbuf1);
+        const float *T1 = sv.T1(l), *T2 = sv.T2(l), *T2g = sv.T2g(l);
+        const float* xl = (l == 0) ? x : sv.x_next(l - 1);
+        float* gprev = (l == 0) ? nullptr : ((l & 1) ? w.g0 : w.g1);
         if ((rc = pack_weights(m, U_host[l], V_host[l], W_host[l], bias_host[l], gate_host[l], Wc1, Wc2, st))) return rc;
         {   // dT2g = (x * g) Wc2^T
             recnow_gemm_desc d = rn_gemm_desc_zero();
@@ -1309,7 +1108,7 @@ extern "C" int recnow_dcn_mix_bwd(const float* x, const float* const* U_host, co
             d.B = Wc2; d.ldb = D; d.b_trans = 1;
             d.C = dT2g; d.ldc = m.LDT;
             d.M = (int)B; d.N = m.LDT; d.K = D;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
         }
         {   // dWc2 = T2g^T (x * g)          -> dW (NS x D) and dbias (N x D).  Computed as the transposed product
             // (M = D rows, N = NS+N columns: tiles 128x160 are 81% full instead of 51% for M = 130) and stored transposed.
@@ -1318,7 +1117,7 @@ extern "C" int recnow_dcn_mix_bwd(const float* x, const float* const* U_host, co
             d.B = T2g; d.ldb = m.LDT; d.b_trans = 0;
             d.C = dWc2; d.ldc = D; d.c_trans = 1;
             d.M = D; d.N = m.LDT; d.K = (int)B;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
             RN_HIP(hipMemcpyAsync(dW_host[l], dWc2, (size_t)m.NS * D * sizeof(float), hipMemcpyDeviceToDevice, st));
             RN_HIP(hipMemcpyAsync(dbias_host[l], dWc2 + (size_t)m.NS * D, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
@@ -1330,10 +1129,10 @@ extern "C" int recnow_dcn_mix_bwd(const float* x, const float* const* U_host, co
             d.M = (int)B; d.N = D; d.K = m.KP; d.k_valid = m.KC;
             d.emul = g; d.lde = D; d.e_mode = RECNOW_OPMODE_MUL;
             d.accumulate = dx_started ? 1 : 0;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
             dx_started = true;
         }
-        if ((rc = mix_mid_bwd(m, dT2g, T2, T1, V_host[l], dC, dT1, dV_host[l], act_inner, act_outer, mid_ws, mid_ws_bytes, gws, gws_bytes, st)))
+        if ((rc = mix_mid_bwd(m, dT2g, T2, T1, V_host[l], w.dC, dT1, dV_host[l], act_inner, act_outer, w.mid_ws, w.mid_ws_bytes, w.gws, w.gws_bytes, st)))
             return rc;
         {   // dWc1 = x_l^T dT1              -> dU, dgate
             recnow_gemm_desc d = rn_gemm_desc_zero();
@@ -1341,7 +1140,7 @@ extern "C" int recnow_dcn_mix_bwd(const float* x, const float* const* U_host, co
             d.B = dT1; d.ldb = m.LDT; d.b_trans = 0;
             d.C = dWc1; d.ldc = m.LDT;
             d.M = D; d.N = m.LDT; d.K = (int)B;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
             int gg = rn_cdiv((int64_t)D * m.KC, 256);
             if (gg > 2048) gg = 2048;
             hipLaunchKernelGGL(k_unpack_w1, gg, 256, 0, st, dWc1, D, S, N, m.LDT, dU_host[l], dgate_host[l]);
@@ -1354,7 +1153,7 @@ extern "C" int recnow_dcn_mix_bwd(const float* x, const float* const* U_host, co
             d.C = (l == 0) ? dx : gprev; d.ldc = D;
             d.M = (int)B; d.N = D; d.K = m.KP; d.k_valid = m.KC;
             d.accumulate = (l == 0) ? 1 : 0;
-            if ((rc = rn_gemm(&d, gws, gws_bytes, st))) return rc;
+            if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
         }
         g = gprev;
     }
@@ -1396,7 +1195,7 @@ extern "C" int recnow_dcn_mix_score_bwd(const float* x, const float* const* U_ho
     if (!mix_head_ok(m)) return RECNOW_EUNSUPPORTED;
     MixHeadGrad hd;
     hd.w = head_w; hd.dscores = dscores; hd.dw = dhead_w; hd.db = dhead_b;
-    return dcnmix_bwd_exact(m, x, U_host, V_host, W_host, bias_host, gate_host, nullptr, (const char*)saved, act_inner, act_outer, dx,
+    return dcnmix_bwd_exact(m, x, U_host, V_host, W_host, bias_host, gate_host, nullptr, saved, act_inner, act_outer, dx,
                             dU_host, dV_host, dW_host, dbias_host, dgate_host, ws, ws_bytes, st, (hipStream_t)stream2, &hd,
                             layer_events_host);
 }
@@ -1536,7 +1335,7 @@ extern "C" int recnow_dcn_mix_step(const recnow_dcn_mix_step_desc* d, int phases
         const RnTileFwd* pack = nullptr;
         if (front && (phases & RECNOW_STEP_FORWARD) && mix_tile_on(m) && d->U_host && d->V_host && d->W_host && d->bias_host && d->gate_host) {
             memset(&pk, 0, sizeof(pk));
-            pk.D = D; pk.L = L; pk.packs = (float*)((char*)w.saved + mix_tile_pack_off(m));
+            pk.D = D; pk.L = L; pk.packs = MixSaved(m, w.saved).tile_packs();
             for (int l = 0; l < L; ++l) { pk.U[l] = d->U_host[l]; pk.Kg[l] = d->gate_host[l]; pk.V[l] = d->V_host[l]; pk.W[l] = d->W_host[l]; pk.bias[l] = d->bias_host[l]; }
             pack = &pk;
         }
@@ -1577,7 +1376,7 @@ extern "C" int recnow_dcn_mix_step(const recnow_dcn_mix_step_desc* d, int phases
         if ((rc = rn_pair_bpr_onepass(d->scores, d->labels, d->mask, w.order, w.seg_id, w.seg_first, B, flags, d->factor, d->reduce_mean,
                                       d->loss, w.dsu, d->n_pair, w.pair, w.pair_bytes, stream, &loss_part, &n_loss_part)))
             return rc;
-        const float* T2g_top = (const float*)((const char*)w.saved + (size_t)(3 * (L - 1) + 2) * act_block(m));
+        const float* T2g_top = MixSavedC(m, w.saved).T2g(L - 1);
         hipLaunchKernelGGL(k_step_dscore, rn_cdiv(BP, STEP_ROWS), 1024, 0, st, w.dsu, (const unsigned long long*)d->n_pair, d->reduce_mean, 1.0e-10f, B, BP,
                            T2g_top, m.LDT, w.ds, w.T2g_ds, w.ds_part, d->loss, d->stats, w.n_seg, loss_part, n_loss_part);
         RN_LAUNCH_CHECK();
@@ -1589,7 +1388,7 @@ extern "C" int recnow_dcn_mix_step(const recnow_dcn_mix_step_desc* d, int phases
             return RECNOW_EINVAL;
         MixHeadGrad hd;
         hd.w = d->head_w; hd.dscores = w.ds; hd.dw = d->dhead_w; hd.db = d->dhead_b;
-        if ((rc = dcnmix_bwd_exact(m, d->x, d->U_host, d->V_host, d->W_host, d->bias_host, d->gate_host, nullptr, (const char*)w.saved,
+        if ((rc = dcnmix_bwd_exact(m, d->x, d->U_host, d->V_host, d->W_host, d->bias_host, d->gate_host, nullptr, w.saved,
                                    d->act_inner, d->act_outer, d->dx, d->dU_host, d->dV_host, d->dW_host, d->dbias_host, d->dgate_host, w.mix,
                                    w.mix_bytes, st, (hipStream_t)d->stream2, &hd, d->layer_events_host, layer_hi, layer_lo, w.T2g_ds, w.ds_part, rn_cdiv(BP, STEP_ROWS))))
             return rc;

@@ -92,3 +92,22 @@ def test_size_queries_cover_the_row_block_route():
     b3 = 8200
     base3 = L * 3 * b3 * 160 * 4 + (L - 1) * b3 * D * 4
     assert base3 <= lib.recnow_dcn_mix_saved_bytes(b3, D, S, N, L) < base3 + (1 << 20)
+
+
+def test_size_queries_match_the_recorded_layout(golden):
+    """Host-only size queries (no device call) over the grid of tests/golden/make_golden_mix_sizes.py -- 1600 shapes that reach every branch of the
+    `saved` and workspace layouts (csrc/dcnmix_layout.hpp) -- against the values recorded in tests/golden/dcn_mix_sizes.npz, entry by entry.
+    rn_gemm decides routes by the number of workspace bytes it is handed, so a size that drifts changes results, not only allocations."""
+    import itertools
+    import numpy as np
+    from rec_now_amd import _lib
+    lib = _lib.load()
+    g = golden('dcn_mix_sizes')
+    grid = np.array(list(itertools.product([1, 255, 256, 2048, 8177, 8192, 8200, 16384, 32768, 65536], [64, 256, 1024, 1152], [16, 64], [1, 2, 3, 4],
+                                           [1, 2, 3, 4, 9])), dtype=np.int64)
+    assert g['shapes'].shape == (1600, 5) and np.array_equal(g['shapes'], grid)
+    assert g['sizes'].shape == (1600, 3) and g['sizes'].dtype == np.int64
+    queries = (lib.recnow_dcn_mix_saved_bytes, lib.recnow_dcn_mix_workspace_bytes, lambda *s: lib.recnow_dcn_mix_step_workspace_bytes(*s, 0))
+    for shape, want in zip(grid.tolist(), g['sizes'].tolist()):
+        for name, q, w in zip(('saved', 'workspace', 'step workspace'), queries, want):
+            assert q(*shape) == w, '%s bytes of (B, D, S, N, L) = %s: %d, recorded %d' % (name, shape, q(*shape), w)
