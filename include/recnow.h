@@ -681,6 +681,43 @@ int recnow_embed_rows_bwd_direct(const int64_t* key, const int32_t* order, const
                                  float* dtable, int64_t V, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Single-slot fetch, sequence embedding and slot pooling (ABI 11): rec_now/rec_block/embedding_util.py:531-584 (fetch_single_slot),
+ * :327-416 (embedding_single_slot), :419-489 (pool_slots).  slots / ids / weights are (B, C); slot_dtype, id_dtype, row_dtype are
+ * RECNOW_KEY_I32 / RECNOW_KEY_I64; `target` is compared as a 64-bit value.  One wave per batch row, selection by 64-bit ballot; every element
+ * of every output is written by the kernel (outputs may be uninitialised), nothing is allocated, no atomics on float data.
+ *   recnow_slot_max_count: *max_count (DEVICE int32) = max over the rows of the number of entries whose slot is `target` (what ncols=None means).
+ *   recnow_slot_fetch:     row b of each output (B, ncols) = the entries of row b whose slot is `target`, in column order, cut to the first ncols
+ *                          or filled up: out_ids (dtype of ids) with default_id, out_weights with default_weight, mask (bytes) 1 / 0, src (int32)
+ *                          the source column / -1.  Each output (and its input) may be NULL.
+ *   recnow_slot_fetch_bwd: dweights[b][c] = dout[b][j] where src[b][j] == c, 0 elsewhere (dweights (B, C), dout (B, ncols)).
+ *   recnow_slot_embed_fwd: the same selection fused with the gather: out[b][j][:] = table[rows[b][c_j]][:] (out (B, ncols, D)), a zero row for
+ *                          filled-up positions and for row indices outside [0, V).  rows: per entry the row of `table` -- the ids themselves, or
+ *                          the inverse index of recnow_embed_unique -- as int32 or int64.  16-byte copies when D % 4 == 0 and table and out are
+ *                          16-byte aligned, element-wise otherwise (any D >= 1).  out_weights / mask / src as recnow_slot_fetch.  key / key32
+ *                          (optional, (B, ncols)): per output position the table row, or for filled-up positions and rows outside the table
+ *                          key_limit (= V > 0; key32 needs V < 2^31 - 1) or INT64_MIN (key_limit = 0) -- the convention of recnow_slot_targets.
+ *                          The table gradient is recnow_embed_rows_bwd_direct (or recnow_embed_rows_bwd) over the B * ncols positions with
+ *                          these keys, C = 1, dout one row per position: fixed summation order, bit-identical from run to run.
+ *   recnow_slot_pool_fwd:  seg (B, C) from recnow_slot_targets (T targets).  out_ids[b][t] = min of ids over the kept entries of segment t, 0 if
+ *                          there is none or the minimum is the dtype's maximum; out_weights[b][t] = their sum of weights (mean != 0: divided by
+ *                          their number, empty 0); cnt[b][t] (optional) = that number.  drop_duplicate != 0: an entry is not kept when the column
+ *                          immediately before it has the same seg.  Sums add in ascending column order.  ids / weights pairs may be NULL.
+ *   recnow_slot_pool_bwd:  dweights[b][c] = dout[b][seg[b][c]] (/ cnt for mean) for kept entries, 0 otherwise.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_slot_max_count(const void* slots, int slot_dtype, int64_t target, int64_t B, int C, int32_t* max_count, void* stream);
+int recnow_slot_fetch(const void* slots, int slot_dtype, int64_t target, const void* ids, int id_dtype, const float* weights,
+                      int64_t B, int C, int ncols, int64_t default_id, float default_weight, void* out_ids, float* out_weights,
+                      uint8_t* mask, int32_t* src, void* stream);
+int recnow_slot_fetch_bwd(const int32_t* src, const float* dout, int64_t B, int C, int ncols, float* dweights, void* stream);
+int recnow_slot_embed_fwd(const float* table, int D, int64_t V, const void* slots, int slot_dtype, int64_t target, const void* rows,
+                          int row_dtype, const float* weights, int64_t B, int C, int ncols, float default_weight, float* out,
+                          float* out_weights, uint8_t* mask, int32_t* src, int64_t* key, int32_t* key32, int64_t key_limit, void* stream);
+int recnow_slot_pool_fwd(const int32_t* seg, const void* ids, int id_dtype, const float* weights, int64_t B, int C, int T, int mean,
+                         int drop_duplicate, void* out_ids, float* out_weights, float* cnt, void* stream);
+int recnow_slot_pool_bwd(const int32_t* seg, const float* cnt, const float* dout, int64_t B, int C, int T, int mean, int drop_duplicate,
+                         float* dweights, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * MultiHashLayer / FastMultiHashLayer (ABI 10): rec_now/layers/multi_hash_layer.py.  bucket_h(id) = hash_h(text of id) % num_bins (unsigned
  * 64-bit), hash_h = SipHash-2-4 keyed (salts[h], salts[h]) -- keras Hashing(salt=(s, s)) -- or, for h = 0 with first_unsalted, FarmHash
  * Fingerprint64 -- Hashing(salt=None).  The text of an integer id is its "%lld" decimal form.  salts: HOST array of num_hash values >= 0;

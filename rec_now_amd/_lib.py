@@ -105,6 +105,12 @@ SIGNATURES = {
     'recnow_embed_rows_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     'recnow_embed_rows_bwd_direct': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _L, _I, _I, _P, _L, _P, _Z, _P]),
     'recnow_embed_scatter_rows': (_I, [_P, _P, _L, _I, _L, _P, _P, _P]),
+    'recnow_slot_max_count': (_I, [_P, _I, _L, _L, _I, _P, _P]),
+    'recnow_slot_fetch': (_I, [_P, _I, _L, _P, _I, _P, _L, _I, _I, _L, _F, _P, _P, _P, _P, _P]),
+    'recnow_slot_fetch_bwd': (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    'recnow_slot_embed_fwd': (_I, [_P, _I, _L, _P, _I, _L, _P, _I, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P, _P, _L, _P]),
+    'recnow_slot_pool_fwd': (_I, [_P, _P, _I, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'recnow_slot_pool_bwd': (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
     'recnow_hash_ids_host': (_I, [_P, _I, _L, _P, _I, _I, _L, _P]),
     'recnow_hash_bytes_host': (_I, [_P, _P, _L, _P, _I, _I, _L, _P]),
     'recnow_hash_ids': (_I, [_P, _I, _L, _P, _I, _I, _L, _P, _P]),
@@ -148,7 +154,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 10     # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 11    # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

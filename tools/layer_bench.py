@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,slot]"""
 import os
 import sys
 
@@ -503,6 +503,104 @@ def hash():
         torch.cuda.empty_cache()
 
 
+def slot():
+    """fetch_single_slot, embedding_single_slot (forward, forward + backward) and pool_slots (T = 24) at B = 65536, C = 128, ncols = 50, V = 2^20,
+    D = 8 and 32; the target slot occurs 0..40 times per row (mean about 20).  Byte model (algorithmic): the (B, C) inputs read once, the outputs
+    written once, each selected table row gathered once.  Baseline: the reference route restated in torch eager on the same GPU -- boolean_mask,
+    unique, gather, pad by scatter (segment reductions by scatter_reduce / index_add for pool_slots)."""
+    from rec_now_amd.rec_block.embedding_util import EmbeddingTable, embedding_single_slot, fetch_single_slot, pool_slots
+    B, C, ncols, V, T, target = 65536, 128, 50, 1 << 20, 24, 7
+    rng = np.random.default_rng(0)
+    count = rng.integers(0, 41, B)
+    place = np.argsort(rng.random((B, C)), axis=1)                                     # rank of a column: the slot sits in `count` random columns
+    other = rng.integers(100, 100 + 3 * T, (B, C))
+    slots_np = np.where(place < count[:, None], target, other).astype(np.int32)
+    slots = torch.from_numpy(slots_np).to(dev)
+    ids = torch.randint(0, V, (B, C), device=dev)
+    w = torch.randn(B, C, device=dev, requires_grad=True)
+    n_sel = int(np.minimum(count, ncols).sum())
+    pool_targets = list(range(100, 100 + T))
+    col = torch.arange(ncols, device=dev)
+
+    def ragged(mask):
+        rows = mask.nonzero()[:, 0]
+        first = torch.cumsum(mask.sum(1), 0) - mask.sum(1)
+        pos = torch.arange(rows.numel(), device=dev) - first[rows]
+        return rows, pos, pos < ncols
+
+    def eager_fetch():
+        mask = slots == target
+        rows, pos, keep = ragged(mask)
+        oi = torch.zeros(B, ncols, dtype=ids.dtype, device=dev)
+        ow = torch.zeros(B, ncols, device=dev)
+        oi[rows[keep], pos[keep]] = ids[mask][keep]
+        ow = ow.index_put((rows[keep], pos[keep]), w[mask][keep])
+        return oi, ow
+
+    def eager_embed(weight):
+        mask = slots == target
+        rows, pos, keep = ragged(mask)
+        uniq, inv = torch.unique(ids[mask], return_inverse=True)
+        emb = weight[uniq][inv]
+        out = torch.zeros(B, ncols, weight.shape[1], device=dev).index_put((rows[keep], pos[keep]), emb[keep])
+        ow = torch.zeros(B, ncols, device=dev).index_put((rows[keep], pos[keep]), w[mask][keep])
+        om = torch.zeros(B, ncols, dtype=torch.bool, device=dev)
+        om[rows[keep], pos[keep]] = True
+        return out, ow.unsqueeze(-1), om.unsqueeze(-1)
+
+    tg = torch.tensor(pool_targets, device=dev, dtype=torch.int32)
+
+    def eager_pool():
+        hit = slots.unsqueeze(-1) == tg
+        seg = torch.where(hit.any(-1), hit.int().argmax(-1) + torch.arange(B, device=dev).unsqueeze(1) * T, -1)
+        keep = seg >= 0
+        s = seg[keep]
+        pi = torch.full((B * T,), torch.iinfo(ids.dtype).max, dtype=ids.dtype, device=dev).scatter_reduce(0, s, ids[keep], 'amin')
+        pi = torch.where(pi != torch.iinfo(ids.dtype).max, pi, 0)
+        pw = torch.zeros(B * T, device=dev).index_add(0, s, w[keep])
+        return pi.reshape(B, T), pw.reshape(B, T)
+
+    def both(run, ref):
+        f1 = timeit(run)
+        r1 = timeit(ref)
+        r2 = timeit(ref)
+        f2 = timeit(run)
+        return (f1 + f2) / 2, (r1 + r2) / 2
+
+    with torch.no_grad():
+        ms, ref = both(lambda: fetch_single_slot(slots, target, ids, w, ncols=ncols), eager_fetch)
+    nbytes = 4.0 * B * C + 12.0 * n_sel + 12.0 * B * ncols                           # slots; selected ids + weights; ids + weights out
+    print('slot fetch_single_slot     B=%d C=%d ncols=%d : %.3f ms %.2f TB/s (byte model %.0f MB) | torch eager %.3f ms -> %.2fx'
+          % (B, C, ncols, ms, nbytes / ms / 1e9, nbytes / 1e6, ref, ref / ms))
+    with torch.no_grad():
+        ms, ref = both(lambda: pool_slots(slots, pool_targets, ids, w), eager_pool)
+    n_pool = float(np.isin(slots_np, pool_targets).sum())
+    nbytes = 4.0 * B * C + 12.0 * n_pool + 12.0 * B * T
+    print('slot pool_slots T=%d       B=%d C=%d : %.3f ms %.2f TB/s (byte model %.0f MB) | torch eager %.3f ms -> %.2fx'
+          % (T, B, C, ms, nbytes / ms / 1e9, nbytes / 1e6, ref, ref / ms))
+    for D in (8, 32):
+        table = EmbeddingTable(torch.randn(V, D, device=dev) * 0.05)
+        ge, gw = torch.randn(B, ncols, D, device=dev), torch.randn(B, ncols, 1, device=dev)
+        run = lambda: embedding_single_slot(table, slots, target, ids, w, ncols=ncols)             # noqa: E731
+        refrun = lambda: eager_embed(table.weight)                                                 # noqa: E731
+
+        def fb_of(fn):
+            def step():
+                table.weight.grad = None
+                w.grad = None
+                e, wt, _ = fn()
+                torch.autograd.backward([e, wt], [ge, gw])
+            return step
+        with torch.no_grad():
+            ms_f, ref_f = both(run, refrun)
+        ms_b, ref_b = both(fb_of(run), fb_of(refrun))
+        nbytes = 4.0 * B * C + n_sel * (12.0 + 4.0 * D) + B * ncols * (4.0 * D + 5.0)     # slots; selected id, weight, table row; out, weights, mask
+        print('slot embedding_single_slot B=%d C=%d ncols=%d D=%d V=2^20 : fwd %.3f ms %.2f TB/s (byte model %.0f MB), fwd+bwd %.3f ms | torch eager fwd %.3f ms, '
+              'fwd+bwd %.3f ms -> ratio fwd %.2fx fwd+bwd %.2fx' % (B, C, ncols, D, ms_f, nbytes / ms_f / 1e9, nbytes / 1e6, ms_b, ref_f, ref_b, ref_f / ms_f, ref_b / ms_b))
+        del table, ge, gw
+        torch.cuda.empty_cache()
+
+
 if __name__ == '__main__':
     which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'gnn', 'ipnn', 'senet', 'attn', 'din', 'focal', 'embed']
     if 'fm' in which:
@@ -525,6 +623,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('slot', slot)):
         if name in which:
             fn()
