@@ -809,6 +809,38 @@ int recnow_sparse_gnn_bwd(const float* x, const float* const* x_fields, int in_l
                           const float* const* dy_all, int dy_aligned, float* dx, float* dw, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Tensor plumbing (ABI 12): rec_now/layers/pooling_layer.py (PoolingLayer), rec_now/layers/fix_length_layer.py (pad_or_truncate,
+ * FixLengthLayer), rec_now/rec_block/embedding_wise_weight.py (gather_embedding_element_wise_weight).  csrc/tensor_util.hip.
+ * Every contiguous tensor is given as (O, R, I): outer extent, the axis worked on, inner extent.  fp32 unless said otherwise.
+ * An empty extent (O, I, P or B equal to 0) returns RECNOW_OK without a launch.  No float atomics: bit-identical from run to run.
+ *   recnow_reduce_axis_fwd: out (O, I) = sum / mean / max / min of x (O, R, I) over R; R >= 1.  ws of
+ *     recnow_reduce_axis_workspace_bytes (0 except for one long row, O == 1 and I == 1: the partials of the two-stage reduction).
+ *   recnow_reduce_axis_bwd: dx (O, R, I) from g (O, I).  sum: g; mean: g * (1 / R); max / min: TensorFlow's rule, g / count at every
+ *     position equal to the result y (O, I), count = the number of such positions of the run (x and y are read only for max / min).
+ *   recnow_pad_axis: out (O, L_out, I) = x cut to, or filled up with the element `fill_bits` to, L_out along the middle axis; elements of
+ *     elt_bytes = 4 or 8 bytes, copied as bits (fill_bits: the element's bit pattern in the low bytes).  Its own backward: the gradient
+ *     of (O, L_out, I) padded or cut back to L_in with fill 0.
+ *   recnow_elem_weight_fwd: out[b][p] = w[b][pos[p]], times x[b][p] when x is given; w (B, E), pos (P) int32 DEVICE entries in [0, E)
+ *     (the caller checks them; the kernel does not), x and out (B, P).  P <= 2^24.
+ *   recnow_elem_weight_bwd: dw[b][e] = sum over {p : pos[p] == e}, in ascending p, of g[b][p] (* x[b][p] when x is given) through the
+ *     inverse of pos as a CSR table: off (E + 1) and idx (P) int32 DEVICE arrays, idx[off[e] .. off[e + 1]) = the positions of e.
+ *     dx[b][p] = g[b][p] * w[b][pos[p]] in the same launch.  dw, dx may each be NULL (w, pos are read only for dx).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define RECNOW_REDUCE_SUM 0
+#define RECNOW_REDUCE_MEAN 1
+#define RECNOW_REDUCE_MAX 2
+#define RECNOW_REDUCE_MIN 3
+size_t recnow_reduce_axis_workspace_bytes(int64_t O, int64_t R, int64_t I);
+int recnow_reduce_axis_fwd(const float* x, int64_t O, int64_t R, int64_t I, int op, float* out, void* ws, size_t ws_bytes, void* stream);
+int recnow_reduce_axis_bwd(const float* x, const float* y, const float* g, int64_t O, int64_t R, int64_t I, int op, float* dx,
+                           void* stream);
+int recnow_pad_axis(const void* x, int elt_bytes, int64_t O, int64_t L_in, int64_t L_out, int64_t I, int64_t fill_bits, void* out,
+                    void* stream);
+int recnow_elem_weight_fwd(const float* w, const int32_t* pos, const float* x, int64_t B, int E, int P, float* out, void* stream);
+int recnow_elem_weight_bwd(const float* g, const float* x, const float* w, const int32_t* pos, const int32_t* off, const int32_t* idx,
+                           int64_t B, int E, int P, float* dw, float* dx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

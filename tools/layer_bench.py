@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,slot]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,slot,tensor_util]"""
 import os
 import sys
 
@@ -601,6 +601,69 @@ def slot():
         torch.cuda.empty_cache()
 
 
+def tensor_util():
+    """PoolingLayer, pad_or_truncate and the element-wise embedding weights at B = 65536: forward and forward + backward, eager and replayed from a
+    graph, each beside the same op written with torch's own operators (sum / mean / amax / amin, F.pad / slicing, w[:, pos]) timed in the same run.
+    Byte model (algorithmic): every input read once, every output written once; the backward adds the output gradient read and the input gradient(s)
+    written (max / min read x and y again).  Set the TB/s beside the plain-stream rate of tools/micro/stream_bench.py on the same box."""
+    import torch.nn.functional as F
+    from rec_now_amd.layers import PoolingLayer
+    from rec_now_amd.layers.fix_length_layer import pad_or_truncate
+    from rec_now_amd.rec_block.embedding_wise_weight import apply_embedding_element_wise_weight, gather_embedding_element_wise_weight
+    B = 65536
+
+    def row(tag, run, ref, args, grads, bytes_f, bytes_b):
+        """run / ref: functions of the differentiable inputs `args`; grads: they carry a gradient (False: forward only)."""
+        def fwd(fn):
+            def step():
+                with torch.no_grad():
+                    return fn(*args)
+            return step
+
+        def fb(fn):
+            def step():
+                for a in args:
+                    a.grad = None
+                y = fn(*args)
+                y.backward(g)
+            return step
+        g = torch.randn_like(run(*args)) if grads else None
+        cols = []
+        for make, nbytes in ((fwd, bytes_f),) + (((fb, bytes_f + bytes_b),) if grads else ()):
+            e1, r1 = timeit(make(run)), timeit(make(ref))
+            r2, e2 = timeit(make(ref)), timeit(make(run))
+            ge, gr = timeit_graph(make(run)), timeit_graph(make(ref))
+            cols.append((nbytes, (e1 + e2) / 2, (r1 + r2) / 2, ge, gr))
+        for name, (nbytes, e, r, ge, gr) in zip(('fwd    ', 'fwd+bwd'), cols):
+            gtxt = 'graph %.3f ms %.2f TB/s | torch graph %.3f ms -> %.2fx' % (ge, nbytes / ge / 1e9, gr, gr / ge) if ge and gr else 'graph n/a'
+            print('tensor_util %-34s %s : eager %.3f ms | torch eager %.3f ms -> %.2fx | %s (byte model %.0f MB)'
+                  % (tag, name, e, r, r / e, gtxt, nbytes / 1e6))
+
+    x = torch.randn(B, 50, 32, device=dev, requires_grad=True)
+    nin, nout = 4.0 * x.numel(), 4.0 * B * 32
+    torch_ops = {'sum': lambda t: t.sum(1), 'mean': lambda t: t.mean(1), 'max': lambda t: t.amax(1), 'min': lambda t: t.amin(1)}
+    for combiner in ('sum', 'mean', 'max', 'min'):
+        layer = PoolingLayer(axis=1, combiner=combiner)
+        extra = nin + nout if combiner in ('max', 'min') else 0.0
+        row('PoolingLayer %s (B,50,32) axis 1' % combiner, layer, torch_ops[combiner], (x,), True, nin + nout, nout + nin + extra)
+    del x
+    x = torch.randn(B, 37, 32, device=dev, requires_grad=True)
+    row('pad_or_truncate (B,37,32) -> 50', lambda t: pad_or_truncate(t, 50, axis=1), lambda t: F.pad(t, (0, 0, 0, 13)), (x,), True,
+        4.0 * B * 32 * (37 + 50), 4.0 * B * 32 * (37 + 50))
+    ids = torch.randint(0, 1 << 40, (B, 80), device=dev)
+    row('pad_or_truncate (B,80) int64 -> 50', lambda t: pad_or_truncate(t, 50), lambda t: t[:, :50].contiguous(), (ids,), False, 8.0 * B * 100, 0.0)
+    del x, ids
+    E, P = 64, 1024
+    pos = np.repeat(np.arange(E), P // E).tolist()
+    pos_t = torch.tensor(pos, device=dev)
+    w = torch.randn(B, E, device=dev, requires_grad=True)
+    xin = torch.randn(B, P, device=dev, requires_grad=True)
+    row('gather element-wise weight E=64 P=1024', lambda t: gather_embedding_element_wise_weight(t, pos), lambda t: t[:, pos_t], (w,), True,
+        4.0 * B * (E + P), 4.0 * B * (E + P))
+    row('apply element-wise weight E=64 P=1024', lambda a, t: apply_embedding_element_wise_weight(a, t, pos), lambda a, t: a * t[:, pos_t], (xin, w), True,
+        4.0 * B * (E + 2 * P), 4.0 * B * (3 * P + 2 * E + P))
+
+
 if __name__ == '__main__':
     which = sys.argv[2].split(',') if len(sys.argv) > 2 else ['fm', 'dcn', 'pair', 'list', 'cin', 'ple', 'star', 'stacked', 'gnn', 'ipnn', 'senet', 'attn', 'din', 'focal', 'embed']
     if 'fm' in which:
@@ -623,6 +686,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('slot', slot)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('slot', slot), ('tensor_util', tensor_util)):
         if name in which:
             fn()
