@@ -841,6 +841,30 @@ int recnow_elem_weight_bwd(const float* g, const float* x, const float* w, const
                            int64_t B, int E, int P, float* dw, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * CANLayer, the co-action network (ABI 13): rec_now/layers/can_layer.py:228-275.  csrc/can.hip.
+ * Every sample b carries its own small MLP in params (B, P): layer after layer, a kernel (D_{k-1}, D_k) row-major, then (use_bias) a
+ * bias (D_k); P = sum_k D_{k-1} D_k [+ D_k].  dims: HOST array of the n_layers output widths D_1 .. D_n.  x (B, L, D0):
+ *   h_0 = x[b][l];  o = h_{k-1} . W_k[b] (+ bias_k[b]);  a = act(o) on every layer but the last (on the last too with last_act);
+ *   h_k = a (+ h_{k-1} with res_net: then every width must equal D0, else RECNOW_EINVAL);
+ *   out[b][l] = h_n * any(x[b][l][:] != 0) with mask (else h_n).
+ * combiner -1: y (B, L, D_n) = out.  combiner RECNOW_REDUCE_*: y (B, D_n) = sum / mean / max / min of out over l (masked positions
+ * count as zeros); L >= 1 then (else RECNOW_EINVAL).  One launch per direction, one workgroup per sample, the sample's parameters in
+ * LDS; no (B, L, D) intermediate, no workspace, no float atomics: the same input gives the same bits on every run.
+ * recnow_can_bwd recomputes the layer chain (it reads no saved activation) from x, params, g (the gradient of y) and, for max / min
+ * only, y: every position whose output equals y shares g / count.  dx (B, L, D0) and dparams (B, P) may each be NULL; every element
+ * of the ones given is written once.
+ * recnow_can_supported: host-only (no device call), 1 exactly for the shapes the kernels take: D0 and every width in 1..64,
+ * 1..8 layers, and P floats plus the backward's staging within the 64 KB of LDS one workgroup asks for.  Other shapes:
+ * RECNOW_EUNSUPPORTED from _fwd / _bwd.  B == 0 returns RECNOW_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_can_supported(int D0, const int* dims, int n_layers, int use_bias);
+int recnow_can_fwd(const float* x, const float* params, float* y, int64_t B, int64_t L, int D0, const int* dims, int n_layers, int act,
+                   int use_bias, int res_net, int last_act, int mask, int combiner, void* stream);
+int recnow_can_bwd(const float* x, const float* params, const float* g, const float* y, int64_t B, int64_t L, int D0, const int* dims,
+                   int n_layers, int act, int use_bias, int res_net, int last_act, int mask, int combiner, float* dx, float* dparams,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,slot,tensor_util]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -405,6 +405,62 @@ def star(mode):
         torch.cuda.empty_cache()
 
 
+def can_ref_eager(x, params, dims, use_bias=True):
+    """The reference algorithm (can_layer.py:243-275) in torch eager with its defaults (tanh between the layers, mask, sum): per layer one
+    batched matmul of the (B, L, din) activations against the sample's (B, din, dout) kernel -- the reference's (B, L, 1, din) x (B, 1, din, dout)
+    broadcast without an L-fold expanded kernel -- so autograd keeps a (B, L, D_k) activation per layer."""
+    B, L, din = x.shape
+    h, at = x, 0
+    for k, dout in enumerate(dims):
+        h = torch.bmm(h, params[:, at:at + din * dout].view(B, din, dout))
+        at += din * dout
+        if use_bias:
+            h = h + params[:, at:at + dout].unsqueeze(1)
+            at += dout
+        if k + 1 < len(dims):
+            h = torch.tanh(h)
+        din = dout
+    return (h * (x != 0).any(-1, keepdim=True).to(h.dtype)).sum(1)
+
+
+def can():
+    """CANLayer at B = 65 536, L = 50 for D0 16 with [16, 16] and D0 32 with [32, 32, 32] (tanh, bias, mask, sum): forward and forward + backward,
+    eager and replayed from a HIP graph, as TB/s of algorithmic bytes (forward: inputs + params + y; backward: those plus g, dx, dparams), beside the
+    reference algorithm in torch eager timed in the same run."""
+    from rec_now_amd.layers.can_layer import CANLayer
+    B, L = 65536, 50
+    for D0, dims in ((16, [16, 16]), (32, [32, 32, 32])):
+        P, Dn = CANLayer.get_dnn_param_size(D0, dims), dims[-1]
+        x = torch.randn(B, L, D0, device=dev)
+        x[torch.rand(B, L, device=dev) < 0.2] = 0.0             # padding positions
+        x.requires_grad_(True)
+        p = (torch.randn(B, P, device=dev) / D0 ** 0.5).requires_grad_(True)
+        gy = torch.randn(B, Dn, device=dev)
+        layer = CANLayer(dnn_dims=dims)
+        run, ref = (lambda: layer(x, p)), (lambda: can_ref_eager(x, p, dims))
+        err = (run() - ref()).abs().max().item()
+
+        def fb_of(fn):
+            def step():
+                x.grad = None
+                p.grad = None
+                fn().backward(gy)
+            return step
+
+        fwd_bytes = 4.0 * (B * L * D0 + B * P + B * Dn)
+        fb_bytes = 2 * fwd_bytes + 4.0 * (B * Dn + B * L * D0 + B * P)
+        ms_f, ms_fb = timeit(run), timeit(fb_of(run))
+        rf, rfb = timeit(ref), timeit(fb_of(ref))
+        gf, gfb = timeit_graph(run), timeit_graph(fb_of(run))
+        gtxt = 'graph fwd %.3f ms %.2f TB/s, fwd+bwd %.3f ms %.2f TB/s' % (gf, fwd_bytes / gf / 1e9, gfb, fb_bytes / gfb / 1e9) if gf and gfb else 'graph n/a'
+        print('CANLayer B=%d L=%d D0=%d dims=%s P=%d : fwd %.3f ms %.2f TB/s, fwd+bwd %.3f ms %.2f TB/s (algorithmic: fwd %.0f MB, fwd+bwd %.0f MB) | %s | '
+              'reference in torch eager: fwd %.3f ms, fwd+bwd %.3f ms -> speedup fwd %.1fx, fwd+bwd %.1fx | max |y - eager| %.2g'
+              % (B, L, D0, dims, P, ms_f, fwd_bytes / ms_f / 1e9, ms_fb, fb_bytes / ms_fb / 1e9, fwd_bytes / 1e6, fb_bytes / 1e6, gtxt, rf, rfb,
+                 rf / ms_f, rfb / ms_fb, err))
+        del x, p, layer
+        torch.cuda.empty_cache()
+
+
 def gnn_ref_eager(x, indices, ws, L, F):
     """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
     from the weight vector, matmul, add, tanh; transpose back and flatten."""
@@ -686,6 +742,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('slot', slot), ('tensor_util', tensor_util)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('slot', slot), ('tensor_util', tensor_util), ('can', can)):
         if name in which:
             fn()
