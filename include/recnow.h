@@ -757,6 +757,54 @@ int recnow_hash_embed_bwd_weights(const int64_t* keys, const float* const* table
                                   const float* dout, int64_t B, int64_t L, float* dweights, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * CartesianProductLayer (ABI 14): rec_now/layers/cartesian_product_layer.py feeding MultiHashLayer / FastMultiHashLayer.  Element (b, j) of the
+ * (B, P) cross, P = len[0] * ... * len[n_inputs - 1], j row-major with the LAST input fastest, is the text
+ *     str(ids[0][b][j0]) SEP str(ids[1][b][j1]) SEP ...          (decimal "%lld" texts; input k is (B, len[k]), or (1, len[k]) with batch1[k])
+ * which is never stored: the kernels compose it per element and hash it like the text of a plain id.  Invalid patterns: input i may carry up to 8
+ * literal alternatives (n_alt[i] = 0: no pattern; a literal may be empty).  The element is replaced by the default string when the regular
+ * expression ^.*SEP ... (lit_a|lit_b|...) ... SEP.*$ -- the group in position i -- matches the JOINED text, which is decided exactly (csrc/hash64.hpp,
+ * rn_cross_match); its buckets are then default_buckets[h], computed by the caller (recnow_hash_bytes_host) and required to lie in [0, num_bins).
+ * Words are little-endian: byte p of a text is bits 8 (p % 8) of word p / 8, zero padded.
+ * Limits (RECNOW_EINVAL beyond them): 1..4 inputs, separator <= 4 bytes, worst-case text (11 bytes per int32 input, 20 per int64 input, plus the
+ * separators) <= 96 bytes, default string <= 96 bytes, literals <= 24 bytes.  With first_unsalted (Fingerprint64, 0..32 bytes) a worst-case text or
+ * a default string longer than 32 bytes is RECNOW_EUNSUPPORTED; B * P * num_hash >= 2^31 as well.
+ *   recnow_cross_text / _host: text (B, P, W) uint8 zero padded, W a multiple of 8 and >= the worst-case text and the default string; lens (B, P) int32.
+ *   recnow_cross_hash_ids / _host: (B * P, num_hash) int64 bucket numbers.
+ *   recnow_cross_hash_embed_fwd: recnow_hash_embed_fwd with L = P and the ids taken from the descriptor; keys / keys32 as there, so the backward
+ *     entry points serve unchanged.
+ * The *_host twins run the same code on the host (host pointers in the descriptor, no GPU call).  No allocation, no host synchronisation.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define RECNOW_CROSS_MAX_INPUTS 4
+#define RECNOW_CROSS_MAX_SEP 4
+#define RECNOW_CROSS_MAX_TEXT 96
+#define RECNOW_CROSS_MAX_ALTS 8
+#define RECNOW_CROSS_MAX_LIT 24
+typedef struct recnow_cross_desc {
+    const void* ids[RECNOW_CROSS_MAX_INPUTS];        /* (B, len[k]) or (1, len[k]) contiguous ids */
+    int32_t dtype[RECNOW_CROSS_MAX_INPUTS];          /* RECNOW_KEY_I32 / RECNOW_KEY_I64 */
+    int32_t len[RECNOW_CROSS_MAX_INPUTS];
+    int32_t batch1[RECNOW_CROSS_MAX_INPUTS];         /* 1: one row shared by the whole batch */
+    int32_t n_inputs;
+    int32_t sep_len;
+    uint32_t sep_word;                               /* the separator's bytes */
+    int32_t default_len;
+    int32_t n_alt[RECNOW_CROSS_MAX_INPUTS];
+    int32_t lit_len[RECNOW_CROSS_MAX_INPUTS][RECNOW_CROSS_MAX_ALTS];
+    uint64_t lit_words[RECNOW_CROSS_MAX_INPUTS][RECNOW_CROSS_MAX_ALTS][RECNOW_CROSS_MAX_LIT / 8];
+    uint64_t default_words[RECNOW_CROSS_MAX_TEXT / 8]; /* the default string's bytes (recnow_cross_text) */
+    int64_t default_buckets[16];                     /* its bucket under each hash function (the hash entry points) */
+} recnow_cross_desc;
+int recnow_cross_text_host(recnow_cross_desc desc, int64_t B, int W, unsigned char* text, int32_t* lens);
+int recnow_cross_hash_ids_host(recnow_cross_desc desc, int64_t B, const int64_t* salts, int num_hash, int first_unsalted, int64_t num_bins,
+                               int64_t* out);
+int recnow_cross_text(recnow_cross_desc desc, int64_t B, int W, unsigned char* text, int32_t* lens, void* stream);
+int recnow_cross_hash_ids(recnow_cross_desc desc, int64_t B, const int64_t* salts_host, int num_hash, int first_unsalted, int64_t num_bins,
+                          int64_t* out, void* stream);
+int recnow_cross_hash_embed_fwd(recnow_cross_desc desc, int64_t B, const int64_t* salts_host, int num_hash, int first_unsalted,
+                                int64_t num_bins, const float* const* tables_host, int D, const float* weights, int mode, float* out,
+                                int64_t* keys, int32_t* keys32, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * StarDenseLayer / StackedDenseLayer (ABI 7): rec_now/layers/star_dense_layer.py:118-163, stacked_dense_layer.py:116-155.
  * A Dense layer personalised per row by K <= 4 parameter rows.  params_host / dparams_host: HOST arrays of K DEVICE pointers to
  * contiguous (B, R) fp32 tensors, R = D*U + U: the first D*U entries of a row are a kernel [d][u], the last U a bias.

@@ -14,6 +14,17 @@ LIB_PATH = os.environ.get('RECNOW_LIB_PATH') or os.path.join(_HERE, 'librecnow_h
 _c = ctypes
 _P, _I, _L, _F, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t
 
+
+class CrossDesc(ctypes.Structure):
+    """recnow_cross_desc of include/recnow.h (passed by value)."""
+    _fields_ = [
+        ('ids', _P * 4), ('dtype', _c.c_int32 * 4), ('len', _c.c_int32 * 4), ('batch1', _c.c_int32 * 4),
+        ('n_inputs', _c.c_int32), ('sep_len', _c.c_int32), ('sep_word', _c.c_uint32), ('default_len', _c.c_int32),
+        ('n_alt', _c.c_int32 * 4), ('lit_len', (_c.c_int32 * 8) * 4), ('lit_words', ((_c.c_uint64 * 3) * 8) * 4),
+        ('default_words', _c.c_uint64 * 12), ('default_buckets', _c.c_int64 * 16),
+    ]
+
+
 # name -> (restype, argtypes); kept in the order of include/recnow.h
 SIGNATURES = {
     'recnow_abi_version': (_I, []),
@@ -116,6 +127,11 @@ SIGNATURES = {
     'recnow_hash_ids': (_I, [_P, _I, _L, _P, _I, _I, _L, _P, _P]),
     'recnow_hash_embed_fwd': (_I, [_P, _I, _L, _L, _P, _I, _I, _L, _P, _I, _P, _I, _P, _P, _P, _P]),
     'recnow_hash_embed_bwd_weights': (_I, [_P, _P, _I, _L, _I, _P, _L, _L, _P, _P]),
+    'recnow_cross_text_host': (_I, [CrossDesc, _L, _I, _P, _P]),
+    'recnow_cross_hash_ids_host': (_I, [CrossDesc, _L, _P, _I, _I, _L, _P]),
+    'recnow_cross_text': (_I, [CrossDesc, _L, _I, _P, _P, _P]),
+    'recnow_cross_hash_ids': (_I, [CrossDesc, _L, _P, _I, _I, _L, _P, _P]),
+    'recnow_cross_hash_embed_fwd': (_I, [CrossDesc, _L, _P, _I, _I, _L, _P, _I, _P, _I, _P, _P, _P, _P]),
     'recnow_star_dense_workspace_bytes': (_Z, [_L, _I, _I]),
     'recnow_star_dense_fwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _I, _I, _I, _P, _P]),
     'recnow_star_dense_bwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
@@ -163,7 +179,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 13    # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 14    # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

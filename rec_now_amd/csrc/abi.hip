@@ -9,5 +9,6 @@
 // _workspace_bytes (attention_by_dnn); 9: recnow_sparse_gnn_fwd / _bwd / _workspace_bytes (SparseGNNLayer); 10: recnow_hash_ids / _ids_host / _bytes_host, recnow_hash_embed_fwd /
 // _bwd_weights, recnow_embed_rows_bwd_direct (MultiHashLayer, FastMultiHashLayer); 11: recnow_slot_max_count, recnow_slot_fetch / _fetch_bwd, recnow_slot_embed_fwd,
 // recnow_slot_pool_fwd / _pool_bwd (fetch_single_slot, embedding_single_slot, pool_slots); 12: recnow_reduce_axis_fwd / _bwd / _workspace_bytes, recnow_pad_axis,
-// recnow_elem_weight_fwd / _bwd (PoolingLayer, FixLengthLayer, gather_embedding_element_wise_weight); 13: recnow_can_fwd / _bwd / _supported (CANLayer).
-extern "C" int recnow_abi_version(void) { return 13; }
+// recnow_elem_weight_fwd / _bwd (PoolingLayer, FixLengthLayer, gather_embedding_element_wise_weight); 13: recnow_can_fwd / _bwd / _supported (CANLayer);
+// 14: recnow_cross_desc, recnow_cross_text / _hash_ids (+ _host twins), recnow_cross_hash_embed_fwd (CartesianProductLayer).
+extern "C" int recnow_abi_version(void) { return 14; }

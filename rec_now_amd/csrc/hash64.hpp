@@ -182,3 +182,139 @@ RN_HD int64_t rn_hash_bucket_text(const RnText& t, int unsalted, uint64_t salt, 
     const uint64_t h = unsalted ? rn_fingerprint64_text(t) : rn_siphash24_text(salt, salt, t);
     return (int64_t)(h % num_bins);
 }
+
+// ---- crossed ids (CartesianProductLayer feeding the hash layers) ------------------------------------------------------------------------
+// The text of one element of a cross, "a-b-c", is composed out of rn_int_text pieces and the separator into zero-padded little-endian words
+// that the caller owns: RN_CROSS_WORDS of them, the 12 of the longest text plus 3, since an append stores the four words from the one it
+// starts in.  The word a piece lands in is a run-time number, so on the device the storage is the lane's own slice of LDS (a per-lane
+// register array indexed that way would live in scratch memory); on the host it is a local array.
+#include "../../include/recnow.h"
+#define RN_CROSS_WORDS (RECNOW_CROSS_MAX_TEXT / 8 + 3)
+
+// the 8 bytes at byte offset `off` (0 <= off <= 96)
+RN_HD uint64_t rn_words_fetch64(const uint64_t* w, int off) {
+    const int i = off >> 3, r = (off & 7) * 8;
+    const uint64_t lo = w[i];
+    return r == 0 ? lo : (lo >> r) | (w[i + 1] << (64 - r));
+}
+// appends the `plen` <= 24 bytes held in x0, x1, x2 (zero padded) at byte `len`; words past the piece are left zero
+RN_HD void rn_cross_append(uint64_t* w, int& len, uint64_t x0, uint64_t x1, uint64_t x2, int plen) {
+    const int i = len >> 3, r = (len & 7) * 8;
+    w[i] |= x0 << r;
+    w[i + 1] = r ? (x0 >> (64 - r)) | (x1 << r) : x1;
+    w[i + 2] = r ? (x1 >> (64 - r)) | (x2 << r) : x2;
+    w[i + 3] = r ? x2 >> (64 - r) : 0ull;
+    len += plen;
+}
+RN_HD int64_t rn_cross_load(const recnow_cross_desc& d, int k, int64_t b, uint32_t j) {
+    const int64_t at = (d.batch1[k] ? 0 : b * (int64_t)d.len[k]) + (int64_t)j;
+    return d.dtype[k] == RECNOW_KEY_I32 ? (int64_t)((const int32_t*)d.ids[k])[at] : ((const int64_t*)d.ids[k])[at];
+}
+// the text of element (b, j), j < P row-major with the last input fastest; returns its length (<= the worst case the entry points check)
+RN_HD int rn_cross_compose(const recnow_cross_desc& d, int64_t b, uint32_t j, uint64_t* w) {
+    uint32_t jk[RECNOW_CROSS_MAX_INPUTS];
+#pragma unroll
+    for (int k = RECNOW_CROSS_MAX_INPUTS - 1; k >= 0; --k) {
+        jk[k] = 0u;
+        if (k < d.n_inputs) {
+            const uint32_t L = (uint32_t)d.len[k], q = j / L;
+            jk[k] = j - q * L;
+            j = q;
+        }
+    }
+    for (int k = 0; k < RN_CROSS_WORDS; ++k) w[k] = 0ull;
+    int len = 0;
+#pragma unroll
+    for (int k = 0; k < RECNOW_CROSS_MAX_INPUTS; ++k)
+        if (k < d.n_inputs) {
+            if (k > 0 && d.sep_len > 0) rn_cross_append(w, len, (uint64_t)d.sep_word, 0ull, 0ull, d.sep_len);
+            const RnText t = rn_int_text(rn_cross_load(d, k, b, jk[k]));
+            rn_cross_append(w, len, t.w0, t.w1, t.w2, t.len);
+        }
+    return len;
+}
+
+// Does the reference's regular expression of some input's pattern match the joined text?  For input i with the literals s_a the expression is
+// ^.*SEP ... (s_a|s_b|..) ... SEP.*$ with the group in position i of n, so the text T matches iff for some literal s and position p
+//   T[p : p + |s|] == s,   T[: p] in (.*SEP){i},   T[p + |s| :] in (SEP.*){n - 1 - i}.
+// T[: p] is in (.*SEP){i}, i > 0, iff it ends with SEP and what is before that holds i - 1 non-overlapping SEPs, that is iff it reaches at
+// least to e_{i-1}, the end of the (i - 1)-th SEP found greedily from the left (the shortest prefix that holds so many); symmetrically with
+// b_k from the right.  This is the expression's own match, not a comparison per field: "5--1" matches ^.*-(1)$.
+RN_HD bool rn_cross_sep_at(const uint64_t* w, int len, int p, uint32_t sep_word, int sl) {
+    if (p < 0 || p + sl > len) return false;
+    if (sl == 0) return true;
+    const uint32_t mask = sl >= 4 ? 0xffffffffu : (1u << (8 * sl)) - 1u;
+    return ((uint32_t)rn_words_fetch64(w, p) & mask) == sep_word;
+}
+RN_HD bool rn_cross_lit_at(const uint64_t* w, int p, const uint64_t* lit, int n) {
+    bool eq = true;
+#pragma unroll
+    for (int k = 0; k < RECNOW_CROSS_MAX_LIT / 8; ++k) {
+        const int nb = n - 8 * k;
+        if (nb > 0) {
+            const uint64_t mask = nb >= 8 ? ~0ull : (1ull << (8 * nb)) - 1ull;
+            eq = eq && (rn_words_fetch64(w, p + 8 * k) & mask) == lit[k];
+        }
+    }
+    return eq;
+}
+RN_HD bool rn_cross_match(const recnow_cross_desc& d, const uint64_t* w, int len) {
+    const int n = d.n_inputs, sl = d.sep_len, never = 1 << 20;
+    const uint32_t sep = d.sep_word;
+    // e1, e2: ends of the first and second SEP from the left; b1, b2: starts of the last and the last but one from the right
+    int e1 = sl ? never : 0, e2 = e1, b1 = sl ? -never : len, b2 = b1;
+    if (sl) {
+        int k = 0;
+        for (int p = 0; p + sl <= len && k < 2;) {
+            if (rn_cross_sep_at(w, len, p, sep, sl)) {
+                p += sl;
+                if (k == 0) e1 = p; else e2 = p;
+                ++k;
+            } else ++p;
+        }
+        k = 0;
+        for (int p = len - sl; p >= 0 && k < 2;) {
+            if (rn_cross_sep_at(w, len, p, sep, sl)) {
+                if (k == 0) b1 = p; else b2 = p;
+                p -= sl;
+                ++k;
+            } else --p;
+        }
+    }
+    bool hit = false;
+#pragma unroll
+    for (int i = 0; i < RECNOW_CROSS_MAX_INPUTS; ++i) {
+        if (i >= n || d.n_alt[i] <= 0) continue;
+        const int after = n - 1 - i;                                                    // fields behind the group
+        const int emin = i <= 1 ? 0 : i == 2 ? e1 : e2;                                 // T[: p - sl] must reach e_{i-1}
+        const int bmax = after <= 1 ? len : after == 2 ? b1 : b2;                       // T[q + sl :] must start by b_{after-1}
+        for (int a = 0; a < d.n_alt[i]; ++a) {
+            const int L = d.lit_len[i][a];
+            const uint64_t* lit = d.lit_words[i][a];
+            const int p_lo = i == 0 ? 0 : emin + sl, p_hi = i == 0 ? 0 : len - L;
+            for (int p = p_lo; p <= p_hi && p + L <= len; ++p) {
+                if (i > 0 && !rn_cross_sep_at(w, len, p - sl, sep, sl)) continue;
+                const int q = p + L;
+                if (after == 0 ? q != len : !(rn_cross_sep_at(w, len, q, sep, sl) && q + sl <= bmax)) continue;
+                if (rn_cross_lit_at(w, p, lit, L)) hit = true;
+            }
+        }
+    }
+    return hit;
+}
+RN_HD bool rn_cross_has_patterns(const recnow_cross_desc& d) {
+    return (d.n_alt[0] | d.n_alt[1] | d.n_alt[2] | d.n_alt[3]) != 0;
+}
+// bucket of a composed text under hash function h (the caller has checked len <= 32 where `unsalted` can be set)
+RN_HD int64_t rn_cross_bucket(const uint64_t* w, int len, int unsalted, uint64_t salt, uint64_t num_bins) {
+    uint64_t v;
+    if (unsalted) {
+        RnText t;
+        t.w0 = w[0]; t.w1 = w[1]; t.w2 = w[2]; t.w3 = w[3];
+        t.len = len;
+        v = rn_fingerprint64_text(t);
+    } else {
+        v = rn_siphash24_words(salt, salt, w, (uint64_t)len);
+    }
+    return (int64_t)(v % num_bins);
+}

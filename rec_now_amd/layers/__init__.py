@@ -1,5 +1,6 @@
 """rec_now_amd.layers -- MI355X-native counterparts of rec_now/layers (same module and symbol names)."""
 from .can_layer import CANLayer  # noqa: F401
+from .cartesian_product_layer import CartesianProductLayer, CrossedIds  # noqa: F401
 from .fix_length_layer import FixLengthLayer  # noqa: F401
 from .multi_hash_layer import FastMultiHashLayer, MultiHashLayer  # noqa: F401
 from .pooling_layer import PoolingLayer  # noqa: F401

@@ -5,7 +5,8 @@ and the rows are combined (the multi-hash trick: a small table stands in for a h
 integer ids go through `tf.strings.as_string` first -- and looks the buckets up afterwards.  Here integer ids stay on the GPU: one HIP kernel
 (csrc/hash_embed.hip) formats, hashes, gathers and reduces in one pass, so no (B, L, num_hash) index tensor and no (B, L, num_hash, D) or
 (B, L, D) temporary exists; `get_pooling` is one launch down to (B, D).  The table gradient goes through the sorted-segment reduction of
-csrc/embed.hip (bit-identical from run to run).
+csrc/embed.hip (bit-identical from run to run).  A `CrossedIds` (CartesianProductLayer on integer tensors) is taken wherever ids are: the kernels of
+csrc/cross_hash.hip compose the "a-b" text of every crossed element on chip and hash it in the same launch.
 
 Hash functions (csrc/hash64.hpp, one source for host and device): keras `Hashing(num_bins, salt=(s, s))` is SipHash-2-4 keyed (s, s), `% num_bins`;
 `Hashing(num_bins, salt=None)` is FarmHash Fingerprint64, `% num_bins` (unsigned 64-bit).  An integer is hashed as its decimal text.  Buckets of
@@ -21,8 +22,10 @@ import torch
 from .. import _lib
 from ..rec_block._segments import build_segments
 from ._keras import Layer, get_initializer
+from .cartesian_product_layer import CrossedIds
 
 _KEY_I32, _KEY_I64, _BUCKETS = 2, 3, 4                           # RECNOW_KEY_I32 / _I64, RECNOW_HASH_BUCKETS
+_CROSS = 5                                                       # host side only: the ids are a CrossedIds (csrc/cross_hash.hip)
 MODE_SUM, MODE_MEAN, MODE_ROWS, MODE_POOLED = 0, 1, 2, 3         # RECNOW_HASH_*
 MAX_NUM_HASH = 16                                                # RN_HASH_MAX_NUM_HASH of csrc/hash64.hpp
 MAX_UNSALTED_BYTES = 32                                          # RN_HASH_MAX_FP_LEN
@@ -90,9 +93,14 @@ class _HashEmbedFunction(torch.autograd.Function):
             out_shape = tuple(shape) + (D,)
         out = torch.empty(out_shape, dtype=torch.float32, device=dev)        # every element is written by the kernel
         wc = _lib.f32c(weights.detach(), 'weights') if weights is not None else None
-        _lib.call('recnow_hash_embed_fwd', _lib.ptr(ids), id_dtype, B, L, ctypes.cast(_i64_array(salts), ctypes.c_void_p), nh,
-                  1 if first_unsalted else 0, num_bins, ctypes.cast(tab_arr, ctypes.c_void_p), D, _lib.ptr(wc), mode, _lib.ptr(out),
-                  _lib.ptr(keys), _lib.ptr(keys32), _lib.stream())
+        if id_dtype == _CROSS:      # ids: (CrossedIds, the default string's buckets); the kernel composes and hashes the texts itself
+            _lib.call('recnow_cross_hash_embed_fwd', ids[0].desc(ids[1]), B, ctypes.cast(_i64_array(salts), ctypes.c_void_p), nh,
+                      1 if first_unsalted else 0, num_bins, ctypes.cast(tab_arr, ctypes.c_void_p), D, _lib.ptr(wc), mode, _lib.ptr(out),
+                      _lib.ptr(keys), _lib.ptr(keys32), _lib.stream())
+        else:
+            _lib.call('recnow_hash_embed_fwd', _lib.ptr(ids), id_dtype, B, L, ctypes.cast(_i64_array(salts), ctypes.c_void_p), nh,
+                      1 if first_unsalted else 0, num_bins, ctypes.cast(tab_arr, ctypes.c_void_p), D, _lib.ptr(wc), mode, _lib.ptr(out),
+                      _lib.ptr(keys), _lib.ptr(keys32), _lib.stream())
         saved = [keys, keys32, wc if need_dt else None] + (tabs if need_dw else [])
         ctx.save_for_backward(*saved)
         ctx.meta = (B, L, nh, num_bins, D, mode, one_table, need_dt, need_dw, len(tables))
@@ -208,7 +216,10 @@ class _HashLayerBase(Layer):
 
     # -- inputs ----------------------------------------------------------------------------------------------------------------------
     def _plan_inputs(self, inputs):
-        """-> (ids tensor or numpy buckets, id_dtype, shape).  Integer GPU tensors are hashed by the kernels; str / bytes arrays on the host."""
+        """-> (ids tensor or numpy buckets, id_dtype, shape).  Integer GPU tensors are hashed by the kernels; str / bytes arrays on the host;
+        a CrossedIds (CartesianProductLayer) -> ((it, its default string's buckets), _CROSS, its (B, P))."""
+        if isinstance(inputs, CrossedIds):
+            return self._plan_cross(inputs), _CROSS, tuple(inputs.shape)
         if isinstance(inputs, torch.Tensor):
             if inputs.dtype.is_floating_point or inputs.dtype in (torch.bool, torch.complex64, torch.complex128):
                 raise TypeError('%s hashes integer ids (int32 / int64) or strings, got a %s tensor' % (type(self).__name__, inputs.dtype))
@@ -226,11 +237,32 @@ class _HashLayerBase(Layer):
                             % (type(self).__name__, type(inputs).__name__))
         return hash_strings_host(flat, self.num_bins, self.salts, self._FAST), _BUCKETS, tuple(arr.shape)
 
+    def _plan_cross(self, crossed):
+        """The limits a cross must keep under this layer, checked before any launch; the buckets of its default string, hashed on the host."""
+        longest = max(crossed.worst_text_bytes, len(crossed.default))
+        if self._FAST and longest > MAX_UNSALTED_BYTES:
+            raise NotImplementedError('%s: the unsalted hash (Fingerprint64) is implemented for texts of up to %d bytes; this cross can reach %d bytes '
+                                      '(11 per int32 input, 20 per int64 input, the separators; or the default string). MultiHashLayer takes it.'
+                                      % (type(self).__name__, MAX_UNSALTED_BYTES, longest))
+        B, P = crossed.shape
+        if B * P * self.num_hash >= (1 << 31):
+            raise NotImplementedError('B * P * num_hash = %d * %d * %d: the kernels address fewer than 2^31 crossed entries' % (B, P, self.num_hash))
+        _lib.require_gpu(crossed.inputs[0], '%s input' % type(self).__name__)
+        default_buckets = None
+        if crossed.has_patterns:
+            default_buckets = hash_strings_host([crossed.default], self.num_bins, self.salts, self._FAST)[0].tolist()
+        return crossed, default_buckets
+
     def _buckets(self, ids, id_dtype, shape):
         """(shape..., num_hash) int64 bucket numbers (embedding_dim <= 0)."""
         nh = self.num_hash
         if id_dtype == _BUCKETS:
             return torch.from_numpy(ids).reshape(tuple(shape) + (nh,))          # hashed on the host already: stays there
+        if id_dtype == _CROSS:
+            out = torch.empty(tuple(shape) + (nh,), dtype=torch.int64, device=ids[0].device)
+            _lib.call('recnow_cross_hash_ids', ids[0].desc(ids[1]), shape[0], ctypes.cast(_i64_array(self.salts), ctypes.c_void_p), nh,
+                      1 if self._FAST else 0, self.num_bins, _lib.ptr(out), _lib.stream())
+            return out
         out = torch.empty(tuple(shape) + (nh,), dtype=torch.int64, device=ids.device)
         _lib.call('recnow_hash_ids', _lib.ptr(ids), id_dtype, ids.numel(), ctypes.cast(_i64_array(self.salts), ctypes.c_void_p), nh,
                   1 if self._FAST else 0, self.num_bins, _lib.ptr(out), _lib.stream())
@@ -258,7 +290,7 @@ class _HashLayerBase(Layer):
 
     # -- reference API ---------------------------------------------------------------------------------------------------------------
     def forward(self, inputs, *args, **kwargs):
-        if not self.built and isinstance(inputs, torch.Tensor):
+        if not self.built and isinstance(inputs, (torch.Tensor, CrossedIds)):
             self._build_device = inputs.device
         if not self.built:
             self.build(None)
@@ -266,7 +298,7 @@ class _HashLayerBase(Layer):
 
     def get(self, inputs):
         if not self.built:
-            if isinstance(inputs, torch.Tensor):
+            if isinstance(inputs, (torch.Tensor, CrossedIds)):
                 self._build_device = inputs.device
             self.build()
         return self(inputs, combiner='sum')
@@ -276,7 +308,7 @@ class _HashLayerBase(Layer):
         if self.embedding_dim <= 0:
             raise ValueError('get_pooling needs embedding_dim > 0')
         if not self.built:
-            if isinstance(keys, torch.Tensor):
+            if isinstance(keys, (torch.Tensor, CrossedIds)):
                 self._build_device = keys.device
             self.build()
         ids, id_dtype, shape = self._plan_inputs(keys)

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -559,6 +559,65 @@ def hash():
         torch.cuda.empty_cache()
 
 
+def cross():
+    """CartesianProductLayer -> MultiHashLayer at B = 65536, two int64 inputs of 10 and 5 ids (P = 50 crossed ids per row, the L of the `hash` row),
+    num_hash = 2, num_bins = 2^20, D = 8 and 32: `call(sum)` ((B, P, D)) and `get_pooling` ((B, D), weighted), forward and forward + backward.  Beside
+    it, in the same run: (a) the same layer on a precomputed (B, 50) int64 id tensor -- the plain-id kernel, so the difference is what composing and
+    hashing the two to three times longer text costs (the crossed launch reads 15 ids per row instead of 50); (b) the host route: the (B, P) Python
+    strings, hash_strings_host, the upload of the (B, P, num_hash) buckets and the gather, timed once each (seconds, not milliseconds)."""
+    import time
+    from rec_now_amd.layers import CartesianProductLayer, MultiHashLayer
+    from rec_now_amd.layers.multi_hash_layer import MODE_SUM, _BUCKETS, hash_strings_host
+    B, L1, L2, nh, nb = 65536, 10, 5, 2, 1 << 20
+    P = L1 * L2
+    a, b = torch.randint(0, 1 << 40, (B, L1), device=dev), torch.randint(0, 1 << 40, (B, L2), device=dev)
+    ids = torch.randint(0, 1 << 40, (B, P), device=dev)
+    product = CartesianProductLayer()
+    crossed = product([a, b])
+    t0 = time.perf_counter()
+    strs = product([a.cpu().numpy(), b.cpu().numpy()])
+    t1 = time.perf_counter()
+    bk = hash_strings_host(strs.reshape(-1).tolist(), nb, [1, 2], False)
+    t2 = time.perf_counter()
+    print('host route B=%d P=%d: Python strings %.2f s, hash_strings_host %.2f s (mean text %.1f bytes)'
+          % (B, P, t1 - t0, t2 - t1, sum(len(t) for t in strs[:64].reshape(-1)) / (64.0 * P)))
+    for D in (8, 32):
+        w = torch.randn(B, P, device=dev, requires_grad=True)
+        layer = MultiHashLayer(nb, D, num_hash=nh, embeddings_initializer='random_normal')
+        layer.get(ids[:4])
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        layer._embed(bk, _BUCKETS, (B, P), MODE_SUM)
+        torch.cuda.synchronize()
+        print('host route D=%d: bucket upload + gather %.1f ms' % (D, (time.perf_counter() - t3) * 1e3))
+        g_sum, g_pool = torch.randn(B, P, D, device=dev), torch.randn(B, D, device=dev)
+        cases = (('call(sum)', lambda: layer(crossed, combiner='sum'), lambda: layer(ids, combiner='sum'), g_sum),
+                 ('get_pooling', lambda: layer.get_pooling(crossed, w), lambda: layer.get_pooling(ids, w), g_pool))
+        for name, run, ref, gy in cases:
+            def fb_of(fn):
+                def step():
+                    for t in layer.tables:
+                        t.grad = None
+                    w.grad = None
+                    fn().backward(gy)
+                return step
+            # both orders: crossed, plain ids, plain ids, crossed; the two figures of each are averaged
+            f1, b1 = timeit(run), timeit(fb_of(run))
+            r1, rb1 = timeit(ref), timeit(fb_of(ref))
+            r2, rb2 = timeit(ref), timeit(fb_of(ref))
+            f2, b2 = timeit(run), timeit(fb_of(run))
+            ms_f, ms_b, rf, rb = (f1 + f2) / 2, (b1 + b2) / 2, (r1 + r2) / 2, (rb1 + rb2) / 2
+            print('MultiHashLayer.%-11s on CrossedIds B=%d (10 x 5 int64) D=%d num_hash=%d num_bins=2^20 : fwd %.3f ms, fwd+bwd %.3f ms | the same on a (B, 50) id '
+                  'tensor: fwd %.3f ms, fwd+bwd %.3f ms -> crossed / plain fwd %.2fx fwd+bwd %.2fx | runs crossed fwd %.3f / %.3f, fwd+bwd %.3f / %.3f, plain fwd '
+                  '%.3f / %.3f, fwd+bwd %.3f / %.3f ms' % (name, B, D, nh, ms_f, ms_b, rf, rb, ms_f / rf, ms_b / rb, f1, f2, b1, b2, r1, r2, rb1, rb2))
+        del w, layer, g_sum, g_pool
+        torch.cuda.empty_cache()
+    plain = MultiHashLayer(nb, -1, num_hash=nh)
+    hs, hp = timeit(lambda: plain(crossed, combiner='concat')), timeit(lambda: plain(ids, combiner='concat'))
+    tx = timeit(lambda: crossed.text_bytes())
+    print('MultiHashLayer bucket numbers only B=%d P=%d num_hash=%d : crossed %.3f ms, plain ids %.3f ms; CrossedIds.text_bytes() %.3f ms' % (B, P, nh, hs, hp, tx))
+
+
 def slot():
     """fetch_single_slot, embedding_single_slot (forward, forward + backward) and pool_slots (T = 24) at B = 65536, C = 128, ncols = 50, V = 2^20,
     D = 8 and 32; the target slot occurs 0..40 times per row (mean about 20).  Byte model (algorithmic): the (B, C) inputs read once, the outputs
@@ -742,6 +801,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('slot', slot), ('tensor_util', tensor_util), ('can', can)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can)):
         if name in which:
             fn()
