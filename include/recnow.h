@@ -857,6 +857,27 @@ int recnow_sparse_gnn_bwd(const float* x, const float* const* x_fields, int in_l
                           const float* const* dy_all, int dy_aligned, float* dx, float* dw, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * SparseGNNLayer, the dense route (ABI 15): the same layer with the graph as a dense matrix on the matrix cores (csrc/sparse_gnn_dense.hip),
+ * for F <= 128 and E <= F * F: else RECNOW_EUNSUPPORTED.  Per call a small launch scatters w into M = I + W (n_sets, 2, FP, FP), FP = F rounded
+ * up to 32, plane 1 the transpose; a layer over a tile of (row, channel) pairs is then one exact-fp32 product on v_mfma_f32_32x32x2_f32
+ * whatever the number of edges.  One launch per direction runs all L layers on tiles in LDS; the backward recomputes the chain and forms
+ * dM = sum over pairs of v_in dz^T as a product over the pairs, added to one workspace row per workgroup; a second launch sums the rows in
+ * row order at the edge positions into dw (no float atomics: dx and dw are bit-identical from run to run).
+ *   Arguments as recnow_sparse_gnn_fwd / _bwd, except: src, dst: DEVICE int32 arrays of E entries, the edges [source, destination] in
+ *     ascending order (entry e belongs to w[.][e]; every index < F; no edge twice) instead of `tab`; ws of
+ *     recnow_sparse_gnn_dense_workspace_bytes(F, E, n_sets, backward): the dense matrices, and with backward != 0 (needed only with dw) the
+ *     rows of dM: at most 1024 rows and at most 32 MB (but 16 rows), independent of B and D.  16-byte aligned.  Both directions need it.
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t recnow_sparse_gnn_dense_workspace_bytes(int F, int E, int n_sets, int backward);
+int recnow_sparse_gnn_dense_fwd(const float* x, const float* const* x_fields, int in_layout, int x_aligned, int out_layout, const int32_t* src,
+                                const int32_t* dst, const float* w, int64_t B, int F, int D, int E, int L, int n_sets, int act, float* y_last,
+                                float* const* y_all, int y_aligned, void* ws, size_t ws_bytes, void* stream);
+int recnow_sparse_gnn_dense_bwd(const float* x, const float* const* x_fields, int in_layout, int x_aligned, int out_layout, const int32_t* src,
+                                const int32_t* dst, const float* w, int64_t B, int F, int D, int E, int L, int n_sets, int act,
+                                const float* dy_last, const float* const* dy_all, int dy_aligned, float* dx, float* dw, void* ws,
+                                size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Tensor plumbing (ABI 12): rec_now/layers/pooling_layer.py (PoolingLayer), rec_now/layers/fix_length_layer.py (pad_or_truncate,
  * FixLengthLayer), rec_now/rec_block/embedding_wise_weight.py (gather_embedding_element_wise_weight).  csrc/tensor_util.hip.
  * Every contiguous tensor is given as (O, R, I): outer extent, the axis worked on, inner extent.  fp32 unless said otherwise.

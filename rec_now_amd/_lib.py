@@ -138,6 +138,9 @@ SIGNATURES = {
     'recnow_sparse_gnn_workspace_bytes': (_Z, [_L, _I, _I, _I, _I]),
     'recnow_sparse_gnn_fwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     'recnow_sparse_gnn_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    'recnow_sparse_gnn_dense_workspace_bytes': (_Z, [_I, _I, _I, _I]),
+    'recnow_sparse_gnn_dense_fwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _Z, _P]),
+    'recnow_sparse_gnn_dense_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _Z, _P]),
     'recnow_reduce_axis_workspace_bytes': (_Z, [_L, _L, _L]),
     'recnow_reduce_axis_fwd': (_I, [_P, _L, _L, _L, _I, _P, _P, _Z, _P]),
     'recnow_reduce_axis_bwd': (_I, [_P, _P, _P, _L, _L, _L, _I, _P, _P]),
@@ -179,7 +182,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 14    # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 15    # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -10,5 +10,6 @@
 // _bwd_weights, recnow_embed_rows_bwd_direct (MultiHashLayer, FastMultiHashLayer); 11: recnow_slot_max_count, recnow_slot_fetch / _fetch_bwd, recnow_slot_embed_fwd,
 // recnow_slot_pool_fwd / _pool_bwd (fetch_single_slot, embedding_single_slot, pool_slots); 12: recnow_reduce_axis_fwd / _bwd / _workspace_bytes, recnow_pad_axis,
 // recnow_elem_weight_fwd / _bwd (PoolingLayer, FixLengthLayer, gather_embedding_element_wise_weight); 13: recnow_can_fwd / _bwd / _supported (CANLayer);
-// 14: recnow_cross_desc, recnow_cross_text / _hash_ids (+ _host twins), recnow_cross_hash_embed_fwd (CartesianProductLayer).
-extern "C" int recnow_abi_version(void) { return 14; }
+// 14: recnow_cross_desc, recnow_cross_text / _hash_ids (+ _host twins), recnow_cross_hash_embed_fwd (CartesianProductLayer);
+// 15: recnow_sparse_gnn_dense_fwd / _bwd / _workspace_bytes (SparseGNNLayer, the dense MFMA route).
+extern "C" int recnow_abi_version(void) { return 15; }

@@ -4,6 +4,10 @@ The fields are the nodes of a hand-given directed graph; every layer replaces a 
 with one trainable weight per edge.  The reference transposes the input to (B, D, F) and multiplies it by a dense (F, F) matrix per layer;
 here one HIP kernel per direction (csrc/sparse_gnn.hip) runs all layers on tiles that stay on chip: the forward reads the input once and
 writes each requested output once, the backward recomputes the layer chain from the input instead of keeping the layer outputs.
+
+Two routes, chosen per layer object with `route=`: 'edges' walks the edge list (csrc/sparse_gnn.hip, at most 64 fields, cost per edge), 'dense'
+multiplies by the dense matrix I + W on the matrix cores (csrc/sparse_gnn_dense.hip, at most 128 fields, cost independent of the edges), 'auto'
+takes the faster one by the measured table below (auto_route).
 """
 import logging
 
@@ -14,6 +18,8 @@ from ._keras import Layer, activation_code
 
 DEFAULT_NEIGHBOR_INITIAL_WEIGHT = 0.1
 MAX_FIELDS = 64                      # SG_MAXF of csrc/sparse_gnn.hip
+MAX_FIELDS_DENSE = 128               # SD_MAXF of csrc/sparse_gnn_dense.hip
+ROUTES = ('edges', 'dense', 'auto')
 LAYOUT_BFD, LAYOUT_BDF, LAYOUT_LIST = 0, 1, 2      # RECNOW_GNN_* of include/recnow.h
 
 
@@ -64,13 +70,37 @@ def _pack_tables(t, num_fields):
     return [len(dG) // CHUNK, len(sG) // CHUNK, 0, 0] + dS + dG + sS + sG + t['ssrc'] + t['sdst'] + t['swid']
 
 
+# route='auto': the fewest edges at which the dense route beat the edge route in BOTH directions, per field count up to which the entry holds.
+# The dense route's cost depends on F rounded up to 32 and not on E, the edge route's grows with E, so the rule is a number of edges.
+# MI355X, B 65 536, D 32, L 3, tanh, unshared weights, ms forward / backward (profiles/gnn_layer_bench.txt):
+#   F 32   in-degree   2 (E 64)       4 (E 128)      8 (E 256)      16 (E 512)     31 (E 992)
+#          edges       0.577 / 4.78   0.576 / 5.49   0.865 / 8.63   1.447 / 15.2   2.633 / 27.9
+#          dense       0.314 / 1.77   0.316 / 1.74   0.320 / 1.72   0.324 / 1.71   0.322 / 1.71
+#   F 64   in-degree   8 (E 512)      32 (E 2048)    63 (E 4032)
+#          edges       3.862 / 32.6   11.51 / 111    21.71 / 216
+#          dense       1.165 / 6.03   1.168 / 6.03   1.167 / 6.08
+# The smallest graphs measured already favour the dense route; below them nothing was measured and the edge route stays.
+DENSE_MIN_EDGES = ((32, 64), (64, 512))
+
+
+def auto_route(num_fields, num_edges):
+    """The route `route='auto'` takes: 'dense' above 64 fields (the edge route stops there), or when the graph has at least the measured
+    cross-over number of edges of its field count; 'edges' otherwise."""
+    if num_fields > MAX_FIELDS:
+        return 'dense'
+    for fields, edges in DENSE_MIN_EDGES:
+        if num_fields <= fields:
+            return 'dense' if num_edges >= edges else 'edges'
+    return 'edges'
+
+
 class _SparseGNNFunction(torch.autograd.Function):
     """All layers as one node.  Saves the input, the weights and the edge tables only; `n_out` outputs: every layer's (in one block) or the
     last one's."""
 
     @staticmethod
     def forward(ctx, meta, w, *xs):
-        F, E, L, n_sets, act, in_layout, out_layout, all_layers, tab = meta
+        F, E, L, n_sets, act, in_layout, out_layout, all_layers, tab, dense = meta
         xs = [_lib.f32c(x, 'SparseGNNLayer input') for x in xs]
         wc = _lib.f32c(w.detach(), 'weights')
         dev = xs[0].device
@@ -83,7 +113,7 @@ class _SparseGNNFunction(torch.autograd.Function):
             D = xs[0].shape[1] // F if xs[0].dim() == 2 else xs[0].shape[2 if in_layout == LAYOUT_BFD else 1]
             x_ptr, xl_ptr, aligned = _lib.ptr(xs[0]), None, 0
         shape = (B, F, D) if out_layout == LAYOUT_BFD else (B, D, F)
-        tabd = _lib.const_array(tab, torch.int32, dev)
+        tabd = _lib.const_array(tab, torch.int32, dev)       # dense: the E sources, then the E destinations of the sorted edge list
         if all_layers:
             y = torch.empty((L,) + shape, dtype=torch.float32, device=dev)
             y_last, y_all = None, _lib.ptr(_lib.block_ptr_array(y, L)) if B else None
@@ -92,17 +122,22 @@ class _SparseGNNFunction(torch.autograd.Function):
             y = torch.empty(shape, dtype=torch.float32, device=dev)
             y_last, y_all = _lib.ptr(y), None
             outs = (y,)
-        if B:
+        if B and dense:
+            ws = _lib.workspace(_lib.load().recnow_sparse_gnn_dense_workspace_bytes(F, E, n_sets, 0), dev)
+            _lib.call('recnow_sparse_gnn_dense_fwd', x_ptr, xl_ptr, in_layout, aligned, out_layout, _lib.ptr(tabd), _lib.ptr(tabd[E:]),
+                      _lib.ptr(wc), B, F, D, E, L, n_sets, act, y_last, y_all, int(y.data_ptr() % 16 == 0 and (F * D) % 4 == 0), _lib.ptr(ws),
+                      ws.numel(), _lib.stream())
+        elif B:
             _lib.call('recnow_sparse_gnn_fwd', x_ptr, xl_ptr, in_layout, aligned, out_layout, _lib.ptr(tabd), _lib.ptr(wc), B, F, D, E, L,
                       n_sets, act, y_last, y_all, int(y.data_ptr() % 16 == 0 and (F * D) % 4 == 0), _lib.stream())
         ctx.save_for_backward(wc, tabd, *xs)
-        ctx.meta = (B, D) + tuple(meta[:8])
+        ctx.meta = (B, D) + tuple(meta[:8]) + (dense,)
         return outs
 
     @staticmethod
     def backward(ctx, *dys):
         wc, tabd, *xs = ctx.saved_tensors
-        B, D, F, E, L, n_sets, act, in_layout, out_layout, all_layers = ctx.meta
+        B, D, F, E, L, n_sets, act, in_layout, out_layout, all_layers, dense = ctx.meta
         dev = wc.device
         need_w, need_x = ctx.needs_input_grad[1] and E > 0, any(ctx.needs_input_grad[2:])
         dw = torch.empty_like(wc) if need_w else None
@@ -123,10 +158,16 @@ class _SparseGNNFunction(torch.autograd.Function):
                 aligned = int(all(x.data_ptr() % 16 == 0 for x in xs))
             else:
                 x_ptr, xl_ptr, aligned = _lib.ptr(xs[0]), None, 0
-            ws = _lib.workspace(_lib.load().recnow_sparse_gnn_workspace_bytes(B, F, D, E, n_sets) if need_w else 0, dev)
-            _lib.call('recnow_sparse_gnn_bwd', x_ptr, xl_ptr, in_layout, aligned, out_layout, _lib.ptr(tabd), _lib.ptr(wc), B, F, D, E, L,
-                      n_sets, act, dy_last, dy_all, al, _lib.ptr(dx), _lib.ptr(dw) if need_w else None, _lib.ptr(ws), ws.numel(),
-                      _lib.stream())
+            if dense:
+                ws = _lib.workspace(_lib.load().recnow_sparse_gnn_dense_workspace_bytes(F, E, n_sets, int(need_w)), dev)
+                _lib.call('recnow_sparse_gnn_dense_bwd', x_ptr, xl_ptr, in_layout, aligned, out_layout, _lib.ptr(tabd), _lib.ptr(tabd[E:]),
+                          _lib.ptr(wc), B, F, D, E, L, n_sets, act, dy_last, dy_all, al, _lib.ptr(dx), _lib.ptr(dw) if need_w else None,
+                          _lib.ptr(ws), ws.numel(), _lib.stream())
+            else:
+                ws = _lib.workspace(_lib.load().recnow_sparse_gnn_workspace_bytes(B, F, D, E, n_sets) if need_w else 0, dev)
+                _lib.call('recnow_sparse_gnn_bwd', x_ptr, xl_ptr, in_layout, aligned, out_layout, _lib.ptr(tabd), _lib.ptr(wc), B, F, D, E, L,
+                          n_sets, act, dy_last, dy_all, al, _lib.ptr(dx), _lib.ptr(dw) if need_w else None, _lib.ptr(ws), ws.numel(),
+                          _lib.stream())
         if dx is None:
             dxs = (None,) * len(xs)
         elif in_layout == LAYOUT_LIST:
@@ -147,15 +188,22 @@ class SparseGNNLayer(Layer):
     Weights: `weights_{idx}` of shape (E,), one per weight set.  Entry k belongs to the k-th pair of the ascending-sorted list of
     [neighbor_idx, field_idx] (the reference's `_generate_indices`), so reference checkpoints load 1:1.
 
-    A callable activation is applied by torch, layer by layer, around one-layer linear kernel calls.  At most 64 fields.
+    A callable activation is applied by torch, layer by layer, around one-layer linear kernel calls.
+
+    route (keyword only): 'edges' (the default) walks the edge list, at most 64 fields; 'dense' multiplies by the dense (F, F) matrix on the
+    matrix cores, at most 128 fields, faster on all but the sparsest graphs; 'auto' picks by `auto_route`.  The routes agree to fp32 rounding,
+    not bit for bit; weights, checkpoints and state_dict names are the same.
     """
 
     def __init__(self, fields, field2neighbors, weights_initializer=_default_initializer, num_layers=1,
-                 share_weights_between_layers=True, activation='tanh', **kwargs):
+                 share_weights_between_layers=True, activation='tanh', *, route='edges', **kwargs):
         """fields: list of F hashable field ids; field2neighbors: dict field -> list / set of neighbours, or a list / set of
         (node_to, node_from) pairs; weights_initializer: defaults to the constant 0.1; num_layers; share_weights_between_layers;
         activation: 'linear' / 'relu' / 'tanh' / 'sigmoid' / None, or a callable on torch tensors."""
         super().__init__(**kwargs)
+        if route not in ROUTES:
+            raise ValueError('route must be one of %s, got %r' % (', '.join(repr(r) for r in ROUTES), route))
+        self.route = route
         self.fields = fields
         self.field2neighbors = self._normalize_neighbors(field2neighbors)
         self.field2idx = {field: idx for idx, field in enumerate(fields)}
@@ -220,7 +268,14 @@ class SparseGNNLayer(Layer):
                             for idx in range(self._num_sets_of_gnn_weights())]
         self.edge_tables = edge_tables(self.indices, len(self.fields))
         self._tab = tuple(_pack_tables(self.edge_tables, len(self.fields)))
+        self._edges = tuple(s for s, _ in self.indices) + tuple(d for _, d in self.indices) or (0,)     # the dense route's src | dst
         self.built = True
+
+    def chosen_route(self):
+        """'edges' or 'dense': what `route` comes to for this graph."""
+        if self.route != 'auto':
+            return self.route
+        return auto_route(len(self.fields), self._num_edges())
 
     def _plan_inputs(self, inputs):
         """(tensors, layout) of the kernel call.  Shape errors first, as the reference raises them; then the device check."""
@@ -258,18 +313,24 @@ class SparseGNNLayer(Layer):
         transpose_outputs=False gives the (B, D, F) order, flattern_outputs=False keeps three dimensions."""
         F, L = len(self.fields), self.num_layers
         xs, in_layout = self._plan_inputs(inputs)
-        if F > MAX_FIELDS:
-            raise NotImplementedError('SparseGNNLayer: %d fields; the fused kernel holds at most %d (csrc/sparse_gnn.hip)' % (F, MAX_FIELDS))
+        dense = self.chosen_route() == 'dense'
+        if not dense and F > MAX_FIELDS:
+            raise NotImplementedError("SparseGNNLayer: %d fields; the fused kernel holds at most %d (csrc/sparse_gnn.hip); pass route='dense' "
+                                      'for up to %d' % (F, MAX_FIELDS, MAX_FIELDS_DENSE))
+        if dense and F > MAX_FIELDS_DENSE:
+            raise NotImplementedError('SparseGNNLayer: %d fields; the dense route holds at most %d (csrc/sparse_gnn_dense.hip)'
+                                      % (F, MAX_FIELDS_DENSE))
+        tab = self._edges if dense else self._tab
         out_layout = LAYOUT_BFD if transpose_outputs else LAYOUT_BDF
         E, n_sets = len(self.indices), len(self.gnn_weights)
         if self.act_callable is None:
             w = torch.stack(self.gnn_weights) if n_sets > 1 else self.gnn_weights[0].reshape(1, E)
-            meta = (F, E, L, n_sets, self.act_code, in_layout, out_layout, bool(return_all_layers), self._tab)
+            meta = (F, E, L, n_sets, self.act_code, in_layout, out_layout, bool(return_all_layers), tab, dense)
             outs = list(_SparseGNNFunction.apply(meta, w, *xs))
         else:       # the kernel runs one linear layer at a time, the callable is torch's
             outs, cur, layout = [], xs, in_layout
             for i in range(L):
-                meta = (F, E, 1, 1, 0, layout, out_layout, False, self._tab)
+                meta = (F, E, 1, 1, 0, layout, out_layout, False, tab, dense)
                 z = _SparseGNNFunction.apply(meta, self.gnn_weights[i % n_sets].reshape(1, E), *cur)[0]
                 z = self.act_callable(z)
                 outs.append(z)

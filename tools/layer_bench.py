@@ -472,47 +472,70 @@ def gnn_ref_eager(x, indices, ws, L, F):
 
 
 def gnn():
-    """SparseGNNLayer at B = 65536, F = 32, D = 32 (F*D = 1024), L = 3, tanh, unshared weights, for a ring (E = 64), E = 256 and the complete
-    graph without self loops (E = 992): forward and backward time each, TB/s of algorithmic bytes (forward 2 B F D 4: x read, y written;
-    backward 3 B F D 4: x and dy read, dx written), and the same step for the reference algorithm in torch eager."""
+    """SparseGNNLayer at B = 65536, D = 32, L = 3, tanh, unshared weights, on circulant graphs (node i aggregates its k nearest neighbours; k = 2 is
+    the ring, k = F - 1 the complete graph): F 32 with in-degree 2, 4, 8, 16, 31, F 64 with 8, 32, 63, F 128 complete.  Per graph the edge route
+    (csrc/sparse_gnn.hip, F <= 64), the dense MFMA route (csrc/sparse_gnn_dense.hip) and the reference algorithm in torch eager, timed in the
+    same run in both orders (edges, dense, reference, reference, dense, edges; the two figures of each are averaged): forward and backward
+    time each, TB/s of algorithmic bytes (forward 2 B F D 4: x read, y written; backward 3 B F D 4: x and dy read, dx written) and for the
+    dense route TFLOP/s of its MFMA work (forward 2 B D F^2 L; backward three times that: the recomputed chain, dz M^T and dM).  First line:
+    the plain-stream rate of the same run (a device copy of the F 32 input)."""
+    import logging
     from rec_now_amd.layers.sparse_gnn_layer import SparseGNNLayer
-    B, F, D, L = 65536, 32, 32, 3
-    graphs = (('ring', {i: [(i - 1) % F, (i + 1) % F] for i in range(F)}),
-              ('8 nearest', {i: [(i + k) % F for k in (-4, -3, -2, -1, 1, 2, 3, 4)] for i in range(F)}),
-              ('complete', {i: [j for j in range(F) if j != i] for i in range(F)}))
-    for name, nbrs in graphs:
+    B, D, L = 65536, 32, 3
+    logging.getLogger().setLevel(logging.ERROR)       # F == D = 32: the layer warns on every call that it reads the input as (B, F, D)
+    src = torch.randn(B, 32 * D, device=dev)
+    ms = timeit(lambda: src.clone())
+    print('plain stream (clone of %d MB): %.3f ms, %.2f TB/s read + written' % (src.numel() * 4 >> 20, ms, 2 * 4.0 * src.numel() / ms / 1e9))
+    del src
+    for F, k in ((32, 2), (32, 4), (32, 8), (32, 16), (32, 31), (64, 8), (64, 32), (64, 63), (128, 127)):
+        offs = [o for j in range(1, k // 2 + 1) for o in (-j, j)] + ([k // 2 + 1] if k % 2 else [])
+        nbrs = {i: sorted((i + o) % F for o in offs) for i in range(F)}
         x = (torch.randn(B, F, D, device=dev) * 0.5).requires_grad_(True)
         gy = torch.randn(B, F * D, device=dev)
-        layer = SparseGNNLayer(list(range(F)), nbrs, num_layers=L, share_weights_between_layers=False, activation='tanh')
-        run = lambda: layer(x)                                  # noqa: E731
-        run()
-        E = len(layer.indices)
+        layers = {r: SparseGNNLayer(list(range(F)), nbrs, num_layers=L, share_weights_between_layers=False, activation='tanh', route=r)
+                  for r in (('edges', 'dense') if F <= 64 else ('dense',))}
+        dense = layers['dense']
+        dense(x[:8])
+        E = len(dense.indices)
+        assert E == k * F
         with torch.no_grad():
-            for v in layer.named_weights().values():
-                v.mul_(min(1.0, 8.0 / (E / F)))
-        ix = torch.tensor(layer.indices, device=dev)
-        ref = lambda: gnn_ref_eager(x, ix, layer.gnn_weights, L, F)      # noqa: E731
+            for v in dense.named_weights().values():
+                v.mul_(min(1.0, 8.0 / k))
+        for lay in layers.values():
+            lay(x[:8])
+            lay.load_state_dict(dense.state_dict())
+        ix = torch.tensor(dense.indices, device=dev)
+        fns = {r: (lambda lay=lay: lay(x)) for r, lay in layers.items()}
+        fns['ref'] = lambda: gnn_ref_eager(x, ix, dense.gnn_weights, L, F)
+        err = {r: float((fns[r]() - fns['ref']()).detach().abs().max()) for r in layers}
 
         def bwd_of(fn):
             y = fn()
 
             def step():
                 x.grad = None
-                layer.zero_grad(set_to_none=True)
+                for lay in layers.values():
+                    lay.zero_grad(set_to_none=True)
                 y.backward(gy, retain_graph=True)
             return step
 
-        nbytes = 4.0 * B * F * D
-        # both orders: fused, reference, reference, fused; the two fused figures are averaged, and so are the two reference figures
-        f1, b1 = timeit(run), timeit(bwd_of(run))
-        r1, rb1 = timeit(ref), timeit(bwd_of(ref))
-        r2, rb2 = timeit(ref), timeit(bwd_of(ref))
-        f2, b2 = timeit(run), timeit(bwd_of(run))
-        ms_f, ms_b, rf, rb = (f1 + f2) / 2, (b1 + b2) / 2, (r1 + r2) / 2, (rb1 + rb2) / 2
-        print('SparseGNNLayer %-9s E=%-3d B=%d F=%d D=%d L=%d tanh unshared : fwd %.3f ms %.2f TB/s, bwd %.3f ms %.2f TB/s (algorithmic) | reference in '
-              'torch eager: fwd %.3f ms, bwd %.3f ms -> speedup fwd %.1fx bwd %.1fx | runs fwd %.3f / %.3f, bwd %.3f / %.3f ms'
-              % (name, E, B, F, D, L, ms_f, 2 * nbytes / ms_f / 1e9, ms_b, 3 * nbytes / ms_b / 1e9, rf, rb, rf / ms_f, rb / ms_b, f1, f2, b1, b2))
-        del x, gy, layer
+        order = [r for r in ('edges', 'dense', 'ref') if r in fns]
+        t = {r: [] for r in order}
+        for r in order + order[::-1]:
+            t[r].append((timeit(fns[r]), timeit(bwd_of(fns[r]))))
+        nbytes, flops = 4.0 * B * F * D, 2.0 * B * D * F * F * L
+        rf, rb = (t['ref'][0][0] + t['ref'][1][0]) / 2, (t['ref'][0][1] + t['ref'][1][1]) / 2
+        print('SparseGNNLayer F=%d in-degree %d E=%d B=%d D=%d L=%d tanh unshared | reference in torch eager: fwd %.3f ms, bwd %.3f ms'
+              % (F, k, E, B, D, L, rf, rb))
+        for r in layers:
+            (f1, b1), (f2, b2) = t[r]
+            ms_f, ms_b = (f1 + f2) / 2, (b1 + b2) / 2
+            mfma = ', MFMA fwd %.1f bwd %.1f TFLOP/s' % (flops / ms_f / 1e9, 3 * flops / ms_b / 1e9) if r == 'dense' else ''
+            print('    %-5s: fwd %.3f ms %.2f TB/s, bwd %.3f ms %.2f TB/s (algorithmic)%s | against eager fwd %.1fx bwd %.1fx fwd+bwd %.1fx | '
+                  'runs fwd %.3f / %.3f, bwd %.3f / %.3f ms | max |y - eager| %.2g'
+                  % (r, ms_f, 2 * nbytes / ms_f / 1e9, ms_b, 3 * nbytes / ms_b / 1e9, mfma, rf / ms_f, rb / ms_b, (rf + rb) / (ms_f + ms_b),
+                     f1, f2, b1, b2, err[r]))
+        del x, gy, layers, dense, fns
         torch.cuda.empty_cache()
 
 
