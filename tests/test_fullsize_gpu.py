@@ -138,9 +138,10 @@ def test_fm_wide_kernels_ragged_sizes(dev, B, F, D):
 
 
 def test_ple_config5_per_rank_size(dev):
-    """configs[4] per-rank share: B = 32768, D_in = 128 x 32, 3 tasks; row subset against the oracle is not available for PLE
-    without re-deriving its weight layout, so the checks are the size-independent ones: row independence (the outputs and
-    input gradients of a row do not depend on which batch it is evaluated in) and linearity of the weight gradients."""
+    """configs[4] per-rank share: B = 32768, D_in = 128 x 32, 3 tasks.  Rows are independent, so the 512-row subset is held to the fp64 oracle
+    (oracle/dense_ref.ple_layer on the layer's own weights, tests/_ple_oracle.oracle_layers): the full-batch outputs and input gradient of those
+    rows, per row, within 1e-5 x the row's max |ref|.  Then the size-independent checks: row independence on the GPU (the outputs and input
+    gradients of a row do not depend on which batch it is evaluated in) and linearity of the weight gradients."""
     from rec_now_amd.layers.ple_layer import PLELayer
     B, Din = 32768, 4096
     g = torch.Generator(device='cpu').manual_seed(14)
@@ -158,6 +159,20 @@ def test_ple_config5_per_rank_size(dev):
     xs = x[sub].to(dev).requires_grad_(True)
     souts = layer(xs)
     sum((o * gy[sub].to(dev)).sum() for o, gy in zip(souts, gys)).backward()
+    from _ple_oracle import oracle_layers, row_margin, torch_np
+    layers64, _ = oracle_layers(layer)
+    x64 = x[sub].double().requires_grad_(True)
+    routs = R.ple_layer(x64, layers64, layer.is_shared_tasks, activation='tanh')
+    sum((o * gy[sub].double()).sum() for o, gy in zip(routs, gys)).backward()
+    for t, (o, ro) in enumerate(zip(outs, routs)):
+        close(o[sub], ro)
+        m = row_margin(torch_np(ro), torch_np(o[sub]), RTOL)
+        print('ple config5: output %d of the full batch vs the fp64 oracle on rows 4096..4607: worst per-row margin %.3f of the bound' % (t, m))
+        assert m <= 1.0, (t, m)
+    close(xd.grad[sub], x64.grad)
+    m = row_margin(torch_np(x64.grad), torch_np(xd.grad[sub]), RTOL)
+    print('ple config5: dx of the full batch vs the fp64 oracle: worst per-row margin %.3f of the bound' % m)
+    assert m <= 1.0, m
     for o, so in zip(outs, souts):
         close(so, o[sub], rtol=5e-6)           # different batch sizes take different tile paths (summation order); tanh via exp2 / rcp
     close(xs.grad, xd.grad[sub], rtol=5e-6)
