@@ -254,8 +254,9 @@ extern "C" int recnow_cin_bwd(const float* const* weights_host, const float* dou
         // Data gradients.  Fused (csrc/cin_bwd.hip, round 4): T = dX_k W_k is formed ONCE on the matrix cores and both reductions -- over f with x0
         // for dX_{k-1}, over h with X_{k-1} for dx0 -- run on the accumulator tile: one forward-sized product instead of two.  Other shapes
         // (rows not a multiple of 128, H_{k-1} not 64 / 128, ...) keep the two products with generated outer-product operands.
-        if (rn_cin_bwd_fused_supported(c.M, Hk, Hp, F)) {
-            float* dst = (k == 0) ? dx0t : dXp;
+        float* const dprev = (k == 0) ? dx0t : dXp;
+        if (rn_cin_bwd_fused_ok(dXk, weights_host[k], x0t, dprev, dx0t, c.M, Hk, Hp, F)) {      // sizes and alignment: a misaligned W_k takes the two products
+            float* dst = dprev;
             if (k > 0) seed(dst, Hp, coffs[k - 1]);          // X_{k-1}'s own share of the output gradient, then accumulate
             if ((rc = rn_cin_bwd_fused(dXk, weights_host[k], x0t, Xp, dst, dx0t, c.M, Hk, Hp, F, st))) return rc;
         } else {

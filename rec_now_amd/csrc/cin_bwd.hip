@@ -242,12 +242,16 @@ bool rn_cin_bwd_fused_supported(int64_t M, int Hk, int Hp, int F) {
     return cb_lds_bytes(F) <= 160 * 1024;
 }
 
+bool rn_cin_bwd_fused_ok(const float* dXk, const float* W, const float* x0t, const float* dXp, const float* dx0t, int64_t M, int Hk, int Hp, int F) {
+    if (!rn_cin_bwd_fused_supported(M, Hk, Hp, F)) return false;
+    return (((uintptr_t)dXk | (uintptr_t)W | (uintptr_t)x0t | (uintptr_t)dXp | (uintptr_t)dx0t) & 15) == 0;
+}
+
 int rn_cin_bwd_fused(const float* dXk, const float* W, const float* x0t, const float* Xp, float* dXp, float* dx0t, int64_t M, int Hk, int Hp,
                      int F, hipStream_t st) {
-    if (!rn_cin_bwd_fused_supported(M, Hk, Hp, F)) return RECNOW_EUNSUPPORTED;
     if (!dXk || !W || !x0t || !Xp || !dXp || !dx0t) return RECNOW_EINVAL;
+    if (!rn_cin_bwd_fused_ok(dXk, W, x0t, dXp, dx0t, M, Hk, Hp, F)) return RECNOW_EUNSUPPORTED;
     if (dXp == dx0t && Hp != F) return RECNOW_EINVAL;
-    if ((((uintptr_t)dXk | (uintptr_t)W | (uintptr_t)x0t | (uintptr_t)dXp | (uintptr_t)dx0t) & 15) != 0) return RECNOW_EUNSUPPORTED;
     CinBwdK k;
     k.dXk = dXk; k.W = W; k.x0t = x0t; k.Xp = Xp; k.dXp = dXp; k.dx0t = dx0t; k.Hk = Hk; k.F = F;
     const size_t lds = cb_lds_bytes(F);
