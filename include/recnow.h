@@ -395,6 +395,12 @@ int recnow_dcn_step_bwd(const float* x0, const float* xl, const float* w, const 
  * The two D-sized contractions per layer run on the exact-fp32 MFMA GEMM with the gate logits folded in as extra
  * columns and the gate-weighted bias folded in as extra K rows; `saved` keeps the small (B x ~(N*S+N)) activations
  * and the layer inputs for backward.
+ * What `saved` holds depends on the route its forward took, and the note below records it: per layer T1 / T2 / T2g; the layer outputs x_{l+1}
+ * or (when they are not materialised) nothing in their place; O_l = T2g_l [W; b] per layer; the packed weights and their piece planes.  A fused-head
+ * forward in split-precision mode on the launch-per-product route ("head-Q", csrc/dcnmix.hip) takes the score as the row dot T2g_{L-1} . Q with
+ * Q = x (W_{L-1} * head_w)^T: it keeps Q (B x ~(N*S+N)) where x_1 would sit, writes NO O_{L-1}, and leaves the planes of [W; b]_{L-1} * head_w where
+ * those of [W; b]_{L-1} would be.  Its backward reads Q as the head's dT2g; one that cannot run the matching input-gradient form (precision flipped
+ * since) recomputes O_{L-1} first.  Sizes are the same on every route (tests/golden/dcn_mix_sizes.npz).
  *
  * Library state (the whole of it).
  *   - Process-wide settings: recnow_set_gemm_precision, recnow_set_gemm_staging, recnow_prof_* (one launching thread per process is the model).

@@ -153,7 +153,8 @@ static bool mix_tile_bwd_on(const MixDims& m) {
 // what it packed under the address of `saved` (host side: a stamp inside the device buffer could not be read back without a synchronisation); the
 // backward packs what is missing for the route it takes, and the lower pieces of a backward cut into layer ranges follow the top piece.  A buffer
 // this process has no record of (filled through another copy of the library, or 256 forwards ago) is "unknown": the backward then packs for itself.
-enum { MIX_HAS_PRODUCT_PACKS = 1, MIX_HAS_TILE_PACKS = 2, MIX_BWD_TILE = 4, MIX_HAS_SPLIT_PLANES = 8, MIX_PLANES_HEAD = 16, MIX_XLESS = 32 };      // (.._XLESS: the forward did not materialise x_{l+1})      // (.._HEAD: the top layer's P3 holds W * w_head)
+enum { MIX_HAS_PRODUCT_PACKS = 1, MIX_HAS_TILE_PACKS = 2, MIX_BWD_TILE = 4, MIX_HAS_SPLIT_PLANES = 8, MIX_PLANES_HEAD = 16, MIX_XLESS = 32, MIX_HEAD_Q = 64 };      // (.._XLESS: the forward did not materialise x_{l+1})      // (.._HEAD: the top layer's P3 holds W * w_head)
+// (.._HEAD_Q: the forward took the score from Q = x Wh^T -- mix_head_q below: `saved` holds Q, the top layer's P2 the planes of Wh, and NO O_{L-1})
 struct MixStamp { const void* sv; int bits; };
 static std::mutex g_mix_stamp_mu;
 static MixStamp g_mix_stamps[256];
@@ -209,12 +210,12 @@ __global__ void __launch_bounds__(256)
 k_pack_all(MixPackPtrs p, int L, int D, int S, int N, int LDT, float* __restrict__ Wc1, float* __restrict__ Wc2,
            const float* __restrict__ wh, float* __restrict__ Wh) {
     const int NS = N * S, KC = NS + N;
-    const int64_t per = (int64_t)D * LDT, packs = (int64_t)L * per * (Wc2 ? 2 : 1), total = packs + (Wh ? (int64_t)KC * D : 0);
+    const int64_t per = (int64_t)D * LDT, packs = (int64_t)L * per * (Wc2 ? 2 : 1), total = packs + (Wh ? per : 0);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        if (i >= packs) {                                // fused scoring head: Wh[k][c] = [W; b]_{L-1}[k][c] * w_head[c]
-            const int64_t e = i - packs;
+        if (i >= packs) {                                // fused scoring head: Wh[k][c] = [W; b; 0]_{L-1}[k][c] * w_head[c]  (LDT x D: the zero rows make it
+            const int64_t e = i - packs;                 // a K = KP operand, the second half of the head-Q input-gradient product)
             const int k = (int)(e / D), c = (int)(e % D);
-            Wh[e] = (k < NS ? p.W[L - 1][e] : p.b[L - 1][(int64_t)(k - NS) * D + c]) * wh[c];
+            Wh[e] = k < KC ? (k < NS ? p.W[L - 1][e] : p.b[L - 1][(int64_t)(k - NS) * D + c]) * wh[c] : 0.f;
             continue;
         }
         const int64_t j = i % ((int64_t)L * per);
@@ -241,7 +242,7 @@ static int pack_all(const MixDims& m, const float* const* U_host, const float* c
     for (int l = 0; l < m.L; ++l) {
         p.U[l] = U_host[l]; p.K[l] = gate_host[l]; p.W[l] = W_host[l]; p.b[l] = bias_host[l];
     }
-    const int64_t total = (int64_t)m.L * m.D * m.LDT * (Wc2_all ? 2 : 1) + (Wh ? (int64_t)m.KC * m.D : 0);
+    const int64_t total = (int64_t)m.L * m.D * m.LDT * (Wc2_all ? 2 : 1) + (Wh ? (int64_t)m.LDT * m.D : 0);
     int g = rn_cdiv(total, 256);
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(k_pack_all, g, 256, 0, st, p, m.L, m.D, m.S, m.N, m.LDT, Wc1_all, Wc2_all, head_w, head_w ? Wh : nullptr);
@@ -408,6 +409,35 @@ k_head_dx_top(const float* __restrict__ O, const float* __restrict__ ds, const f
         reinterpret_cast<float4*>(dx)[i] = make_float4(sc * w.x * o.x, sc * w.y * o.y, sc * w.z * o.z, sc * w.w * o.w);
     }
 }
+// Head-Q: with Wh = [W; b]_{L-1} * w_head and Q = x Wh^T (+ the two side columns x . (b_n * w_head)) -- the product the backward runs
+// anyway as the head's dT2g --
+//   score_r = sum_d x[r][d] w_d O_{L-1}[r][d] + b_head = sum_{k < KC} T2g_{L-1}[r][k] * Q[r][k] + b_head
+//   dscore (x) w_head * O_{L-1} = (dscore * T2g_{L-1}) Wh
+// so the top layer's output product, its (B, D) result O_{L-1} and the backward's read of it all go: the forward runs the Q product and a row dot of
+// two (B, LDT) tensors, the backward reads Q as its dT2g and forms the head's part of dx as the second K = KP half of layer 0's product.
+// k_head_rowdot: 16 lanes per row (four rows per wave), lane j takes the float4 groups j, j + 16, .. of the row in that order (elements x, y, z, w in
+// order), then the 16 partial sums are joined by a butterfly over lane distances 1, 2, 4, 8: a fixed order.  Columns >= KC are never read into the sum
+// (Q's are unwritten).  A zero row of x has Q = 0 exactly, so its score is b_head bit for bit.
+__global__ void __launch_bounds__(256)
+k_head_rowdot(const float* __restrict__ T2g, const float* __restrict__ Q, const float* __restrict__ bias, int64_t B, int KC, int LDT, float* __restrict__ scores) {
+    const int sub = threadIdx.x & 15;
+    const int64_t r = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    float s = 0.f;
+    if (r < B) {
+        for (int c = 4 * sub; c < KC; c += 64) {
+            const float4 t = *reinterpret_cast<const float4*>(T2g + r * LDT + c), q = *reinterpret_cast<const float4*>(Q + r * LDT + c);
+            s += t.x * q.x;
+            if (c + 1 < KC) s += t.y * q.y;
+            if (c + 2 < KC) s += t.z * q.z;
+            if (c + 3 < KC) s += t.w * q.w;
+        }
+    }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    s += __shfl_xor(s, 8, 64);
+    if (r < B && sub == 0) scores[r] = (bias ? bias[0] : 0.f) + s;
+}
 static inline int ew_grid(int64_t n) {
     int64_t g = (n + 255) / 256;
     if (g > 8192) g = 8192;
@@ -416,6 +446,11 @@ static inline int ew_grid(int64_t n) {
 // the fused head rides on the exact-128 formulation with the fused sub-space kernels
 static inline bool mix_head_ok(const MixDims& m) {
     return m.exact && rn_mix_mid_supported(m.S, m.N, m.LDT) && 2 * (m.D / 128) <= m.LDT && m.L <= MIX_PACK_MAX_L;
+}
+
+// The head-Q rule, read by the FORWARD; a backward follows the MIX_HEAD_Q stamp of `saved`.  planes_on: split precision, planes written by this call.
+static inline bool mix_head_q(const MixDims& m, bool head, bool planes_on, bool xless, bool need_dx) {
+    return head && planes_on && xless && mix_head_q_shape(m) && (!need_dx || ((m.L == 2 || m.L == 3) && m.KP == 144));
 }
 
 static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const float* const* V_host,
@@ -450,12 +485,15 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
     }
     // split precision: the piece planes of every layer's packed weights, one launch
     const bool planes_on = pack_product && rn_gemm_precision() == 1 && mix_planes_shape(m);
+    const bool xless = mix_xless(m);
+    const bool tile_split = !tile_fwd && mix_tile_split_on(m) && (y || head);
+    const bool head_q = !tile_fwd && !tile_split && mix_head_q(m, head != nullptr, planes_on, xless, need_dx != 0);
     if (planes_on) {
         RnSplitJobs jobs;
         jobs.n = 0;
         for (int l = 0; l < L; ++l) {
             jobs.job[jobs.n++] = RnSplitJob{sv.Wc1(l), m.LDT, 0, D, 128, sv.plane(l, 0)};
-            jobs.job[jobs.n++] = RnSplitJob{sv.Wc2(l), D, 0, m.KP, D, sv.plane(l, 1)};
+            jobs.job[jobs.n++] = RnSplitJob{(head_q && l == L - 1) ? sv.Wh() : sv.Wc2(l), D, 0, m.KP, D, sv.plane(l, 1)};      // (head-Q: no product leaves the top layer)
             jobs.job[jobs.n++] = RnSplitJob{(head && l == L - 1) ? sv.Wh() : W_host[l], D, 1, D, 128, sv.plane(l, 2)};
             jobs.job[jobs.n++] = RnSplitJob{sv.Wc1(l), m.LDT, 1, m.KP, D, sv.plane(l, 3)};
         }
@@ -464,11 +502,9 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
         rn_prof_end(pr_pl, st);
         if (rc) return rc;
     }
-    const bool xless = mix_xless(m);
     mix_stamp_put(saved, (pack_product ? MIX_HAS_PRODUCT_PACKS : 0) | (tile_fwd ? MIX_HAS_TILE_PACKS : 0) | (planes_on ? MIX_HAS_SPLIT_PLANES | (head ? MIX_PLANES_HEAD : 0) : 0) |
-                             (xless ? MIX_XLESS : 0));
+                             (xless ? MIX_XLESS : 0) | (head_q ? MIX_HEAD_Q : 0));
     const float* xl = x;
-    const bool tile_split = !tile_fwd && mix_tile_split_on(m) && (y || head);
     if (tile_fwd || tile_split) {       // every layer (+ the scoring head) in one launch of row-block workgroups
         RnTileFwd t;
         memset(&t, 0, sizeof(t));
@@ -551,6 +587,24 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, w.gws, w.gws_bytes, st, &sl, act_inner))) return rc;
             } else if ((rc = mix_mid_fwd(m, T1, V_host[l], T2, T2g, act_outer, w.gws, w.gws_bytes, st))) return rc;
             }      // (not the fused GEMM1)
+            }
+            if (head_q && l == L - 1) {      // no output product: Q = x Wh^T (the backward's dT2g of the head), score = T2g . Q + b_head
+                float* const Q = sv.Q();
+                recnow_gemm_desc d = rn_gemm_desc_zero();
+                d.A = x; d.lda = D; d.a_trans = 0;
+                d.B = sv.Wh(); d.ldb = D; d.b_trans = 1;
+                d.C = Q; d.ldc = m.LDT;
+                d.M = (int)B; d.N = m.NS; d.K = D;
+                d.prof_flops = 2.0 * (double)B * D * m.KC;
+                d.sp_bx = sv.Wh() + (size_t)m.NS * D; d.sp_bx_ks = 1; d.sp_bx_rs = D; d.sp_cx = Q + m.NS; d.sp_cx_ms = m.LDT; d.sp_cx_rs = 1; d.sp_r = N;
+                rn_gemm_planes_hint(sv.plane(l, 2));
+                if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;      // (not deferred: Q is complete before it is read)
+                RnProfRecord* pr_rd = rn_prof_on() ? rn_prof_begin(RN_TAG_LAYER_END, 2.0 * (double)B * m.KC, 8.0 * (double)B * m.LDT, st) : nullptr;
+                hipLaunchKernelGGL(k_head_rowdot, rn_cdiv(B, 16), 256, 0, st, T2g, Q, head->b, B, m.KC, m.LDT, head->scores);
+                RN_LAUNCH_CHECK();
+                rn_prof_end(pr_rd, st);
+                xl = out;
+                continue;
             }
             {   // GEMM3: out = x * ([G*H2 | G | 0] [W; b; 0]): K zero-padded NS+N -> KP (a 16-deep k-tile more is cheaper
                 // than a rank-N epilogue update: 215 vs 233 us measured)
@@ -845,6 +899,10 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     const int have = mix_stamp_get(saved);       // what the forward left in `saved` (-1: a forward this copy of the library did not see)
     bool want_tile = mix_tile_on(m) && mix_tile_bwd_on(m) && (l_hi < L - 1 || hd || dy);
     if (!top && have >= 0) want_tile = (have & MIX_BWD_TILE) != 0 && mix_tile_shape(m);      // a lower piece follows the top piece of its pass
+    // What the forward left decides, not the rule: a head-Q forward (MIX_HEAD_Q; an unknown buffer counts as not head-Q) wrote no O_{L-1}, which the
+    // row-block chain reads -- such a `saved` takes the product route, whatever RECNOW_TILE says by now.
+    const bool head_q = have >= 0 && (have & MIX_HEAD_Q) != 0 && hd != nullptr;
+    if (head_q) want_tile = false;
     if (want_tile) {
         if (top && !(have >= 0 && (have & MIX_HAS_TILE_PACKS))) {      // product-route forward (or unknown): the fragment-ordered packs are made here
             int rc0;
@@ -905,6 +963,20 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
     // the input gradient in one go (c2_mode 5 / 6 of the short-K kernel: two experts of 64, K = 144): fused head, 2 or 3 layers; other shapes take the
     // read-modify-write chain.  A pass cut into layer pieces decides the same way in every piece.
     const bool dx_once = hd && dx && (L == 2 || L == 3) && m.KP == 144;
+    // Head-Q `saved`: the top layer's dT2g is the forward's Q (no launch).  The head's part of dx, dscore (x) w_head * O_{L-1} = T2g_ds Wh, is the second
+    // K = KP half of layer 0's one-go product (c2_mode 7 / 8) where that form can run: split precision with the forward's planes current (the top
+    // layer's P2 = planes of Wh).  Otherwise (the precision flipped to exact fp32 since the forward, planes repacked, a shape without the one-go
+    // form) O_{L-1} = T2g_{L-1} [W; b] is recomputed into its free slot first -- one launch, by the piece that reads it -- and today's forms follow.
+    const bool dx_q = head_q && dx_once && planes_bwd && (have & MIX_PLANES_HEAD) != 0;
+    if (head_q && dx && !dx_q && (dx_once ? l_lo == 0 : top)) {
+        recnow_gemm_desc d = rn_gemm_desc_zero();
+        d.A = sv.T2g(L - 1); d.lda = m.LDT; d.a_trans = 0;
+        d.B = sv.Wc2(L - 1); d.ldb = D; d.b_trans = 0;
+        d.C = const_cast<float*>(sv.O(L - 1)); d.ldc = D;
+        d.M = (int)B; d.N = D; d.K = m.KP; d.k_valid = m.KC;
+        d.prof_flops = 2.0 * (double)B * D * m.KC;
+        if ((rc = rn_gemm(&d, gws, gemm_ws, st))) return rc;
+    }
     hipEvent_t e_g = nullptr;        // "g of this layer (and the packs) are ready" -> side stream may start the layer
     MIX_SIGNAL(e_g, st);
     hipEvent_t e_side_prev = nullptr;   // side stream finished the previous (higher) layer: dT1/dC/g buffers reusable
@@ -943,7 +1015,9 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
             if ((rc = side_dw())) return rc;
         }
         // ---------------- chain stream
-        {   // dT2g[:, :NS] = (x*g) W^T;  gate columns dT2g[:, NS+n] = (x*g) . bias_n as the side product
+        const bool q_top = head_q && l == L - 1;        // the forward left this layer's dT2g (before the row scale by dscore) as Q
+        const float* const dT2g_in = q_top ? sv.Q() : dT2g;
+        if (!q_top) {   // dT2g[:, :NS] = (x*g) W^T;  gate columns dT2g[:, NS+n] = (x*g) . bias_n as the side product
             recnow_gemm_desc d = rn_gemm_desc_zero();
             d.A = g; d.A2 = x; d.a_mode = RECNOW_OPMODE_MUL; d.lda = D; d.a_trans = 0;
             d.B = W_host[l]; d.ldb = D; d.b_trans = 1;
@@ -976,7 +1050,7 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
         MIX_WAIT(e_side_prev, st);          // dT1 (and the g buffer about to be rewritten) are free again
         // gate backward, dA_n = (dC_n V_n^T) * act_inner'(H1_n) and dV_n = H1_n^T dC_n
         if (hd && l == L - 1) {
-            if ((rc = rn_mix_mid_bwd(dT2g, T2, T1, V_host[l], dT1, dV_host[l], B, S, N, m.LDT, act_inner, act_outer, w.mid_ws, w.mid_ws_bytes, st, hd->dscores,
+            if ((rc = rn_mix_mid_bwd(dT2g_in, T2, T1, V_host[l], dT1, dV_host[l], B, S, N, m.LDT, act_inner, act_outer, w.mid_ws, w.mid_ws_bytes, st, hd->dscores,
                                      defer_dv, slp)))
                 return rc;
         } else if (defer_dv) {
@@ -996,7 +1070,22 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
             d.M = (int)B; d.N = D; d.K = m.KP; d.k_valid = m.KC;
             d.prof_flops = 2.0 * (double)B * D * m.KC;
             d.accumulate = (l == 0) ? 1 : 0;
-            if (dx_once) {
+            bool launched = false;
+            if (dx_once && dx_q) {
+                // head-Q: d loss / d x = [dT1_0 | T2g_ds] [[U_0 | K_0]^T ; Wh] + g_1 * O_0 [+ g_2 * O_1] in one K = 2 KP product (c2_mode 7 / 8, gemm_shortk.hip
+                // states the summation order); T2g_ds = dscore * T2g_{L-1} is the loss stage's (or the top piece's, in dC: nothing on this route writes dC
+                // after that) and is only read until then
+                if (l == 0) {
+                    RnDxOnce q;
+                    q.A_lo = dT1; q.A_hi = T2g_ds_ready ? T2g_ds_ready : dC; q.lda = m.LDT;      // (a lower piece of a cut pass did not run the head's block above)
+                    q.planes_lo = sv.plane(0, 3); q.planes_hi = sv.plane(L - 1, 1);
+                    q.E2 = gbuf0; q.E3 = sv.O(0);
+                    q.E4 = (L == 3) ? gbuf1 : nullptr; q.E5 = (L == 3) ? sv.O(1) : nullptr;
+                    q.C = dx; q.ld = D; q.M = (int)B; q.N = D;
+                    if ((rc = rn_gemm_dx_once_split(q, st))) return rc;
+                    launched = true;
+                }
+            } else if (dx_once) {
                 // Round 5: d loss / d x = g_0 + g_1 * O_0 [+ g_2 * O_1] + dscore (x) w_head * O_{L-1} is written ONCE, by layer 0's product (c2_mode 5 / 6):
                 // the products of the layers above leave g_l alone (1 pass over B x D each instead of 4), layer 0's reads g_1, O_0, g_2, O_1, O_{L-1}
                 // and writes dx (6 instead of 2): 8 passes per step where the read-modify-write chain took 10.  g_1 / g_2 sit in the two ping-pong
@@ -1015,8 +1104,10 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
                 d.E3 = sv.O(l); d.lde3 = D; d.rv = hd->dscores; d.cv = hd->w;
             }
             }
-            if (planes_bwd) rn_gemm_planes_hint(sv.plane(l, 3));
-            if ((rc = rn_gemm(&d, gws, gemm_ws, st))) return rc;
+            if (!launched) {
+                if (planes_bwd) rn_gemm_planes_hint(sv.plane(l, 3));
+                if ((rc = rn_gemm(&d, gws, gemm_ws, st))) return rc;
+            }
         }
         if (l > 0) MIX_SIGNAL(e_g, st);
         // ---------------- side stream, part 2: needs dC / dT1 of this layer

@@ -56,16 +56,19 @@ static inline bool mix_planes_shape(const MixDims& m) { return m.exact && m.L <=
 
 // `saved`, in this order (a region a shape does not have is empty):
 //   per layer T1 | T2 | T2g                (B, LDT) each
-//   x_1 .. x_{L-1}                         (B, D) layer outputs between the layers
+//   x_1 .. x_{L-1}                         (B, D) layer outputs between the layers.  A forward that does not materialise them (mix_xless) leaves the region
+//                                          unused; the head-Q forward (dcnmix.hip: mix_head_q) keeps Q = x Wh^T (B, LDT) at its start, see Q()
 //   O_0 .. O_{L-1}                         (B, D), exact path: O_l = T2g_l [W; b] is kept next to x_{l+1} = x * O_l (second output of GEMM3), so the
-//                                          backward forms dx = sum_l g_l * O_l inside kernels that stream g_l anyway instead of recomputing the products
+//                                          backward forms dx = sum_l g_l * O_l inside kernels that stream g_l anyway instead of recomputing the products.
+//                                          Head-Q forward: O_{L-1} is NOT written (its slot stays free: a backward that needs it recomputes it there)
 //   Wc1_0 .. Wc1_{L-1}                     [U_l | K_l | 0] (D x LDT), exact path and L <= MIX_PACK_MAX_L, as are the next two
 //   Wc2_0 .. Wc2_{L-1}                     [W_l; b_l; 0] (LDT x D)
 //   Wh                                     (LDT x D) the fused head's pre-scaled top-layer weights [W; b]_{L-1} * w_head
 //   tile packs                             mix_tile_shape: fragment-ordered weights of the row-block kernels (rn_mix_tile_pack_bytes)
 //   per layer P1 | P2 | P3 | P4            mix_planes_shape: piece planes of [U | K] as the B operand of GEMM1, of [W; b] of the product that leaves
 //                                          the layer, of W^T -- or the fused head's W * w_head -- of the dT2g product, of [U | K]^T of the product that
-//                                          forms g_{l-1}
+//                                          forms g_{l-1}.  Head-Q forward: the top layer has no product that leaves it, its P2 holds the (KP x D) planes
+//                                          of Wh instead (the second half of the K = 288 input-gradient product)
 //   tile split planes                      mix_tile_shape: piece planes of the split-precision row-block forward (dcnmix_tile_split.hip)
 // F = float: the forward's view; F = const float: the backward's (where it packs for itself what its forward left out, the const_cast says so).
 template <typename F>
@@ -94,6 +97,7 @@ struct MixSavedT {
     F* T2(int l) const { return (F*)(base + (size_t)(3 * l + 1) * act); }
     F* T2g(int l) const { return (F*)(base + (size_t)(3 * l + 2) * act); }
     F* x_next(int l) const { return (F*)(base + x_off + (size_t)l * xb); }      // x_{l+1}, l < L - 1
+    F* Q() const { return x_next(0); }      // head-Q: (B, LDT), aliases x_1 -- only under mix_xless, L > 1 and LDT <= D (mix_head_q_shape)
     F* O(int l) const { return (F*)(base + o_off + (size_t)l * xb); }
     F* Wc1(int l) const { return (F*)(base + pack_off + (size_t)l * pack); }
     F* Wc2(int l) const { return (F*)(base + pack_off + (size_t)(L + l) * pack); }
@@ -104,6 +108,8 @@ struct MixSavedT {
     }
     Byte* tile_split_planes() const { return base + tile_split_off; }
 };
+// shapes whose fused-head forward may take the score from Q = x Wh^T (dcnmix.hip: mix_head_q): the planes, and room for Q in the x_1 slot
+static inline bool mix_head_q_shape(const MixDims& m) { return mix_planes_shape(m) && m.L > 1 && act_block(m) <= xbuf(m); }
 typedef MixSavedT<float> MixSaved;
 typedef MixSavedT<const float> MixSavedC;
 

@@ -272,6 +272,7 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
             return RECNOW_EUNSUPPORTED;
     }
     k.E4 = d->E4; k.E5 = d->E5; k.E6 = d->E6;
+    k.A_hi = nullptr; k.planes_hi = nullptr;      // (rn_gemm_dx_once_split only)
     if (d->c2_mode == 3 && (!d->hv || !d->hp || !d->emul || d->hp_ld < d->N / 64 || ((uintptr_t)d->hv & 15))) return RECNOW_EINVAL;
     if (d->c2_mode == 4 && (!d->E3 || !d->rv || !d->cv || ((uintptr_t)d->cv & 15) || !host_aligned(d->E3, d->lde3, 0))) return RECNOW_EINVAL;
     k.E3 = d->E3; k.lde3 = d->lde3; k.rv = d->rv; k.cv = d->cv; k.hv = d->hv; k.hp = d->hp; k.hp_ld = d->hp_ld;
@@ -416,6 +417,31 @@ int rn_gemm(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st
 int rn_gemm_deferred(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* out) {
     if (!out) return RECNOW_EINVAL;
     return rn_gemm_impl(d, ws, ws_bytes, st, out);
+}
+// c2_mode 7 / 8 of the short-K kernel (gemm.hpp: RnDxOnce).  The caller owns the shape rules; what a wrong call could turn into an access out of
+// bounds or a misaligned 16-byte access is checked here.
+int rn_gemm_dx_once_split(const RnDxOnce& q, hipStream_t st) {
+    if (!q.A_lo || !q.A_hi || !q.planes_lo || !q.planes_hi || !q.E2 || !q.E3 || !q.C || (q.E4 != nullptr) != (q.E5 != nullptr)) return RECNOW_EINVAL;
+    if (q.M <= 0 || q.N <= 0 || q.M % 128 || q.N % 128 || q.lda < 144 || q.ld < q.N || (int64_t)128 * q.lda >= (1ll << 29) || (int64_t)128 * q.ld >= (1ll << 29))
+        return RECNOW_EUNSUPPORTED;
+    if (!host_aligned(q.A_lo, q.lda, 0) || !host_aligned(q.A_hi, q.lda, 0) || !host_aligned(q.C, q.ld, 0) || !host_aligned(q.E2, q.ld, 0) ||
+        !host_aligned(q.E3, q.ld, 0) || (q.E4 && (!host_aligned(q.E4, q.ld, 0) || !host_aligned(q.E5, q.ld, 0))) || ((uintptr_t)q.planes_lo & 15) ||
+        ((uintptr_t)q.planes_hi & 15))
+        return RECNOW_EUNSUPPORTED;
+    GemmK k;
+    memset(&k, 0, sizeof(k));
+    k.A = q.A_lo; k.A_hi = q.A_hi; k.lda = q.lda; k.planes_hi = (const char*)q.planes_hi;
+    k.C = q.C; k.ldc = q.ld;
+    k.E2 = q.E2; k.E3 = q.E3; k.E4 = q.E4; k.E5 = q.E5; k.lde2 = k.lde3 = q.ld;
+    k.M = q.M; k.N = q.N; k.K = 288; k.batch = 1; k.splitk = 1; k.kchunk = 288; k.tail_pairs = 8; k.direct_store = 1;
+    RnProfRecord* pr = nullptr;
+    if (rn_prof_on()) {      // algorithmic HBM bytes: both A halves and the planes read once, 2 / 4 (M, N) tensors read, C written
+        const double mn = (double)q.M * q.N;
+        pr = rn_prof_begin(RN_TAG_GEMM_SHORTK, 2.0 * mn * 288.0, 4.0 * (2.0 * q.M * 144.0 + 2.0 * 144.0 * q.N + mn * (q.E4 ? 5 : 3)), st);
+    }
+    const int rc = rn_gemm_launch_shortk_split2(k, q.E4 ? 7 : 8, q.planes_lo, st);
+    rn_prof_end(pr, st);
+    return rc;
 }
 void rn_deferred_slabs(const RnDeferredReduce* r, const float** partial, int* nsplit, int* ld, int64_t* stride) {
     GemmK k;

@@ -38,6 +38,19 @@ size_t rn_gemm_split_planes_bytes(int K, int N);
 // split would write) and skips that split; consumed (or dropped) by that one call.
 void rn_gemm_planes_hint(const void* planes);
 
+// The input gradient of a fused-head DCN-v2 step in one go, split precision only (c2_mode 7 / 8 of the short-K kernel, gemm_shortk.hip):
+//   C = [A_lo | A_hi] @ [B_lo ; B_hi] + E2 * E3 [+ E4 * E5]        (M x N; E4 == NULL: without the bracket)
+// A_lo, A_hi: (M, 144) with the leading dimension lda; planes_lo, planes_hi: piece planes of B_lo, B_hi (144 x N each, rn_split_planes_multi);
+// E2 .. E5 and C: (M, N) with the leading dimension ld.  M, N multiples of 128, everything 16-byte aligned.  Internal: recnow_gemm_desc has no such form.
+struct RnDxOnce {
+    const float *A_lo, *A_hi; int64_t lda;
+    const void *planes_lo, *planes_hi;
+    const float *E2, *E3, *E4, *E5;
+    float* C; int64_t ld;
+    int M, N;
+};
+int rn_gemm_dx_once_split(const RnDxOnce& q, hipStream_t st);
+
 static inline recnow_gemm_desc rn_gemm_desc_zero() {
     recnow_gemm_desc d;
     memset(&d, 0, sizeof(d));

@@ -46,6 +46,8 @@ struct GemmK {
     const float* E3;           // c2_mode 4: third epilogue tensor (leading dimension lde3)
     int64_t lde3;
     const float *E4, *E5, *E6; // c2_mode 5 / 6: C = acc + E2 * E3 [+ E4 * E5] + rv (x) cv * E6 (all with the leading dimension lde2)
+    const float* A_hi;         // c2_mode 7 / 8 (K = 288 as two K = 144 halves, rn_gemm_dx_once_split): A of k-tiles 9 .. 17 (leading dimension lda)
+    const char* planes_hi;     //   ... and the piece planes of their B operand; C = acc + E2 * E3 [+ E4 * E5] (8: without the bracket)
     const float *rv, *cv;      // c2_mode 4: row / column vectors of the rank-one factor
     const float* hv;           // c2_mode 3: column vector of the fused row-dot (the scoring head's kernel)
     float* hp;                 // c2_mode 3: partials hp[m][hp_ld], entry 2 * column tile + wave column
@@ -1067,6 +1069,8 @@ int rn_gemm_launch_split(const GemmK& k, bool a_kc, bool b_kc, int a2k, void* pl
 size_t rn_gemm_split_planes_bytes(int K, int N);
 int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, void* planes, hipStream_t st, const void* ready = nullptr);
 size_t rn_gemm_shortk_planes_bytes(int K, int N);
+// K = 288 as two K = 144 halves (k.A / planes_lo, k.A_hi / k.planes_hi); c2_mode 7 / 8
+int rn_gemm_launch_shortk_split2(const GemmK& k, int c2_mode, const void* planes_lo, hipStream_t st);
 // persistent short-K kernel (gemm_shortk.hip): ep = (emul ? 1 : 0) | (accumulate ? 2 : 0)
 int rn_gemm_launch_shortk(const GemmK& k, bool b_kc, int ep, int c2_mode, hipStream_t st);
 

@@ -26,6 +26,11 @@
 // 5 / 6 (round 5: the input gradient accumulated ONCE, by the last product of the backward pass): C = acc + E2 * E3 [+ E4 * E5] + rv[m] * cv[n] * E6
 //   (6: without the bracket); three / five (B, D) tensors read once, C written once.  Their epilogue moves in HALF sub-tiles (16 rows): two
 //   register sets of 2 x 5 float4 instead of 4 x 5 per set, the loads of half s + 1 requested before half s is combined and stored.
+// 7 / 8 (the fused head's score taken from Q = x Wh^T): the one-go input gradient WITHOUT the rank-one term -- dscore (x) w_head * O_{L-1} =
+//   (dscore * T2g_{L-1}) Wh is a second K = 144 product instead: NK = 18, k-tiles 0 .. 8 take A from p.A and B from b_planes, k-tiles 9 .. 17 from
+//   p.A_hi and p.planes_hi (the k-loop is unrolled: the choice is made at compile time per k-tile).  C = acc + E2 * E3 [+ E4 * E5] (8: without the
+//   bracket); split precision only.  Summation order: the accumulators take k-tiles 0 .. 17 in order (first the 144 terms of A, then those of A_hi;
+//   inside a k-tile the six piece products in the order of SKS_TERM below), then t = E4 * E5, t = E2 * E3 + t, C = t + acc.
 // Workgroups per CU (= waves per SIMD): the epilogue's operand registers set it.  These products are HBM-bound, three or two
 // co-resident workgroups still cover each other's epilogues; spilling the epilogue operands to scratch does not.
 // PRE: the whole tile of `emul` (64 registers per lane) is requested BEFORE the tile's k-loop, so it lands under the MFMAs and the
@@ -83,7 +88,12 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
     const int nk = p.K / SK_BK;
     const int ntiles = row_tiles * col_tiles;
     constexpr bool EARLY = NK >= 3 && ((EP && !PRE) || DUAL == 2 || DUAL == 4);       // ring schedule with epilogue loads
-    constexpr bool ONCE = DUAL == 5 || DUAL == 6;                                     // C = acc + E2 * E3 [+ E4 * E5] + rv (x) cv * E6
+    constexpr bool ONCE = DUAL >= 5 && DUAL <= 8;                                     // C = acc + E2 * E3 [+ E4 * E5] [+ rv (x) cv * E6]
+    constexpr bool ONCE_RV = DUAL == 5 || DUAL == 6;                                  // ... with the rank-one term (E6, rv, cv)
+    constexpr bool ONCE_E45 = DUAL == 5 || DUAL == 7;                                 // ... with the bracket
+    constexpr bool K2 = DUAL == 7 || DUAL == 8;                                       // two K = 144 halves: the second from p.A_hi / p.planes_hi
+    static_assert(!K2 || (SPL && NK == 18), "c2_mode 7 / 8: split precision, 18 k-tiles");
+    static_assert(NK != 18 || K2, "18 k-tiles: c2_mode 7 / 8 only");
     static_assert(!ONCE || (EP == 0 && NK >= 3), "the one-go input gradient: ring schedule, no emul / accumulate");
 
     // slot (= workgroup index + round * grid) -> tile.  XCD-aware: slots of one XCD enumerate (row tile, column tile) with
@@ -123,8 +133,11 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
     const int sfb_off = SPL_OPER + ((lane >> 5) * SPL_PLANE_H + wn * 64 + (lane & 31)) * 16;
     auto ring_load = [&](int set, int mm, int nn, int k0) {
         if constexpr (SPL) {
-            const char* __restrict__ pa = reinterpret_cast<const char*>(p.A + (int64_t)mm * p.lda + k0);
-            const char* __restrict__ pb = b_planes + ((int64_t)(k0 >> 3) * p.N + nn) * 16;
+            // (k0 is a constant behind the unrolled k-loop: no branch is left)
+            const bool hi = K2 && k0 >= 9 * SK_BK;
+            const int kh = hi ? k0 - 9 * SK_BK : k0;
+            const char* __restrict__ pa = reinterpret_cast<const char*>((hi ? p.A_hi : p.A) + (int64_t)mm * p.lda + kh);
+            const char* __restrict__ pb = (hi ? p.planes_hi : b_planes) + ((int64_t)(kh >> 3) * p.N + nn) * 16;
             asm volatile("" : "+v"(sa_bo));
             ra[set][0] = *reinterpret_cast<const f32x4*>(pa + sa_bo);
             ra[set][1] = *reinterpret_cast<const f32x4*>(pa + sa_bo + 16);
@@ -332,9 +345,9 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
         float r5[ONCE ? 2 : 1][2];
         const float* F1t = ONCE ? p.E2 + (int64_t)m0 * p.lde2 + n0 : nullptr;
         const float* G1t = ONCE ? p.E3 + (int64_t)m0 * p.lde2 + n0 : nullptr;
-        const float* F2t = DUAL == 5 ? p.E4 + (int64_t)m0 * p.lde2 + n0 : nullptr;
-        const float* G2t = DUAL == 5 ? p.E5 + (int64_t)m0 * p.lde2 + n0 : nullptr;
-        const float* H6t = ONCE ? p.E6 + (int64_t)m0 * p.lde2 + n0 : nullptr;
+        const float* F2t = ONCE_E45 ? p.E4 + (int64_t)m0 * p.lde2 + n0 : nullptr;
+        const float* G2t = ONCE_E45 ? p.E5 + (int64_t)m0 * p.lde2 + n0 : nullptr;
+        const float* H6t = ONCE_RV ? p.E6 + (int64_t)m0 * p.lde2 + n0 : nullptr;
         auto issue5 = [&](int step, int buf) {
             const int s2 = step >> 1, h = step & 1, i = s2 >> 1, j = s2 & 1;
 #pragma unroll
@@ -342,12 +355,14 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
                 const int64_t off = (int64_t)(i * 32 + 16 * h + q * 8) * p.lde2 + j * 32 + f_lane;
                 o5[ONCE ? buf : 0][0][q] = SK_LDS4(F1t + off);
                 o5[ONCE ? buf : 0][1][q] = SK_LDS4(G1t + off);
-                if (DUAL == 5) {
+                if (ONCE_E45) {
                     o5[ONCE ? buf : 0][2][q] = SK_LDS4(F2t + off);
                     o5[ONCE ? buf : 0][3][q] = SK_LDS4(G2t + off);
                 }
-                o5[ONCE ? buf : 0][4][q] = SK_LDS4(H6t + off);
-                r5[ONCE ? buf : 0][q] = p.rv[m0 + wm * 64 + i * 32 + 16 * h + q * 8 + rr0];
+                if (ONCE_RV) {
+                    o5[ONCE ? buf : 0][4][q] = SK_LDS4(H6t + off);
+                    r5[ONCE ? buf : 0][q] = p.rv[m0 + wm * 64 + i * 32 + 16 * h + q * 8 + rr0];
+                }
             }
         };
         if (NK) {
@@ -399,7 +414,7 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
         // buffer `fr` was consumed by the last k-tile and is free: staging space of the epilogue (16 rows x 36 per wave)
         const int fr = (f + nk - 1) & 1;
         float* stg = smem + fr * BUF + wave * (16 * 36);
-        if (DUAL == 3 || DUAL == 4 || ONCE) {
+        if (DUAL == 3 || DUAL == 4 || ONCE_RV) {
             const float* colv = (DUAL == 3 ? p.hv : p.cv) + n0 + wn * 64 + cc;
             hv4[0] = *reinterpret_cast<const f32x4*>(colv);
             hv4[1] = *reinterpret_cast<const f32x4*>(colv + 32);
@@ -422,9 +437,18 @@ k_gemm_shortk(const GemmK p, int row_tiles, int col_tiles, int xcd_aware, const 
                     f32x4 v = a;
                     if (ONCE) {
                         // the order of the former three launches: (g_2 * O_1 + (w_head * ds) * O_2) + g_1 * O_0, then + g_0
-                        f32x4 t = (hv4[j] * r5[ONCE ? h : 0][q]) * o5[ONCE ? h : 0][4][q];
-                        if (DUAL == 5) t = o5[ONCE ? h : 0][2][q] * o5[ONCE ? h : 0][3][q] + t;
-                        t = o5[ONCE ? h : 0][0][q] * o5[ONCE ? h : 0][1][q] + t;
+                        // (c2_mode 7 / 8: the head's term is part of acc; g_2 * O_1 + g_1 * O_0, then + acc)
+                        f32x4 t;
+                        if (ONCE_RV) {
+                            t = (hv4[j] * r5[ONCE ? h : 0][q]) * o5[ONCE ? h : 0][4][q];
+                            if (ONCE_E45) t = o5[ONCE ? h : 0][2][q] * o5[ONCE ? h : 0][3][q] + t;
+                            t = o5[ONCE ? h : 0][0][q] * o5[ONCE ? h : 0][1][q] + t;
+                        } else if (ONCE_E45) {
+                            t = o5[ONCE ? h : 0][2][q] * o5[ONCE ? h : 0][3][q];
+                            t = o5[ONCE ? h : 0][0][q] * o5[ONCE ? h : 0][1][q] + t;
+                        } else {
+                            t = o5[ONCE ? h : 0][0][q] * o5[ONCE ? h : 0][1][q];
+                        }
                         v = t + a;
                     }
                     if (EP & 1) v = v * (PRE ? evt[PRE ? s2 : 0][2 * h + q] : ev[buf][2 * h + q]);
@@ -478,7 +502,7 @@ static int launch_sk(const GemmK& k, hipStream_t st, const char* planes = nullpt
     const int xcd = (rt % 8 == 0 && grid % 8 == 0) ? 1 : 0;
     GemmK kk = k;
     kk.prio = 1;
-    const int64_t pb = (int64_t)(k.K / 8) * k.N * 16;
+    const int64_t pb = (int64_t)((NK == 18 ? k.K / 2 : k.K) / 8) * k.N * 16;      // (18 k-tiles: two plane sets of K / 2 each)
     hipLaunchKernelGGL((k_gemm_shortk<B_KC, EP, DUAL, PRE, NK, SPL>), grid, GEMM_THREADS, lds, st, kk, rt, ct, xcd, planes, pb);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
@@ -511,6 +535,13 @@ int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, 
     if (c2_mode == 5) return launch_sk<true, 0, 5, false, 9, true>(k, st, pl);
     if (c2_mode == 6) return launch_sk<true, 0, 6, false, 9, true>(k, st, pl);
     return launch_sk<true, 0, 0, false, 9, true>(k, st, pl);
+}
+
+int rn_gemm_launch_shortk_split2(const GemmK& k, int c2_mode, const void* planes_lo, hipStream_t st) {
+    if (k.K != 18 * SK_BK || !planes_lo || !k.planes_hi || !k.A_hi || (int64_t)128 * k.lda >= (1ll << 29)) return RECNOW_EUNSUPPORTED;
+    if (c2_mode == 7) return launch_sk<true, 0, 7, false, 18, true>(k, st, (const char*)planes_lo);
+    if (c2_mode == 8) return launch_sk<true, 0, 8, false, 18, true>(k, st, (const char*)planes_lo);
+    return RECNOW_EUNSUPPORTED;
 }
 
 // ep: bit 0 = multiply by emul, bit 1 = accumulate into C.  c2_mode: second output (recnow_gemm_desc).  The caller
