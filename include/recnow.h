@@ -43,6 +43,9 @@ extern "C" {
 #define RECNOW_KEY_F64 1
 #define RECNOW_KEY_I32 2
 #define RECNOW_KEY_I64 3
+/* OR-ed into one of the four above: float ids compare as tf.unique does (listwise_loss_from_batch.py:109) -- equal infinities are
+ * one group, only NaN rows are solo.  Without it they follow `g_i - g_j == 0.0` of the pairwise loss: +-inf pair with nobody. */
+#define RECNOW_KEY_INF_EQUAL 256
 
 /* pair predicate flags */
 #define RECNOW_PAIR_LABEL_GT 1    /* keep (i,j) only if label_i > label_j   (pairwise_loss_from_batch.py:189)     */
@@ -57,11 +60,12 @@ int recnow_abi_version(void);
  * and tf.unique_with_counts of listwise_loss_from_batch.py:109 by canonical keys + stable radix sort + segments.
  * ---------------------------------------------------------------------------------------------------------- */
 
-/* Number of 32-bit key words one group tensor of `dtype` contributes (1 or 2); <0 on bad dtype. */
+/* Number of 32-bit key words one group tensor of `dtype` (with or without RECNOW_KEY_INF_EQUAL) contributes (1 or 2); <0 on bad dtype. */
 int recnow_key_words(int dtype);
 
 /* Canonicalise one group-id tensor into key words.  Float semantics follow `g_i - g_j == 0.0`
  * (pairwise_loss_from_batch.py:33-35): -0.0 == +0.0; NaN and +-inf rows pair with nobody -> solo[i] |= 1.
+ * dtype | RECNOW_KEY_INF_EQUAL: tf.unique equality instead -- only NaN rows are solo, all +inf rows are one group, all -inf rows another.
  * words: [recnow_key_words(dtype)][B] (word-major, most significant word first).  solo: [B], OR-accumulated. */
 int recnow_group_keys(const void* group, int dtype, int64_t B, uint32_t* words, uint8_t* solo, void* stream);
 
@@ -171,24 +175,28 @@ int recnow_occurance_power_weight(const int32_t* order, const int32_t* seg_id, c
 
 /* ------------------------------------------------------------------------------------------------------------
  * In-batch listwise loss: rec_now/rec_block/listwise_loss_from_batch.py:89-173 on sorted segments (no (G,B) matrix).
- *   valid group g: has a label > th and a (label - th) < 0 (:135-137);  p_i = y_i / sum_g y (:144)
+ *   lists: the rows tf.unique (:109) finds equal -- -0.0 == +0.0, equal infinities equal, every NaN alone (RECNOW_KEY_INF_EQUAL)
+ *   valid group g: has a label > th and a (label - th) < 0 (:135-137), both over the PADDED row of the reference's (G,B) matrix:
+ *       with th < 0 the zero labels of the padding make every list shorter than the batch one with a positive;  p_i = y_i / sum_g y (:144)
  *   row g of the reference's dense logits = members' logits + (B - n_g) entries equal to pad_logit
  *       (pad_logit = value_of_masked_logit when do_mask_logits, else 0; :139-140)
  *   l_g = lse(row g) * sum_i p_i - sum_i p_i s_i (:167);  loss = mean over valid groups of w_g l_g, NaN -> 0 (:168-172)
  * Segment arrays are sized B and indexed by segment; valid_rank[g] = index of g among the valid groups in
- * FIRST-OCCURRENCE order (the row order of the reference's outputs, tf.unique :109) or -1.
+ * FIRST-OCCURRENCE order (the row order of the reference's outputs, tf.unique :109) or -1.  The per-list sums (seg_lse, seg_ysum,
+ * seg_psum, seg_pdot) are fp64: a row's gradient softmax_i * psum - p_i cancels where a list's one positive is its top logit, and
+ * an fp32 log-sum-exp leaves such lists 1e-5 .. 1e-4 off relative to their own largest entry.
  * ---------------------------------------------------------------------------------------------------------- */
 size_t recnow_listwise_workspace_bytes(int64_t B);
 int recnow_listwise_segments(const float* labels, const float* logits, const int32_t* order, const int32_t* seg_first,
                              const int32_t* n_seg, int64_t B, float pos_neg_th, float pad_logit, int32_t* seg_valid,
-                             float* seg_lse, float* seg_ysum, float* seg_psum, float* seg_pdot, int32_t* valid_rank,
+                             double* seg_lse, double* seg_ysum, double* seg_psum, double* seg_pdot, int32_t* valid_rank,
                              int32_t* n_valid, void* ws, size_t ws_bytes, void* stream);
 /* loss [1]; dbase[i] = w_g * (softmax_i * psum_g - p_i) (0 outside valid groups): d loss/d logits = dbase / n_valid
  * (do_reduce) or dbase * upstream[row_rank] (per-list losses);  row_rank[i] = valid rank of i's group or -1;
  * group_loss[r] = weighted loss of the r-th valid list.  weights: [n_valid] or NULL. */
 int recnow_listwise_loss_fwdbwd(const float* labels, const float* logits, const int32_t* order, const int32_t* seg_id,
-                                const int32_t* seg_first, const int32_t* seg_valid, const float* seg_lse,
-                                const float* seg_ysum, const float* seg_psum, const float* seg_pdot,
+                                const int32_t* seg_first, const int32_t* seg_valid, const double* seg_lse,
+                                const double* seg_ysum, const double* seg_psum, const double* seg_pdot,
                                 const int32_t* valid_rank, const int32_t* n_valid, const float* weights, int64_t B,
                                 float* loss, float* dbase, int32_t* row_rank, float* group_loss, void* stream);
 /* to_listwise_sample + listwise_loss_via_softmax_cross_entropy_with_logits(do_reduce=True) fused on sorted segments, as ONE call
@@ -196,14 +204,14 @@ int recnow_listwise_loss_fwdbwd(const float* labels, const float* logits, const 
  * the valid lists (0 when there is none: nan_to_zero) and  dlogits[i] = d loss / d logits[i]  (already divided by the number of valid
  * lists), so that a host framework's backward is one multiply.  out2 (2 floats): {loss, (float) number of valid lists}.
  * weights: [>= number of valid lists] in first-occurrence order of the valid groups, or NULL.  One workspace
- * (recnow_listwise_loss_workspace_bytes) holds every intermediate. */
+ * (recnow_listwise_loss_workspace_bytes) holds every intermediate.  key_dtype: RECNOW_KEY_INF_EQUAL is accepted and implied. */
 size_t recnow_listwise_loss_workspace_bytes(int64_t B, int key_dtype);
 int recnow_listwise_loss(const void* groups, int key_dtype, const float* labels, const float* logits, const float* weights, int64_t B,
                          float pos_neg_th, float pad_logit, float* out2, float* dlogits, void* ws, size_t ws_bytes, void* stream);
 /* Dense (n_valid,B) outputs of to_listwise_sample (:131-148) for API parity.  The caller pre-fills mask_out = 0,
  * labels_out = 0, logits_out = pad_logit; members of valid groups are scattered in. */
 int recnow_listwise_dense(const float* labels, const float* logits, const int32_t* order, const int32_t* seg_id,
-                          const float* seg_ysum, const int32_t* valid_rank, int64_t B, uint8_t* mask_out,
+                          const double* seg_ysum, const int32_t* valid_rank, int64_t B, uint8_t* mask_out,
                           float* labels_out, float* logits_out, void* stream);
 int recnow_listwise_dense_bwd(const float* ddense, const int32_t* row_rank, int64_t B, float* dlogits, void* stream);
 /* tf.nn.softmax_cross_entropy_with_logits over the rows of dense (G,N) matrices (:167): row_loss = lse*sum(p) - p.s;

@@ -11,5 +11,7 @@
 // recnow_slot_pool_fwd / _pool_bwd (fetch_single_slot, embedding_single_slot, pool_slots); 12: recnow_reduce_axis_fwd / _bwd / _workspace_bytes, recnow_pad_axis,
 // recnow_elem_weight_fwd / _bwd (PoolingLayer, FixLengthLayer, gather_embedding_element_wise_weight); 13: recnow_can_fwd / _bwd / _supported (CANLayer);
 // 14: recnow_cross_desc, recnow_cross_text / _hash_ids (+ _host twins), recnow_cross_hash_embed_fwd (CartesianProductLayer);
-// 15: recnow_sparse_gnn_dense_fwd / _bwd / _workspace_bytes (SparseGNNLayer, the dense MFMA route).
-extern "C" int recnow_abi_version(void) { return 15; }
+// 15: recnow_sparse_gnn_dense_fwd / _bwd / _workspace_bytes (SparseGNNLayer, the dense MFMA route); 16: RECNOW_KEY_INF_EQUAL in the key dtype of
+// recnow_key_words / recnow_group_keys / recnow_listwise_loss (a version-15 build answers it with RECNOW_EINVAL), fp64 per-list sums (seg_lse, seg_ysum,
+// seg_psum, seg_pdot) in recnow_listwise_segments / _loss_fwdbwd / _dense.
+extern "C" int recnow_abi_version(void) { return 16; }

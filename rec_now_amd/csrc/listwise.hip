@@ -3,6 +3,8 @@
 // per-segment reductions (one wave per group) -- 16*B bytes of traffic instead of O(G*B).
 //
 //   valid group  : has a label > th AND a (label - th) < 0                                  (:135-137)
+//                  both tests run over the padded (G,B) row: with th < 0 the zero padding of a list shorter than the batch is a positive
+//   lists        : tf.unique equality (:109) -- equal infinities are one list, every NaN id is a list of its own (RECNOW_KEY_INF_EQUAL)
 //   row g of the reference's dense matrices = members' logits, padded with `pad_logit`
 //                  (= value_of_masked_logit when do_mask_logits else 0; B - n_g padded entries)   (:139-140)
 //   p_i = y_i / sum_{k in g} y_k                                                            (:144)
@@ -14,23 +16,28 @@
 // one wave per segment.  Outputs indexed by segment g (sorted numbering):
 //   seg_valid, seg_lse (log-sum-exp of the FULL padded row), seg_ysum; first_row[g] = smallest member row.
 //   valid_at_row[first_row] = seg_valid  (valid_at_row must be zero-filled)
+// The four sums and the log-sum-exp are fp64.  The gradient of a row is softmax_i * psum - p_i, and where a list's one positive is also its
+// top logit that difference is exp(-gap) all over the list: with an fp32 log-sum-exp (rounded at ulp(|lse|), 2.4e-7 for |lse| in [2, 4))
+// two-row lists at a gap of 5 came out 4e-5 off, relative to the list's largest entry (tests/test_listwise_lists_gpu.py).  exp(s - max) stays
+// an fp32 expf: its relative error carries over to the gradient as such.
 __global__ void __launch_bounds__(256)
 k_lw_stats(const float* __restrict__ labels, const float* __restrict__ logits, const int32_t* __restrict__ order,
            const int32_t* __restrict__ seg_first, const int32_t* __restrict__ n_seg, int64_t B, float th, float pad_logit,
-           int32_t* __restrict__ seg_valid, float* __restrict__ seg_lse, float* __restrict__ seg_ysum,
-           float* __restrict__ seg_psum, float* __restrict__ seg_pdot, int32_t* __restrict__ first_row,
+           int32_t* __restrict__ seg_valid, double* __restrict__ seg_lse, double* __restrict__ seg_ysum,
+           double* __restrict__ seg_psum, double* __restrict__ seg_pdot, int32_t* __restrict__ first_row,
            int32_t* __restrict__ valid_at_row) {
     const int lane = threadIdx.x & 63;
     const int G = n_seg[0] < 0 ? (int)B : n_seg[0];      // -1: the grouping timed out and left the identity grouping (B one-row lists, none valid)
     for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < G; g += gridDim.x * 4) {
         const int s = seg_first[g], e = seg_first[g + 1];
-        float mx = -INFINITY, ysum = 0.f;
+        float mx = -INFINITY;
+        double ysum = 0.0;
         int pos = 0, neg = 0;
         for (int k = s + lane; k < e; k += 64) {
             const int r = order[k];
             const float y = labels[r], v = logits[r];
             mx = fmaxf(mx, v);
-            ysum += y;
+            ysum += (double)y;
             pos |= (y > th);
             neg |= ((y - th) < 0.f);
         }
@@ -39,24 +46,26 @@ k_lw_stats(const float* __restrict__ labels, const float* __restrict__ logits, c
         pos = __any(pos);
         neg = __any(neg);
         const int n_pad = (int)(B - (e - s));
+        if (n_pad > 0 && 0.f > th) pos = 1;      // the reference tests the padded row: its zero labels are above a negative threshold
         if (n_pad > 0) mx = fmaxf(mx, pad_logit);
-        float z = 0.f, psum = 0.f, pdot = 0.f;
+        double z = 0.0, psum = 0.0, pdot = 0.0;
         for (int k = s + lane; k < e; k += 64) {
             const int r = order[k];
-            const float v = logits[r], p = labels[r] / ysum;
-            z += expf(v - mx);
+            const float v = logits[r];
+            const double p = (double)labels[r] / ysum;
+            z += (double)expf(v - mx);
             psum += p;
-            pdot += p * v;
+            pdot += p * (double)v;
         }
         z = wave_sum(z);
         psum = wave_sum(psum);
         pdot = wave_sum(pdot);
-        if (n_pad > 0) z += (float)n_pad * expf(pad_logit - mx);
+        if (n_pad > 0) z += (double)n_pad * (double)expf(pad_logit - mx);
         if (lane == 0) {
             const int valid = (pos && neg) ? 1 : 0;
             const int fr = order[s];
             seg_valid[g] = valid;
-            seg_lse[g] = mx + logf(z);
+            seg_lse[g] = (double)mx + log(z);
             seg_ysum[g] = ysum;
             seg_psum[g] = psum;
             seg_pdot[g] = pdot;
@@ -82,8 +91,8 @@ __global__ void k_lw_rank(const int32_t* __restrict__ seg_valid, const int32_t* 
 __global__ void __launch_bounds__(256)
 k_lw_grad(const float* __restrict__ labels, const float* __restrict__ logits, const int32_t* __restrict__ order,
           const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first, const int32_t* __restrict__ seg_valid,
-          const float* __restrict__ seg_lse, const float* __restrict__ seg_ysum, const float* __restrict__ seg_psum,
-          const float* __restrict__ seg_pdot, const int32_t* __restrict__ valid_rank, const float* __restrict__ weights,
+          const double* __restrict__ seg_lse, const double* __restrict__ seg_ysum, const double* __restrict__ seg_psum,
+          const double* __restrict__ seg_pdot, const int32_t* __restrict__ valid_rank, const float* __restrict__ weights,
           int64_t B, float* __restrict__ dbase, int32_t* __restrict__ row_rank, float* __restrict__ group_loss) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= B) return;
@@ -91,10 +100,10 @@ k_lw_grad(const float* __restrict__ labels, const float* __restrict__ logits, co
     const int vr = valid_rank[g];
     float d = 0.f;
     if (vr >= 0) {
-        const float w = weights ? weights[vr] : 1.f;
-        const float p = labels[r] / seg_ysum[g];
-        d = w * (expf(logits[r] - seg_lse[g]) * seg_psum[g] - p);
-        if (k == seg_first[g]) group_loss[vr] = w * (seg_lse[g] * seg_psum[g] - seg_pdot[g]);
+        const double w = weights ? (double)weights[vr] : 1.0;
+        const double p = (double)labels[r] / seg_ysum[g];
+        d = (float)(w * (exp((double)logits[r] - seg_lse[g]) * seg_psum[g] - p));
+        if (k == seg_first[g]) group_loss[vr] = (float)(w * (seg_lse[g] * seg_psum[g] - seg_pdot[g]));
     }
     dbase[r] = d;
     row_rank[r] = vr;
@@ -119,7 +128,7 @@ k_lw_mean(const float* __restrict__ group_loss, const int32_t* __restrict__ n_va
 // (mask 0, labels 0, logits pad_logit); members of valid groups are scattered in.
 __global__ void __launch_bounds__(256)
 k_lw_dense(const float* __restrict__ labels, const float* __restrict__ logits, const int32_t* __restrict__ order,
-           const int32_t* __restrict__ seg_id, const float* __restrict__ seg_ysum, const int32_t* __restrict__ valid_rank,
+           const int32_t* __restrict__ seg_id, const double* __restrict__ seg_ysum, const int32_t* __restrict__ valid_rank,
            int64_t B, uint8_t* __restrict__ mask_out, float* __restrict__ labels_out, float* __restrict__ logits_out) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= B) return;
@@ -128,7 +137,7 @@ k_lw_dense(const float* __restrict__ labels, const float* __restrict__ logits, c
     if (vr < 0) return;
     const int64_t o = (int64_t)vr * B + r;
     mask_out[o] = 1;
-    labels_out[o] = labels[r] / seg_ysum[g];
+    labels_out[o] = (float)((double)labels[r] / seg_ysum[g]);
     logits_out[o] = logits[r];
 }
 __global__ void __launch_bounds__(256)
@@ -189,10 +198,10 @@ extern "C" size_t recnow_listwise_workspace_bytes(int64_t B) {
     return 3 * rn_align(n * sizeof(int32_t)) + rn_scan_ws_bytes(B) + 256;     // first_row, valid_at_row, vscan
 }
 
-// Per-segment statistics.  Arrays seg_* and valid_rank are sized B (indexed by segment), n_valid: [1].
+// Per-segment statistics.  Arrays seg_* and valid_rank are sized B (indexed by segment), n_valid: [1]; the four sums are fp64.
 extern "C" int recnow_listwise_segments(const float* labels, const float* logits, const int32_t* order, const int32_t* seg_first,
                                         const int32_t* n_seg, int64_t B, float pos_neg_th, float pad_logit, int32_t* seg_valid,
-                                        float* seg_lse, float* seg_ysum, float* seg_psum, float* seg_pdot, int32_t* valid_rank,
+                                        double* seg_lse, double* seg_ysum, double* seg_psum, double* seg_pdot, int32_t* valid_rank,
                                         int32_t* n_valid, void* ws, size_t ws_bytes, void* stream) {
     if (B < 0 || !n_valid) return RECNOW_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -228,8 +237,8 @@ extern "C" int recnow_listwise_segments(const float* labels, const float* logits
 // Fused loss + gradient base.  weights: [n_valid] by valid rank or NULL.  loss: [1] (mean with NaN -> 0).
 // dbase [B], row_rank [B], group_loss [B] (first n_valid entries = per-list losses in first-occurrence order).
 extern "C" int recnow_listwise_loss_fwdbwd(const float* labels, const float* logits, const int32_t* order, const int32_t* seg_id,
-                                           const int32_t* seg_first, const int32_t* seg_valid, const float* seg_lse,
-                                           const float* seg_ysum, const float* seg_psum, const float* seg_pdot,
+                                           const int32_t* seg_first, const int32_t* seg_valid, const double* seg_lse,
+                                           const double* seg_ysum, const double* seg_psum, const double* seg_pdot,
                                            const int32_t* valid_rank, const int32_t* n_valid, const float* weights, int64_t B,
                                            float* loss, float* dbase, int32_t* row_rank, float* group_loss, void* stream) {
     if (B < 0 || !loss) return RECNOW_EINVAL;
@@ -250,7 +259,7 @@ extern "C" int recnow_listwise_loss_fwdbwd(const float* labels, const float* log
 
 // Dense (Gv,B) outputs of to_listwise_sample.  Caller pre-fills mask_out = 0, labels_out = 0, logits_out = pad_logit.
 extern "C" int recnow_listwise_dense(const float* labels, const float* logits, const int32_t* order, const int32_t* seg_id,
-                                     const float* seg_ysum, const int32_t* valid_rank, int64_t B, uint8_t* mask_out,
+                                     const double* seg_ysum, const int32_t* valid_rank, int64_t B, uint8_t* mask_out,
                                      float* labels_out, float* logits_out, void* stream) {
     if (B < 0) return RECNOW_EINVAL;
     if (B == 0) return RECNOW_OK;
@@ -298,7 +307,8 @@ extern "C" int recnow_softmax_ce_rows_bwd(const float* labels, const float* logi
 // ---- the fused listwise loss in one call (include/recnow.h: recnow_listwise_loss) ----------------------------------------------
 struct LwLossWs {
     int32_t *order, *seg_id, *seg_first, *super_id, *n_seg, *seg_valid, *valid_rank, *n_valid, *row_rank;
-    float *seg_lse, *seg_ysum, *seg_psum, *seg_pdot, *dbase, *group_loss, *loss;
+    double *seg_lse, *seg_ysum, *seg_psum, *seg_pdot;
+    float *dbase, *group_loss, *loss;
     uint32_t* words;
     uint8_t* solo;
     void* grp; size_t grp_bytes;
@@ -315,7 +325,7 @@ static LwLossWs lw_loss_carve(void* ws, int64_t B, int key_dtype) {
     w.order = c.take<int32_t>(n); w.seg_id = c.take<int32_t>(n); w.seg_first = c.take<int32_t>(n + 1); w.super_id = c.take<int32_t>(n);
     w.n_seg = c.take<int32_t>(2); w.seg_valid = c.take<int32_t>(n); w.valid_rank = c.take<int32_t>(n); w.n_valid = c.take<int32_t>(1);
     w.row_rank = c.take<int32_t>(n);
-    w.seg_lse = c.take<float>(n); w.seg_ysum = c.take<float>(n); w.seg_psum = c.take<float>(n); w.seg_pdot = c.take<float>(n);
+    w.seg_lse = c.take<double>(n); w.seg_ysum = c.take<double>(n); w.seg_psum = c.take<double>(n); w.seg_pdot = c.take<double>(n);
     w.dbase = c.take<float>(n); w.group_loss = c.take<float>(n); w.loss = c.take<float>(1);
     w.words = c.take<uint32_t>((size_t)w.n_words * n);
     w.solo = c.take<uint8_t>(n);
@@ -348,6 +358,7 @@ extern "C" int recnow_listwise_loss(const void* groups, int key_dtype, const flo
                                     float pos_neg_th, float pad_logit, float* out2, float* dlogits, void* ws, size_t ws_bytes, void* stream) {
     if (B < 0 || !out2) return RECNOW_EINVAL;
     if (recnow_key_words(key_dtype) < 1) return RECNOW_EINVAL;
+    key_dtype |= RECNOW_KEY_INF_EQUAL;      // lists are what tf.unique makes of the ids, whether or not the caller says so
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) {
         RN_HIP(hipMemsetAsync(out2, 0, 2 * sizeof(float), st));

@@ -15,22 +15,23 @@
 // ------------------------------------------------------------------------------------------------
 // keys
 // ------------------------------------------------------------------------------------------------
-__global__ void k_keys_f32(const float* __restrict__ g, int64_t B, uint32_t* __restrict__ w0, uint8_t* __restrict__ solo) {
+// inf_equal (RECNOW_KEY_INF_EQUAL, the listwise callers): tf.unique equality -- equal infinities are one group, only NaN rows are solo
+__global__ void k_keys_f32(const float* __restrict__ g, int64_t B, uint32_t* __restrict__ w0, uint8_t* __restrict__ solo, int inf_equal) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
     float v = g[i];
     uint32_t u = __float_as_uint(v);
     if (v == 0.0f) u = 0u;                       // -0.0 == +0.0
-    if (!(fabsf(v) < INFINITY)) solo[i] = 1;      // NaN, +-inf: v - v is NaN -> equals nothing
+    if (inf_equal ? v != v : !(fabsf(v) < INFINITY)) solo[i] = 1;      // NaN, +-inf: v - v is NaN -> equals nothing
     w0[i] = u;
 }
-__global__ void k_keys_f64(const double* __restrict__ g, int64_t B, uint32_t* __restrict__ w, uint8_t* __restrict__ solo) {
+__global__ void k_keys_f64(const double* __restrict__ g, int64_t B, uint32_t* __restrict__ w, uint8_t* __restrict__ solo, int inf_equal) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
     double v = g[i];
     uint64_t u = (uint64_t)__double_as_longlong(v);
     if (v == 0.0) u = 0ull;
-    if (!(fabs(v) < (double)INFINITY)) solo[i] = 1;
+    if (inf_equal ? v != v : !(fabs(v) < (double)INFINITY)) solo[i] = 1;
     w[i] = (uint32_t)(u >> 32);
     w[B + i] = (uint32_t)u;
 }
@@ -47,7 +48,7 @@ __global__ void k_keys_i64(const int64_t* __restrict__ g, int64_t B, uint32_t* _
 }
 
 extern "C" int recnow_key_words(int dtype) {
-    switch (dtype) {
+    switch (dtype & ~RECNOW_KEY_INF_EQUAL) {
         case RECNOW_KEY_F32: case RECNOW_KEY_I32: return 1;
         case RECNOW_KEY_F64: case RECNOW_KEY_I64: return 2;
         default: return RECNOW_EINVAL;
@@ -60,9 +61,10 @@ extern "C" int recnow_group_keys(const void* group, int dtype, int64_t B, uint32
     if (!group || !words || !solo) return RECNOW_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int T = 256, G = rn_cdiv(B, T);
-    switch (dtype) {
-        case RECNOW_KEY_F32: hipLaunchKernelGGL(k_keys_f32, G, T, 0, st, (const float*)group, B, words, solo); break;
-        case RECNOW_KEY_F64: hipLaunchKernelGGL(k_keys_f64, G, T, 0, st, (const double*)group, B, words, solo); break;
+    const int inf_equal = (dtype & RECNOW_KEY_INF_EQUAL) ? 1 : 0;
+    switch (dtype & ~RECNOW_KEY_INF_EQUAL) {
+        case RECNOW_KEY_F32: hipLaunchKernelGGL(k_keys_f32, G, T, 0, st, (const float*)group, B, words, solo, inf_equal); break;
+        case RECNOW_KEY_F64: hipLaunchKernelGGL(k_keys_f64, G, T, 0, st, (const double*)group, B, words, solo, inf_equal); break;
         case RECNOW_KEY_I32: hipLaunchKernelGGL(k_keys_i32, G, T, 0, st, (const int32_t*)group, B, words); break;
         case RECNOW_KEY_I64: hipLaunchKernelGGL(k_keys_i64, G, T, 0, st, (const int64_t*)group, B, words); break;
     }
@@ -609,7 +611,7 @@ group_mid_body(const uint32_t* __restrict__ words, uint8_t* __restrict__ solo, i
                GroupMidCtl* __restrict__ ctl, int32_t* __restrict__ idx0, int32_t* __restrict__ idx1, uint32_t* __restrict__ key0,
                uint32_t* __restrict__ key1, unsigned* __restrict__ blockhist, int* __restrict__ headcnt, int32_t* __restrict__ order,
                int32_t* __restrict__ seg_id, int32_t* __restrict__ seg_first, int32_t* __restrict__ super_id, int32_t* __restrict__ n_seg,
-               const int G, const int g) {
+               const int G, const int g, const int inf_equal) {      // inf_equal (RAW = 1): only NaN ids are solo (the listwise callers: tf.unique equality)
     __shared__ unsigned h[256];
     __shared__ unsigned wcnt[4][256];
     __shared__ unsigned boff[256];
@@ -653,7 +655,8 @@ group_mid_body(const uint32_t* __restrict__ words, uint8_t* __restrict__ solo, i
 #pragma unroll
                 for (int r = 0; r < TILE / 256; ++r) {
                     const int64_t i = base + r * 256 + tid;
-                    const bool fl = !(fabsf(__uint_as_float(kk[r])) < INFINITY);
+                    const float v = __uint_as_float(kk[r]);
+                    const bool fl = inf_equal ? v != v : !(fabsf(v) < INFINITY);
                     if (i < B) solo[i] = fl ? 1 : 0;
                     anys |= (i < B && fl) ? 1u : 0u;
                 }
@@ -1029,9 +1032,9 @@ __global__ void __launch_bounds__(256)
 k_group_mid(const uint32_t* __restrict__ words, uint8_t* __restrict__ solo, int64_t B, int n_words, int n_words_first,
             GroupMidCtl* __restrict__ ctl, int32_t* __restrict__ idx0, int32_t* __restrict__ idx1, uint32_t* __restrict__ key0,
             uint32_t* __restrict__ key1, unsigned* __restrict__ blockhist, int* __restrict__ headcnt, int32_t* __restrict__ order,
-            int32_t* __restrict__ seg_id, int32_t* __restrict__ seg_first, int32_t* __restrict__ super_id, int32_t* __restrict__ n_seg) {
+            int32_t* __restrict__ seg_id, int32_t* __restrict__ seg_first, int32_t* __restrict__ super_id, int32_t* __restrict__ n_seg, int inf_equal) {
     group_mid_body<TILE, RAW>(words, solo, B, n_words, n_words_first, ctl, idx0, idx1, key0, key1, blockhist, headcnt, order, seg_id, seg_first, super_id,
-                              n_seg, (int)gridDim.x, (int)blockIdx.x);
+                              n_seg, (int)gridDim.x, (int)blockIdx.x, inf_equal);
 }
 // Front kernel of recnow_dcn_mix_step above GS_MAXB rows: the first G workgroups (dispatched first: co-resident as before) group the batch, the others
 // write the weight packs of the row-block kernels (see k_front_small).
@@ -1044,7 +1047,7 @@ k_front_mid(const uint32_t* __restrict__ words, uint8_t* __restrict__ solo, int6
     if (zero1 && blockIdx.x == 0 && threadIdx.x == 0) *zero1 = 0ull;
     if ((int)blockIdx.x < G) {
         group_mid_body<RN_TILE, RAW>(words, solo, B, 1, 1, ctl, idx0, idx1, key0, key1, blockhist, headcnt, order, seg_id, seg_first, super_id, n_seg, G,
-                                     (int)blockIdx.x);
+                                     (int)blockIdx.x, 0);
         return;
     }
     tl_pack_range(pack, (int64_t)((int)blockIdx.x - G) * 256 + threadIdx.x, (int64_t)((int)gridDim.x - G) * 256);
@@ -1127,8 +1130,9 @@ extern "C" size_t recnow_group_segments_workspace_bytes(int64_t B, int n_words) 
 // The cooperative route (one launch, all workgroups co-resident: <= one per CU) over the workspace of recnow_group_segments; RECNOW_EUNSUPPORTED when the
 // batch does not fit it (the caller then takes the multi-launch chain).  raw = 0: canonical key words + solo flags; raw = 1 / 2: `words` is a float32 / int32
 // id tensor (n_words = 1), the kernel forms keys and solo flags itself (`solo` is written, not read, by the caller's side).  zero1 / zeroed: the front
-// kernels (pack != NULL) also clear one 64-bit word for the caller and say so; the other forms leave *zeroed alone.
-static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t B, int n_words, int n_words_first, int32_t* order, int32_t* seg_id,
+// kernels (pack != NULL) also clear one 64-bit word for the caller and say so; the other forms leave *zeroed alone.  inf_equal (raw = 1 without pack): the
+// flags the kernel forms mark NaN ids only (RECNOW_KEY_INF_EQUAL); it travels as a kernel argument, not as another instantiation.
+static int rn_group_coop(int raw, int inf_equal, const uint32_t* words, uint8_t* solo, int64_t B, int n_words, int n_words_first, int32_t* order, int32_t* seg_id,
                          int32_t* seg_first, int32_t* super_id, int32_t* n_seg, void* ws, size_t ws_bytes, hipStream_t st, const RnTileFwd* pack = nullptr,
                          unsigned long long* zero1 = nullptr, int* zeroed = nullptr, int* packed = nullptr) {
     if (packed) *packed = 0;
@@ -1165,7 +1169,7 @@ static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t 
     const int g = rn_cdiv(B, tile);
 #define GM_LAUNCH(T, R)                                                                                                                          \
     hipLaunchKernelGGL((k_group_mid<T, R>), g, 256, 0, st, words, solo, B, n_words, n_words_first, ctl, idx0, idx1, key0, key1, blockhist, headcnt, \
-                       order, seg_id, seg_first, super_id, n_seg)
+                       order, seg_id, seg_first, super_id, n_seg, inf_equal)
     if (raw && pack && tile == RN_TILE) {      // + the weight packs on workgroups behind the grouping's
         if (raw == 1)
             hipLaunchKernelGGL(k_front_mid<1>, g + RN_FRONT_PACK_WGS, 256, 0, st, words, solo, B, ctl, idx0, idx1, key0, key1, blockhist, headcnt, order, seg_id,
@@ -1194,9 +1198,11 @@ static int rn_group_coop(int raw, const uint32_t* words, uint8_t* solo, int64_t 
 int rn_group_mid_raw(const void* group, int dtype, int64_t B, uint8_t* solo, int32_t* order, int32_t* seg_id, int32_t* seg_first, int32_t* super_id,
                      int32_t* n_seg, void* ws, size_t ws_bytes, hipStream_t st, const RnTileFwd* pack, unsigned long long* zero1, int* zeroed, int* packed) {
     if (packed) *packed = 0;
-    if (B <= GS_MAXB || (dtype != RECNOW_KEY_F32 && dtype != RECNOW_KEY_I32) || !solo || !ws) return RECNOW_EUNSUPPORTED;
+    const int inf_equal = (dtype & RECNOW_KEY_INF_EQUAL) ? 1 : 0;      // the listwise loss; the front kernels (pack) know only the pairwise rule
+    dtype &= ~RECNOW_KEY_INF_EQUAL;
+    if (B <= GS_MAXB || (dtype != RECNOW_KEY_F32 && dtype != RECNOW_KEY_I32) || !solo || !ws || (inf_equal && pack)) return RECNOW_EUNSUPPORTED;
     if (ws_bytes < recnow_group_segments_workspace_bytes(B, 1)) return RECNOW_EWORKSPACE;
-    return rn_group_coop(dtype == RECNOW_KEY_F32 ? 1 : 2, (const uint32_t*)group, solo, B, 1, 1, order, seg_id, seg_first, super_id, n_seg, ws, ws_bytes, st, pack,
+    return rn_group_coop(dtype == RECNOW_KEY_F32 ? 1 : 2, inf_equal, (const uint32_t*)group, solo, B, 1, 1, order, seg_id, seg_first, super_id, n_seg, ws, ws_bytes, st, pack,
                          zero1, zeroed, packed);
 }
 
@@ -1229,7 +1235,7 @@ extern "C" int recnow_group_segments(const uint32_t* words, const uint8_t* solo,
         return RECNOW_OK;
     }
     const int nblk = rn_cdiv(B, RN_TILE);
-    int rc0 = rn_group_coop(0, words, const_cast<uint8_t*>(solo), B, n_words, n_words_first, order, seg_id, seg_first, super_id, n_seg, ws, ws_bytes, st);
+    int rc0 = rn_group_coop(0, 0, words, const_cast<uint8_t*>(solo), B, n_words, n_words_first, order, seg_id, seg_first, super_id, n_seg, ws, ws_bytes, st);
     if (rc0 != RECNOW_EUNSUPPORTED) return rc0;
     RnCarver c(ws, ws_bytes);
     SortPlan* plan = c.take<SortPlan>(1);

@@ -9,6 +9,7 @@ import torch
 from .. import _lib
 
 _KEY_F32, _KEY_F64, _KEY_I32, _KEY_I64 = 0, 1, 2, 3
+_KEY_INF_EQUAL = 256      # RECNOW_KEY_INF_EQUAL: tf.unique equality of float ids (equal infinities are one group, only NaN rows are alone)
 
 
 def _as_key_tensor(g):
@@ -45,10 +46,11 @@ class Segments(object):
         return n
 
 
-def build_segments(groups):
+def build_segments(groups, inf_equal=False):
     """groups: tensor or list of tensors, each with B elements ((B,), (B,1) or (1,B)).  A list means "same group in
     EVERY tensor" (logical AND of the masks, pairwise_loss_from_batch.py:65-73); groups[0] is the main group used for
-    the occurrence weights (:285)."""
+    the occurrence weights (:285).  inf_equal: float ids compare as tf.unique does (the listwise loss) -- equal infinities are one
+    group; the default is the pairwise rule `g_i - g_j == 0.0`, under which +-inf pair with nobody."""
     if not (isinstance(groups, (list, tuple)) and len(groups) > 0 and all(isinstance(g, torch.Tensor) for g in groups)):
         groups = [groups]          # one tensor, or one array-like of ids (e.g. a python list of numbers)
     if len(groups) == 0:
@@ -73,7 +75,7 @@ def build_segments(groups):
         words = torch.empty((n_words, max(B, 1)), dtype=torch.int32, device=dev)
         off = 0
         for (t, dt), nw in zip(keyed, nws):
-            _lib.call('recnow_group_keys', _lib.ptr(t), dt, B, _lib.ptr(words[off:]), _lib.ptr(solo), st)
+            _lib.call('recnow_group_keys', _lib.ptr(t), dt | (_KEY_INF_EQUAL if inf_equal else 0), B, _lib.ptr(words[off:]), _lib.ptr(solo), st)
             off += nw
     seg = Segments()
     seg.B, seg.device = B, dev

@@ -48,7 +48,7 @@ class _ListStats(object):
 
 
 def _list_stats(group_ids, labels, logits, do_mask_logits, value_of_masked_logit, pos_neg_th):
-    seg = build_segments(group_ids.reshape(-1) if isinstance(group_ids, torch.Tensor) else group_ids)
+    seg = build_segments(group_ids.reshape(-1) if isinstance(group_ids, torch.Tensor) else group_ids, inf_equal=True)      # tf.unique equality (:109)
     B, dev = seg.B, seg.device
     st = _ListStats()
     st.seg, st.B = seg, B
@@ -58,7 +58,7 @@ def _list_stats(group_ids, labels, logits, do_mask_logits, value_of_masked_logit
         raise ValueError('group_ids, labels and logits must have the same number of elements')
     n = max(B, 1)
     st.seg_valid = torch.empty(n, dtype=torch.int32, device=dev)
-    st.seg_lse, st.seg_ysum, st.seg_psum, st.seg_pdot = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(4))
+    st.seg_lse, st.seg_ysum, st.seg_psum, st.seg_pdot = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(4))      # fp64 sums (csrc/listwise.hip)
     st.valid_rank = torch.empty(n, dtype=torch.int32, device=dev)
     st.n_valid = torch.empty(1, dtype=torch.int32, device=dev)
     st.pad_logit = float(value_of_masked_logit) if do_mask_logits else 0.0
@@ -271,8 +271,9 @@ def listwise_loss_from_batch(group_ids, labels, logits, weights=None, do_reduce=
     without the (G,B) matrices and (for do_reduce=True) without a host sync.  `weights`: (num_valid_group,) in
     first-occurrence order of the valid groups.  Returns loss [, number of valid lists as a float tensor]."""
     if do_reduce and _LW_ONE_CALL and isinstance(group_ids, torch.Tensor) and group_ids.is_cuda and group_ids.numel() > 0:
-        from ._segments import _as_key_tensor
+        from ._segments import _as_key_tensor, _KEY_INF_EQUAL
         gkey, gdt = _as_key_tensor(group_ids)
+        gdt |= _KEY_INF_EQUAL
         loss, n_valid = _ListwiseOneCall.apply(logits, gkey, gdt, labels, weights, float(value_of_masked_logit) if do_mask_logits else 0.0,
                                                pos_neg_th)
         return (loss, n_valid) if return_num_list else loss
