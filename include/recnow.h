@@ -136,6 +136,26 @@ int recnow_pair_bpr_onepass(const float* scores, const float* labels, const uint
 int recnow_pair_scale_grad(const float* dscores_unnorm, const float* g, const int64_t* n_pair, float eps, int64_t B, float* out,
                            void* stream);
 
+/* The pair set and weights of a label_pair_to_weight_func (pairwise_loss_from_batch.py:175-194) over labels that take at most 16 distinct
+ * values, as a table: label_values [n_values] (distinct, finite), table [n_values x n_values] row-major, both DEVICE pointers;
+ * table[a][b] is the weight of a pair whose positive row has label label_values[a] and whose negative row has label_values[b].  (i, j) is a
+ * pair where the weight is > 0 (:193; zero, negative and NaN drop it, +inf keeps it), AND-ed per direction with score_i < score_j under
+ * RECNOW_PAIR_WRONG_ORDER -- the only predicate flag these take.  Both (i, j) and (j, i) may be pairs.  n_values outside 1..16:
+ * RECNOW_EINVAL.  A row that takes part (mask) with a label outside label_values makes the loss and every dscores entry NaN.
+ *   recnow_pair_table_count        outputs as recnow_pair_count (cnt_row / cnt_super by the positive row); leaves the members (with their class
+ *                                  ids) packed in ws
+ *   recnow_pair_table_bpr_fwdbwd   outputs as recnow_pair_bpr_fwdbwd, each pair weighted table[a][b] * cnt_super[super(i)] ** power; n_pair /
+ *                                  cnt_super from recnow_pair_table_count on the same inputs; RECNOW_PAIR_MEMBERS_PACKED: on the same ws, too. */
+int recnow_pair_table_count(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order,
+                            const int32_t* seg_id, const int32_t* seg_first, const int32_t* super_id, int64_t B, int flags,
+                            const float* label_values, int n_values, const float* table, int32_t* cnt_row, int64_t* cnt_super,
+                            int64_t* n_pair, void* ws, size_t ws_bytes, void* stream);
+int recnow_pair_table_bpr_fwdbwd(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order,
+                                 const int32_t* seg_id, const int32_t* seg_first, const int32_t* super_id,
+                                 const int64_t* cnt_super, const int64_t* n_pair, int64_t B, int flags,
+                                 const float* label_values, int n_values, const float* table, float factor, float power,
+                                 int reduce_mean, float* loss, float* dscores, void* ws, size_t ws_bytes, void* stream);
+
 /* pairwise_loss(outputs, labels, groups) with the reference's defaults (pairloss_func = bpr_loss_func, click_occurance_power = 0,
  * one group tensor; rec_block/pairwise_loss_from_batch.py:228-279) as ONE call: grouping (the single-launch front end when
  * recnow_pairwise_small_supported, else keys + radix sort + segments), the one-walk loss and the gradient

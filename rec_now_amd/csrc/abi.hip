@@ -13,5 +13,6 @@
 // 14: recnow_cross_desc, recnow_cross_text / _hash_ids (+ _host twins), recnow_cross_hash_embed_fwd (CartesianProductLayer);
 // 15: recnow_sparse_gnn_dense_fwd / _bwd / _workspace_bytes (SparseGNNLayer, the dense MFMA route); 16: RECNOW_KEY_INF_EQUAL in the key dtype of
 // recnow_key_words / recnow_group_keys / recnow_listwise_loss (a version-15 build answers it with RECNOW_EINVAL), fp64 per-list sums (seg_lse, seg_ysum,
-// seg_psum, seg_pdot) in recnow_listwise_segments / _loss_fwdbwd / _dense.
-extern "C" int recnow_abi_version(void) { return 16; }
+// seg_psum, seg_pdot) in recnow_listwise_segments / _loss_fwdbwd / _dense; 17: recnow_pair_table_count / recnow_pair_table_bpr_fwdbwd
+// (LabelPairWeightTable: the fused pairwise loss with per-label-pair weights).
+extern "C" int recnow_abi_version(void) { return 17; }

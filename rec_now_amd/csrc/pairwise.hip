@@ -9,39 +9,8 @@
 #include "common.hpp"
 #include "scan.hpp"
 #include "group_small.hpp"
+#include "pairwise_walk.hpp"
 
-struct __attribute__((aligned(16))) Member {   // one sorted row
-    float label;
-    float score;
-    int32_t row;      // original row index
-    int32_t valid;    // sample mask (1 = takes part)
-};
-
-__device__ __forceinline__ Member load_member(const float* __restrict__ scores, const float* __restrict__ labels,
-                                              const uint8_t* __restrict__ mask, const int32_t* __restrict__ order, int64_t k) {
-    Member m;
-    m.row = order[k];
-    m.label = labels[m.row];
-    m.score = scores[m.row];
-    m.valid = mask ? (mask[m.row] != 0) : 1;
-    return m;
-}
-
-// Where a walk's member records come from: the packed array (k_pack_members), or -- UNP, the step's loss stage since round 5 -- straight from the loss's
-// inputs through the sorted order (three dependent gathers instead of one 16-byte load: used to FILL the LDS stage of a workgroup, which is what the walks
-// read; a walk that cannot be staged -- a group of more than 2048 rows -- pays the gathers per member).  Saves the pack launch in front of the walk.
-template <bool UNP>
-struct MemberSrc {
-    const Member* __restrict__ mem;
-    const float* __restrict__ scores;
-    const float* __restrict__ labels;
-    const uint8_t* __restrict__ mask;
-    const int32_t* __restrict__ order;
-    __device__ __forceinline__ Member operator[](int64_t k) const {
-        if constexpr (UNP) return load_member(scores, labels, mask, order, k);
-        else return mem[k];
-    }
-};
 
 // zero_b / zero_1 (optional): the B per-row counters and the one total that the counting kernel adds into -- cleared here
 // instead of by two memset launches (a loss call is a chain of few-microsecond launches; each one removed is ~4 us)
@@ -65,59 +34,6 @@ __device__ __forceinline__ bool pair_ok(const Member& a, const Member& b) {   //
 }
 
 
-// The rows of a workgroup are 256 consecutive sorted positions, so the members they walk form ONE contiguous range of the
-// member array: [first row's segment start, last row's segment end).  When it fits (<= PW_STAGE members, 32 KB) it is staged
-// in LDS once, coalesced, and every per-row walk reads LDS (a walk is a chain of dependent 16-byte loads otherwise: ~0.4 us
-// per member from L1/L2).  Block-uniform decision; oversize ranges (one huge group) fall back to global loads.
-#define PW_STAGE 2048
-template <typename SRC>
-__device__ __forceinline__ bool stage_members(const SRC mem, const int32_t* __restrict__ seg_id,
-                                              const int32_t* __restrict__ seg_first, int64_t B, Member* lds, int* base, int rows_per_block = 0) {
-    *base = 0;
-    const int64_t rpb = rows_per_block > 0 ? rows_per_block : (int64_t)blockDim.x;
-    const int64_t k0 = (int64_t)blockIdx.x * rpb;
-    if (k0 >= B) return false;
-    const int64_t k1 = min(B, k0 + rpb) - 1;
-    const int lo = seg_first[seg_id[k0]], hi = seg_first[seg_id[k1] + 1];
-    if (hi - lo > PW_STAGE) return false;
-    for (int i = threadIdx.x; i < hi - lo; i += blockDim.x) lds[i] = mem[lo + i];
-    __syncthreads();
-    *base = lo;
-    return true;
-}
-// A row's walk over its segment, from LDS when the block's range was staged, else from global memory.  Two loops, so each
-// reads through a pointer of a known address space (one generic pointer made every read a flat_load that waits on both
-// counters), unrolled by four so that four member reads are in flight instead of one per ~40-instruction body.
-#define PW_WALK(IN_LDS, STAGED, SBASE, MEM, S, E, J, O, BODY)            \
-    do {                                                                  \
-        if (IN_LDS) {                                                     \
-            _Pragma("unroll 4") for (int J = (S); J < (E); ++J) {        \
-                const Member O = (STAGED)[J - (SBASE)];                   \
-                BODY                                                      \
-            }                                                             \
-        } else {                                                          \
-            _Pragma("unroll 4") for (int J = (S); J < (E); ++J) {        \
-                const Member O = (MEM)[J];                                \
-                BODY                                                      \
-            }                                                             \
-        }                                                                 \
-    } while (0)
-
-// the same two loops with a stride of one wave: lanes of a wave share the walk of ONE row (k_pair_long)
-#define PW_WALK_STRIDED(IN_LDS, STAGED, SBASE, MEM, S, E, J, O, BODY)    \
-    do {                                                                  \
-        if (IN_LDS) {                                                     \
-            _Pragma("unroll 4") for (int J = (S); J < (E); J += 64) {    \
-                const Member O = (STAGED)[J - (SBASE)];                   \
-                BODY                                                      \
-            }                                                             \
-        } else {                                                          \
-            _Pragma("unroll 4") for (int J = (S); J < (E); J += 64) {    \
-                const Member O = (MEM)[J];                                \
-                BODY                                                      \
-            }                                                             \
-        }                                                                 \
-    } while (0)
 
 // One candidate of a row's walk.  Labels are strictly ordered in at most one direction, so at most one of (me, o) / (o, me) is a
 // pair; both take their terms from ONE exp(-|x|) (x = the active pair's score difference): softplus(-x) = max(-x, 0) +
@@ -148,7 +64,6 @@ __device__ __forceinline__ void bpr_term(const Member& me, const Member& o, bool
 // the thread-per-row kernels below, which skip the walk of such rows.  A workgroup owns 64 consecutive sorted rows; a segment
 // lying strictly inside them is shorter than 64 rows, so only the first and the last row's segment can be long, and looking at
 // those two decides block-uniformly whether there is anything to do: batches without long groups pay one empty launch.
-#define PW_LONG 512
 template <int FLAGS, int MODE>                     // MODE 0: pair counts;  1: BPR loss and gradient terms
 __global__ void __launch_bounds__(256)
 k_pair_long(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first, int64_t B,
@@ -575,9 +490,6 @@ __global__ void k_seg_empty2(int32_t* seg_first, int32_t* n_seg, unsigned long l
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-#define RN_PW_T 256
-#define RN_PW_LPR 4        // lanes per row of the quad form of k_pair_all
-#define RN_VEC_BLOCKS 1024
 
 extern "C" size_t recnow_pairwise_workspace_bytes(int64_t B) {
     if (B < 0) return 0;
@@ -606,24 +518,6 @@ extern "C" size_t recnow_pairwise_workspace_bytes(int64_t B) {
         default: hipLaunchKernelGGL((k_pair_long<3, MODE>), rn_cdiv(B, 64), 256, 0, st, __VA_ARGS__); break;     \
     }
 
-// workspace layout: members (B + 1) | per-block loss partials | long-row counts | long-row loss terms | long-row gradient terms
-struct PairWs {
-    Member* mem;
-    double* part;
-    int32_t* long_cnt;
-    float *long_la, *long_ga;
-};
-static inline PairWs pair_ws(void* ws, size_t ws_bytes, int64_t B) {
-    RnCarver c(ws, ws_bytes);
-    PairWs p;
-    p.mem = c.take<Member>(B + 1);
-    const int G = 2 * rn_cdiv(B, RN_PW_T / RN_PW_LPR);
-    p.part = c.take<double>(G > RN_VEC_BLOCKS ? G : RN_VEC_BLOCKS);
-    p.long_cnt = c.take<int32_t>(B);
-    p.long_la = c.take<float>(B);
-    p.long_ga = c.take<float>(B);
-    return p;
-}
 
 // The Member array lives at the start of the pairwise workspace; every entry point re-packs it (B x 16 B).
 static int pack_members(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, int64_t B,

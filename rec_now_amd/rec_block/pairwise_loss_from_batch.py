@@ -6,13 +6,16 @@ the reference's dense O(B^2) masks are replaced by sort-by-group + segmented pai
 kernels (csrc/scan_sort.hip, csrc/pairwise.hip); pair order, counts and weights are identical to the reference's.
 
 Two execution paths:
-  * fused   -- `pairloss_func is bpr_loss_func` and no `label_pair_to_weight_func`: loss and d(loss)/d(outputs) come
-               out of one kernel, pairs are never materialised;
+  * fused   -- `pairloss_func` is `bpr_loss_func` (or a functools.partial of it that binds only `factor` / `reduce_mean`) and
+               `label_pair_to_weight_func` is None or a `LabelPairWeightTable`: loss and d(loss)/d(outputs) come out of one
+               kernel, pairs are never materialised;
   * general -- any other callable: pairs are materialised (bit-exact reference order), labels/outputs are gathered to
                (P,) vectors and the user's callables run on those.  Exact for element-wise callables (what the
                reference's own test uses, tests/rec_block/test_pairwise_loss_from_batch.py:51-53); callables that
                inspect the (B,B) *shape* are not supported.
 """
+import functools
+
 import torch
 
 from .. import _lib
@@ -216,6 +219,107 @@ class _PairBprFused(torch.autograd.Function):
         return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None
 
 
+class LabelPairWeightTable(object):
+    """An element-wise `label_pair_to_weight_func` over labels that take at most 16 distinct values, as a K x K table: `weights[a, b]`
+    is the weight of a pair whose positive row has label `label_values[a]` and whose negative row has label `label_values[b]`.  Passed as
+    `pairwise_loss(..., label_pair_to_weight_func=table)` it keeps the call on the fused route (csrc/pairwise_table.hip); it is also an
+    ordinary weight callable (lookup with torch ops, NaN for a label outside the values), so every other route takes it as well.
+
+    label_values: 1..16 distinct finite values (list, numpy or tensor), stored and compared as float32 (-0.0 equals 0.0).
+    The table comes from `weights` ((K, K), kept as given), or from ONE call of `label_pair_to_weight_func(M, M^T, **kwargs)` on the
+    (K, K) broadcast matrices of the values -- as the reference calls it on its (B, B) label matrices (:187-193) --, or, with neither,
+    from the default rule: 1.0 where values[a] > values[b], else 0.  As in the reference (:193) a pair survives where its weight is > 0:
+    zero, negative and NaN entries drop the pair, +inf keeps it."""
+
+    MAX_VALUES = 16
+
+    def __init__(self, label_values, label_pair_to_weight_func=None, weights=None, **kwargs):
+        vals = torch.as_tensor(label_values).detach().to('cpu', torch.float32).reshape(-1).clone()
+        K = vals.numel()
+        if K == 0:
+            raise ValueError('label_values must hold at least one value')
+        if K > self.MAX_VALUES:
+            raise ValueError('label_values holds %d values, at most %d are supported' % (K, self.MAX_VALUES))
+        if not bool(torch.isfinite(vals).all()):
+            raise ValueError('label_values must be finite (as float32)')
+        if int((vals.reshape(-1, 1) == vals.reshape(1, -1)).sum()) != K:
+            raise ValueError('label_values must be distinct (compared as float32; -0.0 equals 0.0)')
+        if weights is not None and label_pair_to_weight_func is not None:
+            raise ValueError('pass either weights or label_pair_to_weight_func, not both')
+        if kwargs and label_pair_to_weight_func is None:
+            raise ValueError('keyword arguments %s are for label_pair_to_weight_func, which was not given' % sorted(kwargs))
+        if weights is not None:
+            w = torch.as_tensor(weights).detach().to('cpu', torch.float32).clone()
+        elif label_pair_to_weight_func is not None:
+            a, b = vec_to_matrix_pair(vals)
+            w = torch.as_tensor(label_pair_to_weight_func(a.clone(), b.clone(), **kwargs)).detach().to('cpu', torch.float32).clone()
+        else:
+            a, b = vec_to_matrix_pair(vals)
+            w = (a > b).to(torch.float32)
+        if tuple(w.shape) != (K, K):
+            raise ValueError('the weight table must have shape (%d, %d), got %s' % (K, K, tuple(w.shape)))
+        self.label_values = vals
+        self.weights = w.contiguous()
+        self.n_values = K
+        self._per_device = {}
+
+    def on_device(self, device):
+        """(label_values, weights) as float32 tensors on `device`, uploaded once per device."""
+        device = torch.device(device)
+        if device.type == 'cpu':
+            return self.label_values, self.weights
+        hit = self._per_device.get(device)
+        if hit is None:
+            hit = (self.label_values.to(device), self.weights.to(device).contiguous())
+            self._per_device[device] = hit
+        return hit
+
+    def __call__(self, label_pos, label_neg, **ignored):
+        lp, ln = torch.as_tensor(label_pos), torch.as_tensor(label_neg)
+        vals, w = self.on_device(lp.device)
+        lp, ln = torch.broadcast_tensors(lp.to(torch.float32), ln.to(device=lp.device, dtype=torch.float32))
+        hit_p, hit_n = lp.unsqueeze(-1) == vals, ln.unsqueeze(-1) == vals
+        out = w[hit_p.to(torch.uint8).argmax(-1), hit_n.to(torch.uint8).argmax(-1)]
+        return torch.where(hit_p.any(-1) & hit_n.any(-1), out, torch.full_like(out, float('nan')))
+
+
+class _PairBprTable(torch.autograd.Function):
+    """The fused route with a LabelPairWeightTable: recnow_pair_table_count (members with class ids, pair counts per row / main group /
+    batch) then recnow_pair_table_bpr_fwdbwd on the same workspace.  No host synchronisation, nothing sized by the number of pairs."""
+
+    @staticmethod
+    def forward(ctx, outputs, labels, mask, seg, table, flags, factor, power, reduce_mean, want_np=True):
+        B, dev = seg.B, seg.device
+        ctx.want_np = bool(want_np)
+        scores = _flat_f32(outputs, B, 'outputs')
+        labs = _flat_f32(labels, B, 'labels')
+        m = _flat_mask(mask, B)
+        vals, w = table.on_device(dev)
+        K = table.n_values
+        cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+        cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
+        n_pair = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), dev)
+        st = _lib.stream()
+        _lib.call('recnow_pair_table_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
+                  _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(vals), K, _lib.ptr(w), _lib.ptr(cnt_row),
+                  _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
+        _lib.call('recnow_pair_table_bpr_fwdbwd', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
+                  _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super), _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED,
+                  _lib.ptr(vals), K, _lib.ptr(w), float(factor), float(power), 1 if reduce_mean else 0, _lib.ptr(loss), _lib.ptr(dscores),
+                  _lib.ptr(ws), ws.numel(), st)
+        ctx.save_for_backward(dscores[:B])
+        ctx.shape = outputs.shape
+        return loss, _n_pair_out(ctx, n_pair)
+
+    @staticmethod
+    def backward(ctx, g, _g_np):
+        (dscores,) = ctx.saved_tensors
+        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None
+
+
 class _PairBprSmall(torch.autograd.Function):
     """B <= 8192 rows, one float32 / int32 group tensor: keys, grouping and member packing in ONE launch
     (recnow_group_pack_small), then the counting and loss kernels of the general route on the packed members."""
@@ -337,11 +441,18 @@ def group_rows(groups):
 
 
 def pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair=False, click_occurance_power=0.0, mask=None,
-                        factor=1.0, reduce_mean=True, segments=None, return_num_pair=True):
+                        factor=1.0, reduce_mean=True, segments=None, return_num_pair=True, label_pair_weights=None):
     """Fused BPR pairwise loss; returns (loss, n_pair) as 0-dim tensors, no host sync.  `pairwise_loss` routes here
     whenever the defaults make it possible; exposed because it also accepts `factor` / `reduce_mean` and a precomputed
     `segments=group_rows(groups)` (then `groups` is not looked at again).  return_num_pair=False: the second value is None (the
-    float32 conversion of the pair count is a kernel of its own)."""
+    float32 conversion of the pair count is a kernel of its own).  label_pair_weights: a `LabelPairWeightTable` in place of the
+    default rule "label_i > label_j, weight 1"."""
+    if label_pair_weights is not None:
+        if not isinstance(label_pair_weights, LabelPairWeightTable):
+            raise TypeError('label_pair_weights must be a LabelPairWeightTable, got %s' % type(label_pair_weights))
+        seg = segments if segments is not None else build_segments(groups)
+        return _PairBprTable.apply(outputs, labels, mask, seg, label_pair_weights, _FLAG_WRONG_ORDER if only_use_wrong_order_pair else 0,
+                                   factor, click_occurance_power, reduce_mean, return_num_pair)
     flags = _FLAG_LABEL_GT | (_FLAG_WRONG_ORDER if only_use_wrong_order_pair else 0)
     if segments is None and float(click_occurance_power) == 0.0 and _ONE_CALL:
         one = _one_call_route(groups)
@@ -354,6 +465,17 @@ def pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair=False
                                        return_num_pair)
     seg = segments if segments is not None else build_segments(groups)
     return _PairBprFused.apply(outputs, labels, mask, seg, flags, factor, click_occurance_power, reduce_mean, return_num_pair)
+
+
+def _bpr_options(pairloss_func):
+    """(factor, reduce_mean) when `pairloss_func` is `bpr_loss_func` itself or a functools.partial of it that binds nothing but the
+    keywords `factor` / `reduce_mean` -- what the fused route can compute --, else None."""
+    if pairloss_func is bpr_loss_func:
+        return 1.0, True
+    if (isinstance(pairloss_func, functools.partial) and pairloss_func.func is bpr_loss_func and not pairloss_func.args
+            and set(pairloss_func.keywords) <= {'factor', 'reduce_mean'}):
+        return pairloss_func.keywords.get('factor', 1.0), pairloss_func.keywords.get('reduce_mean', True)
+    return None
 
 
 def _merge_weights_by_mul(weights1, weights2):
@@ -378,12 +500,17 @@ def pairwise_loss(outputs, labels, groups,
     Args (as the reference): outputs, labels: (B,)/(B,1) tensors; groups: tensor or list of tensors (AND of the
     conditions, groups[0] = main group for `click_occurance_power`); pairloss_func(outputs_pos, outputs_neg, weights);
     only_use_wrong_order_pair; return_num_pair; click_occurance_power; mask (bool, same shape as labels);
-    label_pair_to_weight_func(label_pos, label_neg, **kwargs) -> weights, pairs with weight <= 0 are dropped.
+    label_pair_to_weight_func(label_pos, label_neg, **kwargs) -> weights, pairs with weight <= 0 are dropped; a
+    `LabelPairWeightTable` keeps the call on the fused route (with bpr_loss_func, or a functools.partial of it binding factor / reduce_mean).
     Returns: loss, or (loss, n_pair as float32 tensor) when return_num_pair.
     """
-    if pairloss_func is bpr_loss_func and label_pair_to_weight_func is None:
+    table = label_pair_to_weight_func if isinstance(label_pair_to_weight_func, LabelPairWeightTable) else None
+    if table is not None and kwargs:
+        raise ValueError('a LabelPairWeightTable took its keyword arguments when it was built; got %s' % sorted(kwargs))
+    bpr = _bpr_options(pairloss_func)
+    if bpr is not None and (label_pair_to_weight_func is None or table is not None):
         loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
-                                           return_num_pair=return_num_pair)
+                                           factor=bpr[0], reduce_mean=bpr[1], return_num_pair=return_num_pair, label_pair_weights=table)
         return (loss, n_pair) if return_num_pair else loss
 
     # general path: materialise the pair list, then run the user's callables on (P,) vectors

@@ -1,0 +1,298 @@
+"""GPU parity of the fused pairwise loss with a LabelPairWeightTable (csrc/pairwise_table.hip) against the dense fp64 oracle
+(oracle/dense_ref.pairwise_loss, torch autograd for the gradient).  The oracle is handed the ORIGINAL weight function, never the table,
+so the table's construction is under test as well.  Bounds as tests/test_pairwise_gpu.py: pair count exact, loss within
+1e-5 * max(1, |ref|), gradient within 1e-5 * max|ref grad|.  Table entries are O(1), so the oracle's own fp64 result is the scale.
+
+Wherever the fused route is claimed, the module's `pair_indices` (the door to the general route) is patched to raise."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import dense_ref as R
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-5
+LEVELS = [0.0, 1.0, 2.0, 3.0]
+NAN = float('nan')
+
+
+def _mod():
+    from rec_now_amd.rec_block import pairwise_loss_from_batch as M
+    return M
+
+
+# ---- the three weight functions of the issue ---------------------------------------------------------------------------------------
+def _w_gap(a, b, **k):                       # (i) one direction only
+    return torch.clamp(a - b, min=0.0) * k['scale']
+
+
+def _w_sym(a, b, **k):                       # (ii) both directions, tied labels are pairs
+    return (a - b).abs() + 0.5
+
+
+# (iii) explicit, asymmetric: zero, negative, NaN and positive entries, positive on part of the diagonal
+W_EXPLICIT = [[0.5, 0.0, -1.0, NAN],
+              [1.5, 0.0, 0.25, 0.0],
+              [2.0, 0.75, 1.0, -0.5],
+              [NAN, 3.0, 0.0, 0.0]]
+
+
+def _w_explicit(a, b, **k):                  # the oracle's view of (iii): labels are the integers 0..3
+    return torch.tensor(W_EXPLICIT, dtype=a.dtype)[a.long(), b.long()]
+
+
+def _table(M, kind):
+    if kind == 'gap':
+        return M.LabelPairWeightTable(LEVELS, _w_gap, scale=2.0), _w_gap, {'scale': 2.0}
+    if kind == 'sym':
+        return M.LabelPairWeightTable(LEVELS, _w_sym), _w_sym, {}
+    return M.LabelPairWeightTable(LEVELS, weights=W_EXPLICIT), _w_explicit, {}
+
+
+# ---- batches ---------------------------------------------------------------------------------------------------------------------------
+def _batch(name):
+    """(groups, scores, labels, mask) as numpy; the mask keeps ~80 % of the rows."""
+    seed = {'b1': 1, 'b2': 2, 'b64': 3, 'b1000': 4, 'b2900': 5}[name]
+    rng = np.random.default_rng(seed)
+    if name == 'b2900':
+        # one group beyond PW_STAGE = 2048 (global-memory walk), one beyond PW_LONG = 512 (wave per row inside LDS), 200 rows in small groups
+        groups = np.concatenate([np.zeros(2100), np.ones(600), rng.integers(2, 22, 200)]).astype(np.float32)
+        rng.shuffle(groups)
+    else:
+        B, G = {'b1': (1, 1), 'b2': (2, 1), 'b64': (64, 4), 'b1000': (1000, 17)}[name]
+        groups = rng.integers(0, G, B).astype(np.float32)
+    B = groups.size
+    scores = rng.normal(size=B).astype(np.float32)
+    labels = rng.integers(0, 4, B).astype(np.float32)
+    mask = rng.random(B) < 0.8
+    return groups, scores, labels, mask
+
+
+def _oracle(g, s, y, mask, wf, wkw, power, wrong, factor=1.0):
+    s64 = torch.from_numpy(s).double().requires_grad_(True)
+    lf = R.bpr_loss_func if factor == 1.0 else (lambda p, n, w: R.bpr_loss_func(p, n, w, factor))
+    rloss, rn = R.pairwise_loss(s64, torch.from_numpy(y).double(), torch.from_numpy(g), lf, only_use_wrong_order_pair=wrong,
+                                return_num_pair=True, click_occurance_power=power, mask=None if mask is None else torch.from_numpy(mask),
+                                label_pair_to_weight_func=wf, **wkw)
+    rloss.backward()
+    return rloss.item(), rn, s64.grad.numpy()
+
+
+def _no_general_route(monkeypatch, M):
+    def refuse(*a, **k):
+        raise AssertionError('the general route (pair_indices) was taken')
+    monkeypatch.setattr(M, 'pair_indices', refuse)
+
+
+def _run(M, dev, g, s, y, mask, power, wrong, **kw):
+    sd = torch.from_numpy(s).to(dev).requires_grad_(True)
+    loss, n_pair = M.pairwise_loss(sd, torch.from_numpy(y).to(dev), torch.from_numpy(g).to(dev), only_use_wrong_order_pair=wrong,
+                                   return_num_pair=True, click_occurance_power=power,
+                                   mask=None if mask is None else torch.from_numpy(mask).to(dev), **kw)
+    loss.backward()
+    return loss.item(), n_pair.item(), sd.grad.cpu().numpy()
+
+
+def _check(got, want):
+    loss, n_pair, grad = got
+    rloss, rn, rgrad = want
+    gerr = np.abs(grad - rgrad).max() if grad.size else 0.0
+    scale = max(np.abs(rgrad).max(), 1e-12) if grad.size else 1.0
+    print('n_pair %d (ref %d)  loss %.9g (ref %.9g, err %.3g)  grad err %.3g of max %.3g' % (n_pair, rn, loss, rloss, abs(loss - rloss), gerr, scale))
+    assert n_pair == rn                                               # integer path: exact
+    assert abs(loss - rloss) <= RTOL * max(1.0, abs(rloss))
+    assert gerr <= RTOL * scale
+
+
+# ---- the reference's own golden ------------------------------------------------------------------------------------------------------
+def test_reference_golden_through_a_table(dev, monkeypatch):
+    # the 5-row case of the reference's tests/rec_block/test_pairwise_loss_from_batch.py:34-63 (and the mask of :66)
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g = torch.tensor([[1, 1, 2, 2, 2.]], device=dev).t()
+    s = torch.tensor([[0, 1, 2, 3, 4.]], device=dev).t()
+    y = torch.tensor([[1.1, 0, 0, 1, 1]], device=dev).t()
+
+    def _label_pair_to_weight_func(label_matrix, label_matrix_transpose, **kwargs):
+        return (label_matrix > label_matrix_transpose).to(torch.float32)
+
+    t = M.LabelPairWeightTable([0, 1, 1.1], _label_pair_to_weight_func)
+    loss = M.pairwise_loss(s, y, g, click_occurance_power=-0.5, label_pair_to_weight_func=t)
+    assert abs(loss.item() - 0.5415076) < 1e-4
+    mask = torch.tensor([[True, True, False, False, False]], device=dev).t()
+    loss = M.pairwise_loss(s, y, g, click_occurance_power=-0.5, mask=mask, label_pair_to_weight_func=t)
+    assert abs(loss.item() - 1.3132617) < 1e-4
+
+
+# ---- parity: every weight function meets every batch, every power meets both long-group sizes (b2900 holds both) -----------------------
+CASES = [
+    # kind, batch, power, wrong order, mask
+    ('gap', 'b64', 0.0, False, True),
+    ('sym', 'b64', -0.5, True, False),
+    ('explicit', 'b64', 1.0, False, True),
+    ('gap', 'b1000', -0.5, True, True),
+    ('sym', 'b1000', 1.0, False, True),
+    ('explicit', 'b1000', 0.0, True, False),
+    ('gap', 'b2900', 1.0, False, True),
+    ('sym', 'b2900', 0.0, False, False),
+    ('explicit', 'b2900', -0.5, True, True),
+    ('gap', 'b1', -0.5, False, False),
+    ('sym', 'b1', 0.0, False, False),
+    ('explicit', 'b1', 1.0, True, True),
+    ('gap', 'b2', 0.0, True, False),
+    ('sym', 'b2', -0.5, False, False),
+    ('explicit', 'b2', -0.5, False, False),
+]
+
+
+@pytest.mark.parametrize('kind,batch,power,wrong,use_mask', CASES)
+def test_table_route_vs_oracle(dev, monkeypatch, kind, batch, power, wrong, use_mask):
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g, s, y, mask = _batch(batch)
+    if not use_mask:
+        mask = None
+    elif batch in ('b1', 'b2'):
+        mask = np.ones(g.size, dtype=bool)
+    t, wf, wkw = _table(M, kind)
+    got = _run(M, dev, g, s, y, mask, power, wrong, label_pair_to_weight_func=t)
+    _check(got, _oracle(g, s, y, mask, wf, wkw, power, wrong))
+
+
+@pytest.mark.parametrize('with_table', [True, False])
+@pytest.mark.parametrize('power', [0.0, -0.5])
+def test_factor_through_functools_partial(dev, monkeypatch, with_table, power):
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g, s, y, mask = _batch('b1000')
+    lf = functools.partial(M.bpr_loss_func, factor=0.7)
+    if with_table:
+        t, wf, wkw = _table(M, 'sym')
+        got = _run(M, dev, g, s, y, mask, power, False, pairloss_func=lf, label_pair_to_weight_func=t)
+    else:
+        wf, wkw = None, {}
+        got = _run(M, dev, g, s, y, mask, power, False, pairloss_func=lf)
+    _check(got, _oracle(g, s, y, mask, wf, wkw, power, False, factor=0.7))
+
+
+def test_reduce_mean_false_and_precomputed_segments(dev):
+    M = _mod()
+    g, s, y, mask = _batch('b1000')
+    t, wf, wkw = _table(M, 'explicit')
+    gd = torch.from_numpy(g).to(dev)
+    sd = torch.from_numpy(s).to(dev).requires_grad_(True)
+    loss, n_pair = M.pairwise_loss_fused(sd, torch.from_numpy(y).to(dev), None, click_occurance_power=-0.5, mask=torch.from_numpy(mask).to(dev),
+                                         factor=0.7, reduce_mean=False, segments=M.group_rows(gd), label_pair_weights=t)
+    loss.backward()
+    s64 = torch.from_numpy(s).double().requires_grad_(True)
+    lf = lambda p, n, w: R.bpr_loss_func(p, n, w, 0.7, reduce_mean=False)       # noqa: E731
+    rloss, rn = R.pairwise_loss(s64, torch.from_numpy(y).double(), torch.from_numpy(g), lf, return_num_pair=True, click_occurance_power=-0.5,
+                                mask=torch.from_numpy(mask), label_pair_to_weight_func=wf)
+    rloss.backward()
+    _check((loss.item(), n_pair.item(), sd.grad.cpu().numpy()), (rloss.item(), rn, s64.grad.numpy()))
+
+
+@pytest.mark.parametrize('batch,power,wrong', [('b1000', 0.0, False), ('b1000', -0.5, True), ('b2900', 1.0, False)])
+def test_default_rule_table_equals_the_fused_route(dev, monkeypatch, batch, power, wrong):
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g, s, y, mask = _batch(batch)
+    want = _run(M, dev, g, s, y, mask, power, wrong)
+    got = _run(M, dev, g, s, y, mask, power, wrong, label_pair_to_weight_func=M.LabelPairWeightTable(LEVELS))
+    _check(got, want)
+
+
+def test_no_pairs(dev, monkeypatch):
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g, s, y, mask = _batch('b1000')
+    dead = M.LabelPairWeightTable(LEVELS, weights=[[0.0, -1.0, NAN, 0.0], [-0.5, 0.0, 0.0, NAN], [0.0, 0.0, -2.0, 0.0], [NAN, 0.0, 0.0, 0.0]])
+    live, _, _ = _table(M, 'sym')
+    for t, m in ((dead, mask), (dead, None), (live, np.zeros(g.size, dtype=bool))):
+        for power in (0.0, -0.5):
+            loss, n_pair, grad = _run(M, dev, g, s, y, m, power, False, label_pair_to_weight_func=t)
+            assert loss == 0.0 and n_pair == 0.0
+            assert np.array_equal(grad, np.zeros_like(grad))
+
+
+def test_unknown_label(dev, monkeypatch):
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g, s, y, mask = _batch('b1000')
+    t, wf, wkw = _table(M, 'sym')
+    row = int(np.flatnonzero(mask)[10])
+    y = y.copy()
+    y[row] = 7.0
+    for m in (mask, None):
+        for power in (0.0, -0.5):
+            loss, n_pair, grad = _run(M, dev, g, s, y, m, power, False, label_pair_to_weight_func=t)
+            assert np.isnan(loss)
+            assert np.isnan(grad).all()
+    # the same row masked out: no effect, finite and equal to the oracle
+    mask2 = mask.copy()
+    mask2[row] = False
+    got = _run(M, dev, g, s, y, mask2, -0.5, False, label_pair_to_weight_func=t)
+    assert np.isfinite(got[0]) and np.isfinite(got[2]).all()
+    _check(got, _oracle(g, s, y, mask2, wf, wkw, -0.5, False))
+
+
+def test_run_to_run_bit_identical(dev, monkeypatch):
+    M = _mod()
+    _no_general_route(monkeypatch, M)
+    g, s, y, mask = _batch('b2900')
+    t, _, _ = _table(M, 'sym')
+    for power in (0.0, -0.5):
+        a = _run(M, dev, g, s, y, None, power, False, label_pair_to_weight_func=t)
+        b = _run(M, dev, g, s, y, None, power, False, label_pair_to_weight_func=t)
+        assert np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes()
+        assert a[1] == b[1]
+        assert a[2].tobytes() == b[2].tobytes()
+
+
+def test_no_memory_proportional_to_the_pairs(dev):
+    """B 2900 with table (ii) and no mask: every ordered pair inside a group is a pair, P > 4 million (8 bytes per pair alone: > 35 MB).  The
+    table route's peak allocation across forward + backward stays below 16 pairwise workspaces; the general route with the same table,
+    wrapped in a plain lambda so that it is just another callable, gives the same loss."""
+    from rec_now_amd import _lib
+    M = _mod()
+    g, s, y, _ = _batch('b2900')
+    t, _, _ = _table(M, 'sym')
+    gd, yd = torch.from_numpy(g).to(dev), torch.from_numpy(y).to(dev)
+    sd = torch.from_numpy(s).to(dev).requires_grad_(True)
+    M.pairwise_loss(sd, yd, gd, label_pair_to_weight_func=t)              # (uploads the table: 80 bytes that stay)
+    sd.grad = None
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    loss, n_pair = M.pairwise_loss(sd, yd, gd, return_num_pair=True, label_pair_to_weight_func=t)
+    loss.backward()
+    torch.cuda.synchronize()
+    growth = torch.cuda.max_memory_allocated() - base
+    bound = 16 * _lib.load().recnow_pairwise_workspace_bytes(g.size)
+    print('pairs %d  peak growth %d bytes  bound %d bytes' % (n_pair.item(), growth, bound))
+    assert n_pair.item() > 4.0e6
+    assert growth < bound
+    loss_general, n_general = M.pairwise_loss(sd, yd, gd, return_num_pair=True, label_pair_to_weight_func=lambda a, b, **k: t(a, b))
+    print('table route %.9g  general route %.9g' % (loss.item(), loss_general.item()))
+    assert n_general.item() == n_pair.item()
+    assert abs(loss.item() - loss_general.item()) <= RTOL * max(1.0, abs(loss_general.item()))
+
+
+def test_other_loss_function_takes_the_general_route(dev, monkeypatch):
+    M = _mod()
+    g, s, y, mask = _batch('b1000')
+    t, wf, wkw = _table(M, 'gap')
+    calls = []
+    real = M.pair_indices
+
+    def spy(*a, **k):
+        calls.append(1)
+        return real(*a, **k)
+    monkeypatch.setattr(M, 'pair_indices', spy)
+    lf = lambda p, n, w: M.bpr_loss_func(p, n, w, 0.7)                       # noqa: E731  (not bpr_loss_func itself: the general route)
+    got = _run(M, dev, g, s, y, mask, -0.5, False, pairloss_func=lf, label_pair_to_weight_func=t)
+    assert calls
+    _check(got, _oracle(g, s, y, mask, wf, wkw, -0.5, False, factor=0.7))

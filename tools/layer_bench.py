@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -122,6 +122,41 @@ def pairwise(B, G, tag):
     mg = timeit_graph(step)
     if mg:
         print('   replayed from a HIP graph (GPU time of the step): %.3f ms  %.1f M rows/s' % (mg, B / mg / 1e3))
+
+
+def pair_table():
+    """pairwise_loss with per-label-pair weights at config 3's shape (B = 65 536, 1024 groups, four label levels, weight |a - b| + 0.5: both
+    directions and tied labels are pairs): the fused table route, the general route with the same table (handed over as a plain callable) and
+    the default fused loss without a table as the yardstick -- wall time per step, and GPU time (the step replayed from a HIP graph) where the
+    route can be captured."""
+    from rec_now_amd.rec_block.pairwise_loss_from_batch import LabelPairWeightTable, pairwise_loss
+    B, G = 65536, 1024
+    rng = np.random.default_rng(2)
+    g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+    y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+    s = torch.randn(B, device=dev, requires_grad=True)
+    table = LabelPairWeightTable([0.0, 1.0, 2.0, 3.0], lambda a, b: (a - b).abs() + 0.5)
+    rows = (('table route', {'label_pair_to_weight_func': table}),
+            ('general route, same table', {'label_pair_to_weight_func': lambda a, b, **k: table(a, b)}),
+            ('default fused loss, no table', {}))
+    res = {}
+    for tag, kw in rows:
+        npair = [None]
+
+        def step():
+            s.grad = None
+            loss, n = pairwise_loss(s, y, g, return_num_pair=True, **kw)
+            loss.backward()
+            npair[0] = n
+        ms = timeit(step)
+        mg = timeit_graph(step)
+        res[tag] = (ms, mg)
+        print('pairwise_loss %s B=%d groups=%d pairs=%d : wall %.3f ms per fwd+bwd, GPU %s' % (
+            tag, B, G, float(npair[0].item()), ms, ('%.3f ms (graph replay)' % mg) if mg else 'time not separable (host synchronisations: no capture)'))
+    t, ge, d = res['table route'], res['general route, same table'], res['default fused loss, no table']
+    print('   wall: general / table = %.1fx, table / default = %.2fx' % (ge[0] / t[0], t[0] / d[0]))
+    if t[1] and d[1]:
+        print('   GPU: table / default = %.2fx; general route wall / table GPU = %.1fx' % (t[1] / d[1], ge[0] / t[1]))
 
 
 def listwise():
@@ -813,6 +848,8 @@ if __name__ == '__main__':
         pairwise(8192, 0, 'config2-skewed (Zipf 1.2 group sizes, cap 2048)')
         pairwise(65536, 1024, 'config3')
         pairwise(65536, 0, 'config3-skewed (Zipf 1.2 group sizes, cap 2048)')
+    if 'pair_table' in which:
+        pair_table()
     if 'list' in which:
         listwise()
     if 'cin' in which:
