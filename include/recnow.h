@@ -156,6 +156,30 @@ int recnow_pair_table_bpr_fwdbwd(const float* scores, const float* labels, const
                                  const float* label_values, int n_values, const float* table, float factor, float power,
                                  int reduce_mean, float* loss, float* dscores, void* ws, size_t ws_bytes, void* stream);
 
+/* The fused pairwise loss for pair terms other than BPR: the `pairloss_func` of pairwise_loss (pairwise_loss_from_batch.py:228-279) as one of
+ *   RECNOW_PAIR_KIND_HINGE            f(u) = max(u, 0)        (subgradient 0 at u == 0)
+ *   RECNOW_PAIR_KIND_SQUARED_HINGE    f(u) = max(u, 0) ** 2
+ *   RECNOW_PAIR_KIND_MARGIN_LOGISTIC  f(u) = softplus(u)
+ * of u = margin - factor * (s_i - s_j) per pair (i, j):
+ *   loss = sum_p w_p f(u_p) / (float(P) + 1e-10)   (or the raw sum if !reduce_mean),   dscores[k] = d loss / d scores[k]
+ * The pair set and w_p follow `table`:
+ *   table != NULL  label_values / n_values / table as recnow_pair_table_count; w_p = table[a][b] * cnt_super[super(i_p)] ** power; flags:
+ *                  [RECNOW_PAIR_WRONG_ORDER]; n_pair / cnt_super from recnow_pair_table_count on the same inputs.  A row that takes part with a
+ *                  label outside label_values makes the loss and every dscores entry NaN.
+ *   table == NULL  the rule label_i > label_j: flags must hold RECNOW_PAIR_LABEL_GT [| RECNOW_PAIR_WRONG_ORDER]; w_p = cnt_super[super(i_p)] **
+ *                  power; n_pair / cnt_super from recnow_pair_count with the same flags; label_values / n_values are not looked at.
+ * RECNOW_PAIR_MEMBERS_PACKED: ws is the workspace that count call just used (its packed rows are reused); without it the rows are packed here.
+ * Workspace: recnow_pairwise_workspace_bytes(B).  RECNOW_EINVAL: an unknown kind, a non-finite margin or factor, n_values outside 1..16 with a
+ * table, table == NULL without RECNOW_PAIR_LABEL_GT, any other flag, power != 0 without cnt_super.  B == 0 writes loss = 0. */
+#define RECNOW_PAIR_KIND_HINGE 1
+#define RECNOW_PAIR_KIND_SQUARED_HINGE 2
+#define RECNOW_PAIR_KIND_MARGIN_LOGISTIC 3
+int recnow_pair_kind_fwdbwd(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order,
+                            const int32_t* seg_id, const int32_t* seg_first, const int32_t* super_id, const int64_t* cnt_super,
+                            const int64_t* n_pair, int64_t B, int flags, int kind, float margin, const float* label_values, int n_values,
+                            const float* table, float factor, float power, int reduce_mean, float* loss, float* dscores, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* pairwise_loss(outputs, labels, groups) with the reference's defaults (pairloss_func = bpr_loss_func, click_occurance_power = 0,
  * one group tensor; rec_block/pairwise_loss_from_batch.py:228-279) as ONE call: grouping (the single-launch front end when
  * recnow_pairwise_small_supported, else keys + radix sort + segments), the one-walk loss and the gradient

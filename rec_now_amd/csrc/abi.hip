@@ -14,5 +14,6 @@
 // 15: recnow_sparse_gnn_dense_fwd / _bwd / _workspace_bytes (SparseGNNLayer, the dense MFMA route); 16: RECNOW_KEY_INF_EQUAL in the key dtype of
 // recnow_key_words / recnow_group_keys / recnow_listwise_loss (a version-15 build answers it with RECNOW_EINVAL), fp64 per-list sums (seg_lse, seg_ysum,
 // seg_psum, seg_pdot) in recnow_listwise_segments / _loss_fwdbwd / _dense; 17: recnow_pair_table_count / recnow_pair_table_bpr_fwdbwd
-// (LabelPairWeightTable: the fused pairwise loss with per-label-pair weights).
-extern "C" int recnow_abi_version(void) { return 17; }
+// (LabelPairWeightTable: the fused pairwise loss with per-label-pair weights); 18: recnow_pair_kind_fwdbwd (hinge, squared-hinge and margin-logistic
+// pair terms on the fused route).
+extern "C" int recnow_abi_version(void) { return 18; }

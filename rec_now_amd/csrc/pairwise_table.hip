@@ -20,10 +20,7 @@
 // No float atomics: per-row terms are written by their row, loss partials per workgroup are summed in fixed order (bitwise reproducible).
 #include "common.hpp"
 #include "pairwise_walk.hpp"
-
-#define PT_MAXV 16
-#define PT_BAD 256
-#define PT_CLS(v) (((v) >> 1) & 15)
+#include "pairwise_table.hpp"      // PT_* macros, pt_load_table, pt_dirs, pt_bad_flag
 
 // members with class ids; clears the counters the counting kernel adds into (zero_b: B entries, zero_1: one) and the unknown-label flag
 __global__ void k_pt_pack(const float* __restrict__ scores, const float* __restrict__ labels, const uint8_t* __restrict__ mask,
@@ -49,33 +46,6 @@ __global__ void k_pt_pack(const float* __restrict__ scores, const float* __restr
 __global__ void k_pt_flag(const Member* __restrict__ mem, int64_t B, unsigned* __restrict__ bad) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < B && (mem[k].valid & PT_BAD)) atomicOr(bad, 1u);
-}
-
-// tw[0..256): W reduced to "> 0 else 0", row-major with a stride of 16; tw[256..512): its transpose.  The caller synchronises.
-__device__ __forceinline__ void pt_load_table(const float* __restrict__ W, int nv, float* tw) {
-    for (int i = threadIdx.x; i < PT_MAXV * PT_MAXV; i += blockDim.x) {
-        const int a = i >> 4, b = i & 15;
-        float w = (a < nv && b < nv) ? W[a * nv + b] : 0.f;
-        w = w > 0.f ? w : 0.f;                                                     // zero, negative and NaN drop the pair; +inf keeps it
-        tw[i] = w;
-        tw[PT_MAXV * PT_MAXV + ((b << 4) | a)] = w;
-    }
-}
-
-// Weights of the two directions of one candidate: wf of (me, o), wb of (o, me); 0 where that direction is no pair.  trow / tcol: row
-// class(me) of the table and of its transpose.  The wrong-order rule ANDs in per direction (reference :197-203).
-template <int WRONG>
-__device__ __forceinline__ void pt_dirs(const Member& me, const Member& o, bool other, const float* trow, const float* tcol, float& wf, float& wb) {
-    const int oc = PT_CLS(o.valid);
-    const bool both = other && ((me.valid & o.valid & 1) != 0);
-    bool okf = both, okb = both;
-    if (WRONG) {
-        okf = okf && (me.score < o.score);
-        okb = okb && (o.score < me.score);
-    }
-    const float f = trow[oc], b = tcol[oc];
-    wf = okf ? f : 0.f;
-    wb = okb ? b : 0.f;
 }
 
 // One candidate, both directions from one exp(-|d|); hardware exp2 / log2 / rcp and selects instead of per-lane branches, as bpr_term.
@@ -253,9 +223,6 @@ k_pt_finalize(const double* __restrict__ part, int n, const unsigned long long* 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-// the unknown-label flag lives in the spare member record mem[B] of the pairwise workspace
-static inline unsigned* pt_bad_flag(const PairWs& pw, int64_t B) { return reinterpret_cast<unsigned*>(pw.mem + B); }
-
 #define PT_FLAGS_OK(flags) (((flags) & ~(RECNOW_PAIR_WRONG_ORDER | RECNOW_PAIR_MEMBERS_PACKED)) == 0)
 
 extern "C" int recnow_pair_table_count(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order,
@@ -323,6 +290,24 @@ extern "C" int recnow_pair_table_bpr_fwdbwd(const float* scores, const float* la
                            (const unsigned long long*)n_pair, B, table, n_values, factor, power, reduce_mean, pw.long_la, pw.long_ga, bad, pw.part, dscores);
     }
     hipLaunchKernelGGL(k_pt_finalize, 1, 1024, 0, st, pw.part, G, (const unsigned long long*)n_pair, reduce_mean, loss);
+    RN_LAUNCH_CHECK();
+    return RECNOW_OK;
+}
+
+// ---- for pairwise_kind.hip: the packing and finalize kernels above, launched from another translation unit -------------------------------
+int rn_pt_pack_members(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, int64_t B, const float* label_values,
+                       int n_values, const PairWs& pw, hipStream_t st) {
+    unsigned* bad = pt_bad_flag(pw, B);
+    const int G = rn_cdiv(B, RN_PW_T);
+    hipLaunchKernelGGL(k_pt_pack, G, RN_PW_T, 0, st, scores, labels, mask, order, B, label_values, n_values, pw.mem,
+                       (unsigned long long*)nullptr, (unsigned long long*)nullptr, bad);
+    hipLaunchKernelGGL(k_pt_flag, G, RN_PW_T, 0, st, pw.mem, B, bad);
+    RN_LAUNCH_CHECK();
+    return RECNOW_OK;
+}
+
+int rn_pt_finalize(const double* part, int n, const int64_t* n_pair, int reduce_mean, float* loss, hipStream_t st) {
+    hipLaunchKernelGGL(k_pt_finalize, 1, 1024, 0, st, part, n, (const unsigned long long*)n_pair, reduce_mean, loss);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
 }

@@ -1,4 +1,4 @@
-// Shared by the pair walks of pairwise.hip and pairwise_table.hip: the 16-byte member record of a sorted row, the LDS staging of a workgroup's
+// Shared by the pair walks of pairwise.hip, pairwise_table.hip and pairwise_kind.hip: the 16-byte member record of a sorted row, the LDS staging of a workgroup's
 // member range, the walk loops and the layout of the pairwise workspace (recnow_pairwise_workspace_bytes).
 #pragma once
 #include "common.hpp"
@@ -90,7 +90,7 @@ __device__ __forceinline__ bool stage_members(const SRC mem, const int32_t* __re
         }                                                                 \
     } while (0)
 
-// segments longer than this are walked by a wave per row (k_pair_long, k_pair_all; the table walks of pairwise_table.hip)
+// segments longer than this are walked by a wave per row (k_pair_long, k_pair_all; the table walks of pairwise_table.hip, the kind walks of pairwise_kind.hip)
 #define PW_LONG 512
 
 #define RN_PW_T 256

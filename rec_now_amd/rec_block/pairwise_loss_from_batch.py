@@ -6,15 +6,18 @@ the reference's dense O(B^2) masks are replaced by sort-by-group + segmented pai
 kernels (csrc/scan_sort.hip, csrc/pairwise.hip); pair order, counts and weights are identical to the reference's.
 
 Two execution paths:
-  * fused   -- `pairloss_func` is `bpr_loss_func` (or a functools.partial of it that binds only `factor` / `reduce_mean`) and
-               `label_pair_to_weight_func` is None or a `LabelPairWeightTable`: loss and d(loss)/d(outputs) come out of one
-               kernel, pairs are never materialised;
+  * fused   -- `pairloss_func` is `bpr_loss_func` (or a functools.partial of it that binds only `factor` / `reduce_mean`), or one of
+               `hinge_loss_func` / `squared_hinge_loss_func` / `margin_bpr_loss_func` (or a functools.partial binding only `margin` /
+               `factor` / `reduce_mean`), and `label_pair_to_weight_func` is None or a `LabelPairWeightTable`: loss and
+               d(loss)/d(outputs) come out of one kernel, pairs are never materialised;
   * general -- any other callable: pairs are materialised (bit-exact reference order), labels/outputs are gathered to
                (P,) vectors and the user's callables run on those.  Exact for element-wise callables (what the
                reference's own test uses, tests/rec_block/test_pairwise_loss_from_batch.py:51-53); callables that
                inspect the (B,B) *shape* are not supported.
 """
 import functools
+import math
+import numbers
 
 import torch
 
@@ -90,6 +93,57 @@ def bpr_loss_func(outputs_pos, outputs_neg, weights=None, factor=1.0, reduce_mea
     """BPR / logistic pair loss on explicit vectors (reference :96-127):
     sum(w * softplus(-factor*(pos-neg))) / (P + 1e-10)   (raw sum when reduce_mean=False).  weights are constants."""
     return _BprVec.apply(outputs_pos, outputs_neg, weights, factor, reduce_mean)
+
+
+_KIND_HINGE, _KIND_SQUARED_HINGE, _KIND_MARGIN_LOGISTIC = 1, 2, 3      # RECNOW_PAIR_KIND_* of include/recnow.h
+
+
+def _finite_number(value, what):
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value):
+        raise ValueError('%s must be a finite Python number, got %r' % (what, value))
+    return float(value)
+
+
+def _kind_loss_vec(kind, outputs_pos, outputs_neg, weights, margin, factor, reduce_mean):
+    """sum(weights * f(margin - factor * (pos - neg))) [/ (P + 1e-10)] in plain torch ops on the tensors' own device: what the general
+    route runs when one of the three functions below reaches it inside a lambda.  Not a hot path (`pairwise_loss` fuses the functions
+    themselves and never comes here)."""
+    margin, factor = _finite_number(margin, 'margin'), _finite_number(factor, 'factor')
+    u = margin - factor * (outputs_pos - outputs_neg)
+    if kind == _KIND_HINGE:
+        losses = torch.relu(u)                                     # subgradient 0 at u == 0
+    elif kind == _KIND_SQUARED_HINGE:
+        losses = torch.relu(u) ** 2
+    else:
+        losses = torch.nn.functional.softplus(u)
+    n = losses.numel()
+    if weights is not None:
+        losses = losses * torch.as_tensor(weights).detach()        # weights are constants
+    loss = losses.sum()
+    if reduce_mean:
+        loss = loss / (float(n) + SMALL_POSIVITE_FLOAT)
+    return loss
+
+
+def hinge_loss_func(outputs_pos, outputs_neg, weights=None, margin=1.0, factor=1.0, reduce_mean=True):
+    """Margin ranking (hinge) pair loss on explicit vectors, with the calling convention of `bpr_loss_func`:
+    sum(w * max(margin - factor*(pos-neg), 0)) / (P + 1e-10)   (raw sum when reduce_mean=False); P counts every pair, also those whose
+    term is 0.  weights are constants; the subgradient at the kink is 0.  As `pairloss_func` of `pairwise_loss` it stays on the fused route."""
+    return _kind_loss_vec(_KIND_HINGE, outputs_pos, outputs_neg, weights, margin, factor, reduce_mean)
+
+
+def squared_hinge_loss_func(outputs_pos, outputs_neg, weights=None, margin=1.0, factor=1.0, reduce_mean=True):
+    """Squared hinge pair loss: sum(w * max(margin - factor*(pos-neg), 0)**2) / (P + 1e-10); otherwise as `hinge_loss_func`."""
+    return _kind_loss_vec(_KIND_SQUARED_HINGE, outputs_pos, outputs_neg, weights, margin, factor, reduce_mean)
+
+
+def margin_bpr_loss_func(outputs_pos, outputs_neg, weights=None, margin=1.0, factor=1.0, reduce_mean=True):
+    """BPR / logistic pair loss with a margin: sum(w * softplus(margin - factor*(pos-neg))) / (P + 1e-10); otherwise as `hinge_loss_func`."""
+    return _kind_loss_vec(_KIND_MARGIN_LOGISTIC, outputs_pos, outputs_neg, weights, margin, factor, reduce_mean)
+
+
+_KIND_NAME_OF_FUNC = {hinge_loss_func: 'hinge', squared_hinge_loss_func: 'squared_hinge', margin_bpr_loss_func: 'margin_bpr'}
+_KIND_OF_NAME = {'hinge': _KIND_HINGE, 'squared_hinge': _KIND_SQUARED_HINGE, 'margin_bpr': _KIND_MARGIN_LOGISTIC}
 
 
 def occurance_power_weight(group_id, power=0.0):
@@ -320,6 +374,50 @@ class _PairBprTable(torch.autograd.Function):
         return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None
 
 
+class _PairKindFused(torch.autograd.Function):
+    """The fused route of hinge_loss_func / squared_hinge_loss_func / margin_bpr_loss_func (csrc/pairwise_kind.hip): the counting entry of the
+    pair rule -- recnow_pair_table_count with a LabelPairWeightTable, recnow_pair_count for label_i > label_j -- then recnow_pair_kind_fwdbwd
+    on the same workspace.  No host synchronisation, nothing sized by the number of pairs."""
+
+    @staticmethod
+    def forward(ctx, outputs, labels, mask, seg, table, wrong, kind, margin, factor, power, reduce_mean, want_np=True):
+        B, dev = seg.B, seg.device
+        ctx.want_np = bool(want_np)
+        scores = _flat_f32(outputs, B, 'outputs')
+        labs = _flat_f32(labels, B, 'labels')
+        m = _flat_mask(mask, B)
+        st = _lib.stream()
+        if table is not None:
+            vals, w = table.on_device(dev)
+            K = table.n_values
+            flags = _FLAG_WRONG_ORDER if wrong else 0
+            cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+            cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
+            n_pair = torch.empty(1, dtype=torch.int64, device=dev)
+            ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), dev)
+            _lib.call('recnow_pair_table_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
+                      _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(vals), K, _lib.ptr(w), _lib.ptr(cnt_row),
+                      _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
+        else:
+            vals, w, K = None, None, 0
+            flags = _FLAG_LABEL_GT | (_FLAG_WRONG_ORDER if wrong else 0)
+            _, cnt_super, n_pair, ws = _count(scores, labs, m, seg, flags)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
+        _lib.call('recnow_pair_kind_fwdbwd', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
+                  _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super), _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED,
+                  int(kind), float(margin), _lib.ptr(vals), K, _lib.ptr(w), float(factor), float(power), 1 if reduce_mean else 0,
+                  _lib.ptr(loss), _lib.ptr(dscores), _lib.ptr(ws), ws.numel(), st)
+        ctx.save_for_backward(dscores[:B])
+        ctx.shape = outputs.shape
+        return loss, _n_pair_out(ctx, n_pair)
+
+    @staticmethod
+    def backward(ctx, g, _g_np):
+        (dscores,) = ctx.saved_tensors
+        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None, None, None
+
+
 class _PairBprSmall(torch.autograd.Function):
     """B <= 8192 rows, one float32 / int32 group tensor: keys, grouping and member packing in ONE launch
     (recnow_group_pack_small), then the counting and loss kernels of the general route on the packed members."""
@@ -441,15 +539,27 @@ def group_rows(groups):
 
 
 def pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair=False, click_occurance_power=0.0, mask=None,
-                        factor=1.0, reduce_mean=True, segments=None, return_num_pair=True, label_pair_weights=None):
-    """Fused BPR pairwise loss; returns (loss, n_pair) as 0-dim tensors, no host sync.  `pairwise_loss` routes here
+                        factor=1.0, reduce_mean=True, segments=None, return_num_pair=True, label_pair_weights=None, *, kind=None, margin=0.0):
+    """Fused pairwise loss; returns (loss, n_pair) as 0-dim tensors, no host sync.  `pairwise_loss` routes here
     whenever the defaults make it possible; exposed because it also accepts `factor` / `reduce_mean` and a precomputed
     `segments=group_rows(groups)` (then `groups` is not looked at again).  return_num_pair=False: the second value is None (the
     float32 conversion of the pair count is a kernel of its own).  label_pair_weights: a `LabelPairWeightTable` in place of the
-    default rule "label_i > label_j, weight 1"."""
+    default rule "label_i > label_j, weight 1".
+    kind (keyword only): None -- the BPR term softplus(-factor (s_i - s_j)), `margin` must stay 0 --, or 'hinge' / 'squared_hinge' /
+    'margin_bpr': the term of `hinge_loss_func` / `squared_hinge_loss_func` / `margin_bpr_loss_func` on u = margin - factor (s_i - s_j)
+    (csrc/pairwise_kind.hip).  margin (keyword only): a finite Python number."""
+    if label_pair_weights is not None and not isinstance(label_pair_weights, LabelPairWeightTable):
+        raise TypeError('label_pair_weights must be a LabelPairWeightTable, got %s' % type(label_pair_weights))
+    if kind is not None:
+        if kind not in _KIND_OF_NAME:
+            raise ValueError("kind must be None, 'hinge', 'squared_hinge' or 'margin_bpr', got %r" % (kind,))
+        margin, factor = _finite_number(margin, 'margin'), _finite_number(factor, 'factor')
+        seg = segments if segments is not None else build_segments(groups)
+        return _PairKindFused.apply(outputs, labels, mask, seg, label_pair_weights, bool(only_use_wrong_order_pair), _KIND_OF_NAME[kind], margin,
+                                    factor, click_occurance_power, reduce_mean, return_num_pair)
+    if margin != 0.0:
+        raise ValueError('margin needs a kind: the BPR term has none')
     if label_pair_weights is not None:
-        if not isinstance(label_pair_weights, LabelPairWeightTable):
-            raise TypeError('label_pair_weights must be a LabelPairWeightTable, got %s' % type(label_pair_weights))
         seg = segments if segments is not None else build_segments(groups)
         return _PairBprTable.apply(outputs, labels, mask, seg, label_pair_weights, _FLAG_WRONG_ORDER if only_use_wrong_order_pair else 0,
                                    factor, click_occurance_power, reduce_mean, return_num_pair)
@@ -478,6 +588,26 @@ def _bpr_options(pairloss_func):
     return None
 
 
+def _kind_options(pairloss_func):
+    """(kind name, margin, factor, reduce_mean) when `pairloss_func` is `hinge_loss_func`, `squared_hinge_loss_func` or `margin_bpr_loss_func`
+    itself, or a functools.partial of one that binds no positional argument and nothing but the keywords `margin` / `factor` /
+    `reduce_mean` -- what csrc/pairwise_kind.hip can compute --, else None.  A bound `margin` / `factor` that is no finite Python number
+    raises ValueError here, as the function itself would on its first call."""
+    func, kw = pairloss_func, {}
+    if isinstance(pairloss_func, functools.partial):
+        if pairloss_func.args or not set(pairloss_func.keywords) <= {'margin', 'factor', 'reduce_mean'}:
+            return None
+        func, kw = pairloss_func.func, pairloss_func.keywords
+    try:
+        name = _KIND_NAME_OF_FUNC.get(func)
+    except TypeError:                       # an unhashable callable
+        return None
+    if name is None:
+        return None
+    return (name, _finite_number(kw.get('margin', 1.0), 'margin'), _finite_number(kw.get('factor', 1.0), 'factor'),
+            bool(kw.get('reduce_mean', True)))
+
+
 def _merge_weights_by_mul(weights1, weights2):
     if weights1 is None:
         return weights2
@@ -501,7 +631,8 @@ def pairwise_loss(outputs, labels, groups,
     conditions, groups[0] = main group for `click_occurance_power`); pairloss_func(outputs_pos, outputs_neg, weights);
     only_use_wrong_order_pair; return_num_pair; click_occurance_power; mask (bool, same shape as labels);
     label_pair_to_weight_func(label_pos, label_neg, **kwargs) -> weights, pairs with weight <= 0 are dropped; a
-    `LabelPairWeightTable` keeps the call on the fused route (with bpr_loss_func, or a functools.partial of it binding factor / reduce_mean).
+    `LabelPairWeightTable` keeps the call on the fused route (with bpr_loss_func, or a functools.partial of it binding factor / reduce_mean;
+    with hinge_loss_func / squared_hinge_loss_func / margin_bpr_loss_func, or a functools.partial of one binding margin / factor / reduce_mean).
     Returns: loss, or (loss, n_pair as float32 tensor) when return_num_pair.
     """
     table = label_pair_to_weight_func if isinstance(label_pair_to_weight_func, LabelPairWeightTable) else None
@@ -511,6 +642,12 @@ def pairwise_loss(outputs, labels, groups,
     if bpr is not None and (label_pair_to_weight_func is None or table is not None):
         loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
                                            factor=bpr[0], reduce_mean=bpr[1], return_num_pair=return_num_pair, label_pair_weights=table)
+        return (loss, n_pair) if return_num_pair else loss
+    kopt = _kind_options(pairloss_func) if (label_pair_to_weight_func is None or table is not None) else None
+    if kopt is not None:
+        loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
+                                           factor=kopt[2], reduce_mean=kopt[3], return_num_pair=return_num_pair, label_pair_weights=table,
+                                           kind=kopt[0], margin=kopt[1])
         return (loss, n_pair) if return_num_pair else loss
 
     # general path: materialise the pair list, then run the user's callables on (P,) vectors

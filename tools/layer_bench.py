@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -157,6 +157,51 @@ def pair_table():
     print('   wall: general / table = %.1fx, table / default = %.2fx' % (ge[0] / t[0], t[0] / d[0]))
     if t[1] and d[1]:
         print('   GPU: table / default = %.2fx; general route wall / table GPU = %.1fx' % (t[1] / d[1], ge[0] / t[1]))
+
+
+def pair_kind():
+    """pairwise_loss with a pair loss other than BPR at the shape of pair_table() (B = 65 536, 1024 groups, four label levels, the table
+    |a - b| + 0.5): hinge_loss_func on the fused route, the same function inside a lambda (the general route: pairs materialised, one host
+    synchronisation -- not capturable, so wall time only), margin_bpr_loss_func on the fused route and the BPR table route as the yardstick.
+    Wall time per forward + backward and GPU time (the step replayed from a HIP graph); the four routes are measured in turn, twice, so the
+    spread between the two passes stands beside every ratio."""
+    from rec_now_amd.rec_block.pairwise_loss_from_batch import (LabelPairWeightTable, hinge_loss_func, margin_bpr_loss_func, pairwise_loss)
+    B, G = 65536, 1024
+    rng = np.random.default_rng(2)
+    g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+    y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+    s = torch.randn(B, device=dev, requires_grad=True)
+    table = LabelPairWeightTable([0.0, 1.0, 2.0, 3.0], lambda a, b: (a - b).abs() + 0.5)
+    rows = (('hinge fused', {'pairloss_func': hinge_loss_func}, True),
+            ('hinge in a lambda (general route)', {'pairloss_func': lambda p, n, w: hinge_loss_func(p, n, w)}, False),
+            ('margin_bpr fused', {'pairloss_func': margin_bpr_loss_func}, True),
+            ('BPR table route', {}, True))
+    res = {tag: [] for tag, _, _ in rows}
+    for run in (1, 2):
+        for tag, kw, capture in rows:
+            npair = [None]
+
+            def step():
+                s.grad = None
+                loss, n = pairwise_loss(s, y, g, return_num_pair=True, label_pair_to_weight_func=table, **kw)
+                loss.backward()
+                npair[0] = n
+            ms = timeit(step)
+            mg = timeit_graph(step) if capture else None
+            res[tag].append((ms, mg))
+            print('run %d  pairwise_loss %s B=%d groups=%d pairs=%d : wall %.3f ms per fwd+bwd, GPU %s' % (
+                run, tag, B, G, float(npair[0].item()), ms,
+                ('%.3f ms (graph replay)' % mg) if mg else 'time not separable (host synchronisation: no capture)'))
+    h, lam, mb, t = (res[tag] for tag, _, _ in rows)
+    for run in (0, 1):
+        line = '   run %d  wall: general / hinge fused = %.1fx' % (run + 1, lam[run][0] / h[run][0])
+        if h[run][1] and mb[run][1] and t[run][1]:
+            line += ';  GPU: hinge / table = %.2fx, margin_bpr / table = %.2fx' % (h[run][1] / t[run][1], mb[run][1] / t[run][1])
+        print(line)
+    print('   spread between the two runs, wall: hinge fused %.3f ms, general %.3f ms' % (abs(h[0][0] - h[1][0]), abs(lam[0][0] - lam[1][0])))
+    if all(r[1] for r in h + mb + t):
+        print('   spread between the two runs, GPU: hinge fused %.4f ms, margin_bpr fused %.4f ms, BPR table route %.4f ms'
+              % (abs(h[0][1] - h[1][1]), abs(mb[0][1] - mb[1][1]), abs(t[0][1] - t[1][1])))
 
 
 def listwise():
@@ -850,6 +895,8 @@ if __name__ == '__main__':
         pairwise(65536, 0, 'config3-skewed (Zipf 1.2 group sizes, cap 2048)')
     if 'pair_table' in which:
         pair_table()
+    if 'pair_kind' in which:
+        pair_kind()
     if 'list' in which:
         listwise()
     if 'cin' in which:
