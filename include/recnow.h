@@ -180,6 +180,35 @@ int recnow_pair_kind_fwdbwd(const float* scores, const float* labels, const uint
                             const float* table, float factor, float power, int reduce_mean, float* loss, float* dscores, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* The NDCG (LambdaRank) pair weight of the fused pairwise loss, and the in-batch NDCG.  A list is one segment; only rows that take part (mask)
+ * are ranked.  Position of row i, from 0:  r_i = #{ j in the list, taking part, j != i : s_j > s_i or (s_j == s_i and j < i) }  (original row
+ * indices break ties, so the positions form a permutation); q_i: the same count on the labels.
+ *   D(r) = 1 / log2(2 + r), and 0 for r >= topn when topn > 0;   G(y) = 2**y - 1 (RECNOW_NDCG_GAIN_EXP2) or y (RECNOW_NDCG_GAIN_LINEAR)
+ *   DCG = sum G(y_i) D(r_i),  IDCG = sum G(y_i) D(q_i) per list (fp64, fixed order),  inv = 1 / IDCG where IDCG > 0, else 0
+ *   lambda_ij = |G(y_i) - G(y_j)| * |D(r_i) - D(r_j)| * inv(list)
+ * recnow_pair_lambda_terms  ranks every row (one compare-only traversal of each segment) and leaves {D(r_i), G(y_i)} and inv per sorted row in
+ *   `ws`.  Outputs, each optional (NULL): rank [B] int32 (-1: the row does not take part), discount / gain / inv_idcg [B] float32, all by
+ *   ORIGINAL row; list_dcg / list_idcg [B] fp64 by segment (the first n_seg entries are written); ndcg_mean [1] = mean of DCG / IDCG over the
+ *   lists with IDCG > 0 (0 when there is none), n_lists [1] = their number.  flags: 0 -- the rows are packed here from scores / labels / mask /
+ *   order --, or RECNOW_PAIR_MEMBERS_PACKED: ws is the workspace recnow_pair_count / recnow_pair_table_count just used on these inputs (scores,
+ *   labels, mask and order are then not looked at).  topn <= 0: no cut-off.  No host synchronisation; bitwise reproducible.
+ * recnow_pair_lambda_fwdbwd  the loss of recnow_pair_kind_fwdbwd (same kinds, pair rules, flags, n_pair / cnt_super and NaN rule; BPR is
+ *   RECNOW_PAIR_KIND_MARGIN_LOGISTIC at margin 0) with every pair's weight multiplied by lambda_ij.  The pair set is untouched: a pair with
+ *   lambda == 0 still counts in n_pair.  flags MUST hold RECNOW_PAIR_MEMBERS_PACKED: ws is the workspace on which the matching count call and then
+ *   recnow_pair_lambda_terms (with RECNOW_PAIR_MEMBERS_PACKED) have just run.
+ * Workspace of both, and of the count call in front of them: recnow_pair_lambda_workspace_bytes(B) (it begins with the pairwise workspace). */
+#define RECNOW_NDCG_GAIN_EXP2 0
+#define RECNOW_NDCG_GAIN_LINEAR 1
+size_t recnow_pair_lambda_workspace_bytes(int64_t B);
+int recnow_pair_lambda_terms(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, const int32_t* seg_id,
+                             const int32_t* seg_first, int64_t B, int flags, int gain, int topn, int32_t* rank, float* discount,
+                             float* gain_out, float* inv_idcg, double* list_dcg, double* list_idcg, float* ndcg_mean, int64_t* n_lists,
+                             void* ws, size_t ws_bytes, void* stream);
+int recnow_pair_lambda_fwdbwd(const int32_t* seg_id, const int32_t* seg_first, const int32_t* super_id, const int64_t* cnt_super,
+                              const int64_t* n_pair, int64_t B, int flags, int kind, float margin, int n_values, const float* table,
+                              float factor, float power, int reduce_mean, float* loss, float* dscores, void* ws, size_t ws_bytes,
+                              void* stream);
+
 /* pairwise_loss(outputs, labels, groups) with the reference's defaults (pairloss_func = bpr_loss_func, click_occurance_power = 0,
  * one group tensor; rec_block/pairwise_loss_from_batch.py:228-279) as ONE call: grouping (the single-launch front end when
  * recnow_pairwise_small_supported, else keys + radix sort + segments), the one-walk loss and the gradient

@@ -24,49 +24,8 @@
 #include "pairwise_walk.hpp"
 #include "pairwise_table.hpp"
 
-// f(u) and f'(u) of one direction.  relu as `u < 0 ? 0 : u`, so that a NaN score of a taking-part row reaches the loss as it does in torch.relu.
-template <int KIND>
-__device__ __forceinline__ void pk_f(float u, float& f, float& df) {
-    if (KIND == RECNOW_PAIR_KIND_HINGE) {
-        f = u < 0.f ? 0.f : u;
-        df = u > 0.f ? 1.f : 0.f;
-    } else if (KIND == RECNOW_PAIR_KIND_SQUARED_HINGE) {
-        const float h = u < 0.f ? 0.f : u;
-        f = h * h;
-        df = h + h;
-    } else {                                                                       // hardware exp2 / log2 / rcp, as bpr_term (pairwise.hip)
-        const float ex = __builtin_amdgcn_exp2f(-1.44269504f * fabsf(u));          // in (0, 1]: 1 + ex is never denormal
-        const float inv = __builtin_amdgcn_rcpf(1.f + ex);
-        f = fmaxf(u, 0.f) + 0.69314718f * __builtin_amdgcn_logf(1.f + ex);         // softplus(u)
-        df = u >= 0.f ? inv : ex * inv;                                            // sigma(u)
-    }
-}
-
-// One candidate, both directions.  The loss term of the backward direction is the other row's forward term: only its derivative is used here
-// (the compiler drops the unused log2).
-template <int KIND>
-__device__ __forceinline__ void pk_term(const Member& me, const Member& o, float wf, float wb, float factor, float margin, float& la, float& ga) {
-    const float d = factor * (me.score - o.score);
-    float ff, dff, fb, dfb;
-    pk_f<KIND>(margin - d, ff, dff);
-    pk_f<KIND>(margin + d, fb, dfb);
-    la += wf > 0.f ? wf * ff : 0.f;
-    ga += (wb > 0.f ? wb * dfb : 0.f) - (wf > 0.f ? wf * dff : 0.f);
-}
-
-// Direction weights of one candidate under the default rule label_i > label_j (weight 1); Member.valid is 0 / 1 here.
-template <int WRONG>
-__device__ __forceinline__ void pk_dirs(const Member& me, const Member& o, bool other, float& wf, float& wb) {
-    const bool both = other && ((me.valid & o.valid & 1) != 0);
-    bool okf = both && (me.label > o.label), okb = both && (o.label > me.label);
-    if (WRONG) {
-        okf = okf && (me.score < o.score);
-        okb = okb && (o.score < me.score);
-    }
-    wf = okf ? 1.f : 0.f;
-    wb = okb ? 1.f : 0.f;
-}
-
+// pk_f, pk_term (one candidate, both directions) and pk_dirs (the default rule's direction weights) live in pairwise_walk.hpp: the walks of
+// pairwise_lambda.hip use them as well.
 #define PK_TW (TABLE ? 2 * PT_MAXV * PT_MAXV : 1)
 
 // ---- long segments: a wave per row (k_pt_long<WRONG, 1> over KIND and TABLE) ------------------------------------------------------------

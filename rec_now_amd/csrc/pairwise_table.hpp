@@ -1,4 +1,4 @@
-// Shared by the table walks of pairwise_table.hip (BPR) and pairwise_kind.hip (hinge, squared hinge, margin-logistic): the class id kept in
+// Shared by the table walks of pairwise_table.hip (BPR), pairwise_kind.hip (hinge, squared hinge, margin-logistic) and pairwise_lambda.hip: the class id kept in
 // Member.valid, the K x K weight table in LDS and the direction weights of one candidate.  The packing, flag and finalize kernels stay in
 // pairwise_table.hip; pairwise_kind.hip launches them through the two host helpers declared at the end.
 #pragma once

@@ -9,7 +9,8 @@ Two execution paths:
   * fused   -- `pairloss_func` is `bpr_loss_func` (or a functools.partial of it that binds only `factor` / `reduce_mean`), or one of
                `hinge_loss_func` / `squared_hinge_loss_func` / `margin_bpr_loss_func` (or a functools.partial binding only `margin` /
                `factor` / `reduce_mean`), and `label_pair_to_weight_func` is None or a `LabelPairWeightTable`: loss and
-               d(loss)/d(outputs) come out of one kernel, pairs are never materialised;
+               d(loss)/d(outputs) come out of one kernel, pairs are never materialised; `lambda_weight=NDCGLambdaWeight(...)` (the
+               LambdaRank pair weight, rec_block/ndcg.py) stays on this route as well (csrc/pairwise_lambda.hip);
   * general -- any other callable: pairs are materialised (bit-exact reference order), labels/outputs are gathered to
                (P,) vectors and the user's callables run on those.  Exact for element-wise callables (what the
                reference's own test uses, tests/rec_block/test_pairwise_loss_from_batch.py:51-53); callables that
@@ -23,6 +24,7 @@ import torch
 
 from .. import _lib
 from ._segments import _as_key_tensor, build_segments
+from .ndcg import NDCGLambdaWeight, lambda_workspace, ndcg_rank_terms, rank_terms_packed
 
 SMALL_POSIVITE_FLOAT = 1.0E-10   # reference :13 (spelling kept)
 
@@ -418,6 +420,53 @@ class _PairKindFused(torch.autograd.Function):
         return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None, None, None
 
 
+class _PairLambdaFused(torch.autograd.Function):
+    """The fused route with an NDCGLambdaWeight (csrc/pairwise_lambda.hip), every call on ONE workspace: the counting entry of the pair rule --
+    recnow_pair_table_count with a LabelPairWeightTable, recnow_pair_count for label_i > label_j --, the rank pre-pass
+    (recnow_pair_lambda_terms) and recnow_pair_lambda_fwdbwd.  BPR is the margin-logistic kind at margin 0.  No pair list, no host
+    synchronisation, nothing sized by the number of pairs."""
+
+    @staticmethod
+    def forward(ctx, outputs, labels, mask, seg, table, wrong, kind, margin, factor, power, reduce_mean, lam, want_np=True):
+        B, dev = seg.B, seg.device
+        ctx.want_np = bool(want_np)
+        scores = _flat_f32(outputs, B, 'outputs')
+        labs = _flat_f32(labels, B, 'labels')
+        m = _flat_mask(mask, B)
+        st = _lib.stream()
+        cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+        cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
+        n_pair = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = lambda_workspace(B, dev)
+        if table is not None:
+            vals, w = table.on_device(dev)
+            K = table.n_values
+            flags = _FLAG_WRONG_ORDER if wrong else 0
+            _lib.call('recnow_pair_table_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
+                      _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(vals), K, _lib.ptr(w), _lib.ptr(cnt_row),
+                      _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
+        else:
+            w, K = None, 0
+            flags = _FLAG_LABEL_GT | (_FLAG_WRONG_ORDER if wrong else 0)
+            _lib.call('recnow_pair_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
+                      _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(cnt_row), _lib.ptr(cnt_super), _lib.ptr(n_pair),
+                      _lib.ptr(ws), ws.numel(), st)
+        rank_terms_packed(seg, ws, lam.gain, lam.topn)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
+        _lib.call('recnow_pair_lambda_fwdbwd', _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super),
+                  _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED, int(kind), float(margin), K, _lib.ptr(w), float(factor), float(power),
+                  1 if reduce_mean else 0, _lib.ptr(loss), _lib.ptr(dscores), _lib.ptr(ws), ws.numel(), st)
+        ctx.save_for_backward(dscores[:B])
+        ctx.shape = outputs.shape
+        return loss, _n_pair_out(ctx, n_pair)
+
+    @staticmethod
+    def backward(ctx, g, _g_np):
+        (dscores,) = ctx.saved_tensors
+        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None, None, None, None
+
+
 class _PairBprSmall(torch.autograd.Function):
     """B <= 8192 rows, one float32 / int32 group tensor: keys, grouping and member packing in ONE launch
     (recnow_group_pack_small), then the counting and loss kernels of the general route on the packed members."""
@@ -539,7 +588,8 @@ def group_rows(groups):
 
 
 def pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair=False, click_occurance_power=0.0, mask=None,
-                        factor=1.0, reduce_mean=True, segments=None, return_num_pair=True, label_pair_weights=None, *, kind=None, margin=0.0):
+                        factor=1.0, reduce_mean=True, segments=None, return_num_pair=True, label_pair_weights=None, *, kind=None, margin=0.0,
+                        lambda_weight=None):
     """Fused pairwise loss; returns (loss, n_pair) as 0-dim tensors, no host sync.  `pairwise_loss` routes here
     whenever the defaults make it possible; exposed because it also accepts `factor` / `reduce_mean` and a precomputed
     `segments=group_rows(groups)` (then `groups` is not looked at again).  return_num_pair=False: the second value is None (the
@@ -547,9 +597,27 @@ def pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair=False
     default rule "label_i > label_j, weight 1".
     kind (keyword only): None -- the BPR term softplus(-factor (s_i - s_j)), `margin` must stay 0 --, or 'hinge' / 'squared_hinge' /
     'margin_bpr': the term of `hinge_loss_func` / `squared_hinge_loss_func` / `margin_bpr_loss_func` on u = margin - factor (s_i - s_j)
-    (csrc/pairwise_kind.hip).  margin (keyword only): a finite Python number."""
+    (csrc/pairwise_kind.hip).  margin (keyword only): a finite Python number.
+    lambda_weight (keyword only): None, or an `NDCGLambdaWeight` -- every pair's weight is multiplied by the LambdaRank weight |delta NDCG| of
+    the pair (rec_block/ndcg.py); the pair set, the pair count and the occurrence counts stay what they are without it.  The call then takes
+    the segments route: count, rank pre-pass, lambda walk (csrc/pairwise_lambda.hip)."""
     if label_pair_weights is not None and not isinstance(label_pair_weights, LabelPairWeightTable):
         raise TypeError('label_pair_weights must be a LabelPairWeightTable, got %s' % type(label_pair_weights))
+    if lambda_weight is not None:
+        if not isinstance(lambda_weight, NDCGLambdaWeight):
+            raise TypeError('lambda_weight must be an NDCGLambdaWeight, got %s' % type(lambda_weight))
+        if kind is None:
+            if margin != 0.0:
+                raise ValueError('margin needs a kind: the BPR term has none')
+            kind_code, margin = _KIND_MARGIN_LOGISTIC, 0.0            # softplus(-factor (s_i - s_j))
+        else:
+            if kind not in _KIND_OF_NAME:
+                raise ValueError("kind must be None, 'hinge', 'squared_hinge' or 'margin_bpr', got %r" % (kind,))
+            kind_code, margin = _KIND_OF_NAME[kind], _finite_number(margin, 'margin')
+        factor = _finite_number(factor, 'factor')
+        seg = segments if segments is not None else build_segments(groups)
+        return _PairLambdaFused.apply(outputs, labels, mask, seg, label_pair_weights, bool(only_use_wrong_order_pair), kind_code, margin, factor,
+                                      click_occurance_power, reduce_mean, lambda_weight, return_num_pair)
     if kind is not None:
         if kind not in _KIND_OF_NAME:
             raise ValueError("kind must be None, 'hinge', 'squared_hinge' or 'margin_bpr', got %r" % (kind,))
@@ -623,6 +691,7 @@ def pairwise_loss(outputs, labels, groups,
                   click_occurance_power=0.0,
                   mask=None,
                   label_pair_to_weight_func=None,
+                  lambda_weight=None,
                   **kwargs
                   ):
     """Pairwise loss over all in-batch pairs (i, j) of the same group with label_i > label_j (reference :228-279).
@@ -633,21 +702,27 @@ def pairwise_loss(outputs, labels, groups,
     label_pair_to_weight_func(label_pos, label_neg, **kwargs) -> weights, pairs with weight <= 0 are dropped; a
     `LabelPairWeightTable` keeps the call on the fused route (with bpr_loss_func, or a functools.partial of it binding factor / reduce_mean;
     with hinge_loss_func / squared_hinge_loss_func / margin_bpr_loss_func, or a functools.partial of one binding margin / factor / reduce_mean).
+    lambda_weight: None, or an `NDCGLambdaWeight` (rec_block/ndcg.py): the LambdaRank weight |delta NDCG| of each pair, one more factor of
+    the pair's weight beside the rule weight and the occurrence weight; it never changes which pairs exist.  Wherever the call is fused
+    without it, it is fused with it; on the general route the weight is formed for the pair list from `ndcg_rank_terms`.
     Returns: loss, or (loss, n_pair as float32 tensor) when return_num_pair.
     """
+    if lambda_weight is not None and not isinstance(lambda_weight, NDCGLambdaWeight):
+        raise TypeError('lambda_weight must be an NDCGLambdaWeight, got %s' % type(lambda_weight))
     table = label_pair_to_weight_func if isinstance(label_pair_to_weight_func, LabelPairWeightTable) else None
     if table is not None and kwargs:
         raise ValueError('a LabelPairWeightTable took its keyword arguments when it was built; got %s' % sorted(kwargs))
     bpr = _bpr_options(pairloss_func)
     if bpr is not None and (label_pair_to_weight_func is None or table is not None):
         loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
-                                           factor=bpr[0], reduce_mean=bpr[1], return_num_pair=return_num_pair, label_pair_weights=table)
+                                           factor=bpr[0], reduce_mean=bpr[1], return_num_pair=return_num_pair, label_pair_weights=table,
+                                           lambda_weight=lambda_weight)
         return (loss, n_pair) if return_num_pair else loss
     kopt = _kind_options(pairloss_func) if (label_pair_to_weight_func is None or table is not None) else None
     if kopt is not None:
         loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
                                            factor=kopt[2], reduce_mean=kopt[3], return_num_pair=return_num_pair, label_pair_weights=table,
-                                           kind=kopt[0], margin=kopt[1])
+                                           kind=kopt[0], margin=kopt[1], lambda_weight=lambda_weight)
         return (loss, n_pair) if return_num_pair else loss
 
     # general path: materialise the pair list, then run the user's callables on (P,) vectors
@@ -667,6 +742,11 @@ def pairwise_loss(outputs, labels, groups,
         else:
             occ = torch.empty(0, dtype=torch.float32, device=flat_out.device)
         weights = _merge_weights_by_mul(weights, occ)
+    if lambda_weight is not None:
+        terms = ndcg_rank_terms(outputs, labels, groups, mask=mask, gain=lambda_weight.gain, topn=lambda_weight.topn)
+        pl, nl = pos.long(), neg.long()
+        lam = (terms.gain[pl] - terms.gain[nl]).abs() * (terms.discount[pl] - terms.discount[nl]).abs() * terms.inv_idcg[pl]
+        weights = _merge_weights_by_mul(weights, lam)
     if weights is not None:
         weights = weights.detach()                                                              # reference :269-270
     outputs_pos = flat_out[pos.long()]

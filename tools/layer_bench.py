@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -202,6 +202,55 @@ def pair_kind():
     if all(r[1] for r in h + mb + t):
         print('   spread between the two runs, GPU: hinge fused %.4f ms, margin_bpr fused %.4f ms, BPR table route %.4f ms'
               % (abs(h[0][1] - h[1][1]), abs(mb[0][1] - mb[1][1]), abs(t[0][1] - t[1][1])))
+
+
+def pair_lambda():
+    """pairwise_loss with the NDCG (LambdaRank) pair weight at the shape of pair_kind() (B = 65 536, 1024 groups, four label levels, the table
+    |a - b| + 0.5): BPR and hinge_loss_func with `lambda_weight=NDCGLambdaWeight()` on the fused route (count, rank pre-pass, lambda walk), the
+    same two losses without the weight (the existing table routes: the yardstick), and BPR with the weight inside a lambda (the general route:
+    pairs materialised, one host synchronisation -- not capturable, so wall time only).  Wall time per forward + backward and GPU time (the
+    step replayed from a HIP graph); the routes are measured in turn, twice, so the spread between the two passes stands beside every ratio."""
+    from rec_now_amd.rec_block.ndcg import NDCGLambdaWeight
+    from rec_now_amd.rec_block.pairwise_loss_from_batch import (LabelPairWeightTable, bpr_loss_func, hinge_loss_func, pairwise_loss)
+    B, G = 65536, 1024
+    rng = np.random.default_rng(2)
+    g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+    y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+    s = torch.randn(B, device=dev, requires_grad=True)
+    table = LabelPairWeightTable([0.0, 1.0, 2.0, 3.0], lambda a, b: (a - b).abs() + 0.5)
+    lam = NDCGLambdaWeight()
+    rows = (('BPR + lambda fused', {'lambda_weight': lam}, True),
+            ('hinge + lambda fused', {'pairloss_func': hinge_loss_func, 'lambda_weight': lam}, True),
+            ('BPR table route, no lambda', {}, True),
+            ('hinge fused, no lambda', {'pairloss_func': hinge_loss_func}, True),
+            ('BPR + lambda in a lambda (general route)', {'pairloss_func': lambda p, n, w: bpr_loss_func(p, n, w), 'lambda_weight': lam}, False))
+    res = {tag: [] for tag, _, _ in rows}
+    for run in (1, 2):
+        for tag, kw, capture in rows:
+            npair = [None]
+
+            def step():
+                s.grad = None
+                loss, n = pairwise_loss(s, y, g, return_num_pair=True, label_pair_to_weight_func=table, **kw)
+                loss.backward()
+                npair[0] = n
+            ms = timeit(step)
+            mg = timeit_graph(step) if capture else None
+            res[tag].append((ms, mg))
+            print('run %d  pairwise_loss %s B=%d groups=%d pairs=%d : wall %.3f ms per fwd+bwd, GPU %s' % (
+                run, tag, B, G, float(npair[0].item()), ms,
+                ('%.3f ms (graph replay)' % mg) if mg else 'time not separable (host synchronisation: no capture)'))
+    bl, hl, b0, h0, ge = (res[tag] for tag, _, _ in rows)
+    for run in (0, 1):
+        line = '   run %d  wall: BPR lambda / BPR = %.2fx, hinge lambda / hinge = %.2fx, general / BPR lambda fused = %.1fx' % (
+            run + 1, bl[run][0] / b0[run][0], hl[run][0] / h0[run][0], ge[run][0] / bl[run][0])
+        if all(r[run][1] for r in (bl, hl, b0, h0)):
+            line += ';  GPU: BPR lambda / BPR = %.2fx, hinge lambda / hinge = %.2fx' % (bl[run][1] / b0[run][1], hl[run][1] / h0[run][1])
+        print(line)
+    print('   spread between the two runs, wall: BPR lambda fused %.3f ms, general %.3f ms' % (abs(bl[0][0] - bl[1][0]), abs(ge[0][0] - ge[1][0])))
+    if all(r[1] for r in bl + hl + b0 + h0):
+        print('   spread between the two runs, GPU: BPR lambda %.4f ms, hinge lambda %.4f ms, BPR table route %.4f ms, hinge fused %.4f ms'
+              % (abs(bl[0][1] - bl[1][1]), abs(hl[0][1] - hl[1][1]), abs(b0[0][1] - b0[1][1]), abs(h0[0][1] - h0[1][1])))
 
 
 def listwise():
@@ -897,6 +946,8 @@ if __name__ == '__main__':
         pair_table()
     if 'pair_kind' in which:
         pair_kind()
+    if 'pair_lambda' in which:
+        pair_lambda()
     if 'list' in which:
         listwise()
     if 'cin' in which:
