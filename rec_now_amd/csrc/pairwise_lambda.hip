@@ -9,9 +9,9 @@
 //
 //  1. rank pre-pass (k_pl_rank_long, k_pl_rank): the two-route shape and the bounds of the walks of pairwise_kind.hip -- a thread per row from the
 //     workgroup's LDS stage, a wave per row for segments over PW_LONG, global reads for ranges over PW_STAGE.  Per candidate two compares on the
-//     scores, two on the labels and two integer adds; per ROW one fp64 log2 each for D(r) and D(q), rounded to float32 (B evaluations: the
-//     difference D(r_i) - D(r_j) a walk forms is then good to half an ulp of D), the {discount, gain} record beside the member, the position and
-//     the row's fp64 terms G D(r), G D(q).
+//     scores, two on the labels and two integer adds; per ROW one fp64 log2 each for D(r) and D(q); D(r) rounded to float32 (B evaluations: the
+//     difference D(r_i) - D(r_j) a walk forms is then good to half an ulp of D) goes into the {discount, gain} record beside the member, the
+//     unrounded values into the row's fp64 terms G D(r), G D(q); the position.
 //  2. per-segment sums (k_pl_segsum): a workgroup per segment (grid-stride over the segments), 256 threads striding the segment, fp64, fixed
 //     order, no atomics; it writes inv per sorted row.  k_pl_metric (one workgroup): mean of DCG / IDCG over the lists with IDCG > 0 and their
 //     number, in fixed order.  Nothing here synchronises with the host.
@@ -95,10 +95,10 @@ k_pl_rank_long(const Member* __restrict__ mem, const int32_t* __restrict__ seg_i
     }
 }
 
-// D(r) in fp64, rounded once
-__device__ __forceinline__ float pl_discount(int r, int topn) {
-    if (topn > 0 && r >= topn) return 0.f;
-    return (float)(1.0 / log2(2.0 + (double)r));
+// D(r) in fp64: the list sums take it as it is, the record beside the member holds it rounded once
+__device__ __forceinline__ double pl_discount(int r, int topn) {
+    if (topn > 0 && r >= topn) return 0.0;
+    return 1.0 / log2(2.0 + (double)r);
 }
 
 template <int GAIN>
@@ -123,18 +123,18 @@ k_pl_rank(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, co
         q = rq.y;
     }
     const bool takes = (me.valid & 1) != 0;
-    PairAux a;
-    a.discount = 0.f;
-    a.gain = 0.f;
-    float dq = 0.f;
+    double dr = 0.0, dq = 0.0, gn = 0.0;
     if (takes) {
-        a.discount = pl_discount(r, topn);
+        dr = pl_discount(r, topn);
         dq = pl_discount(q, topn);
-        a.gain = GAIN == RECNOW_NDCG_GAIN_LINEAR ? me.label : (float)(exp2((double)me.label) - 1.0);
+        gn = GAIN == RECNOW_NDCG_GAIN_LINEAR ? (double)me.label : exp2((double)me.label) - 1.0;
     }
+    PairAux a;
+    a.discount = (float)dr;
+    a.gain = (float)gn;
     aux[k] = a;
-    td[k] = (double)a.gain * (double)a.discount;
-    tq[k] = (double)a.gain * (double)dq;
+    td[k] = gn * dr;                                // DCG and IDCG are fp64 sums of fp64 terms: not of the float32 records
+    tq[k] = gn * dq;
     if (rank) rank[me.row] = takes ? r : -1;
     if (disc_out) disc_out[me.row] = a.discount;
     if (gain_out) gain_out[me.row] = a.gain;
