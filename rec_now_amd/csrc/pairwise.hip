@@ -6,6 +6,10 @@
 //
 // Integer/latency-bound: the member records (16 B each) of a segment are read by every lane of the segment at the
 // same time (wave-uniform broadcast loads served by L1), work is sum_g n_g^2 candidate compares.
+//
+// This file holds the plain family (pair_ok / bpr_term over four FLAGS: at most one direction of a candidate is a pair): its counting and
+// forward+backward kernels on the two route skeletons of pairwise_walk.hpp, the one-call walk k_pair_all with its own loops, the pair emission,
+// the small-batch front end and every entry point that takes no table, kind or NDCG weight.
 #include "common.hpp"
 #include "scan.hpp"
 #include "group_small.hpp"
@@ -56,62 +60,47 @@ __device__ __forceinline__ void bpr_term(const Member& me, const Member& o, bool
     ga += fwd ? -sg : (bwd ? sg : 0.f);
 }
 
-// ---- long segments: a wave per row ------------------------------------------------------------------
-// One thread per row makes the time of a call the latency of the longest walk: a 2048-row group (the Zipf-skewed batches of
-// SURVEY 8d) is 2048 dependent iterations per lane whatever the rest of the batch looks like.  Rows of segments longer than
-// PW_LONG are therefore walked by a whole wave each -- lanes stride over the members (coalesced 16-byte reads), partial sums
-// are joined by the fixed butterfly of wave_sum, so results stay bitwise reproducible -- and parked per sorted position for
-// the thread-per-row kernels below, which skip the walk of such rows.  A workgroup owns 64 consecutive sorted rows; a segment
-// lying strictly inside them is shorter than 64 rows, so only the first and the last row's segment can be long, and looking at
-// those two decides block-uniformly whether there is anything to do: batches without long groups pay one empty launch.
+// The plain family: what one candidate adds to a row (a pair count, or the BPR terms of bpr_term), and where the row's sums go.  The routes
+// themselves are pw_wave_rows / pw_thread_rows of pairwise_walk.hpp.
+template <int FLAGS>
+struct PairCount : PwPlain {
+    typedef int Row;
+    typedef long long Out;
+    int32_t* long_cnt;
+    PwCountOut out;
+    __device__ __forceinline__ Row begin(const Member&, int64_t, bool) const { return 0; }
+    __device__ __forceinline__ void candidate(Row& cc, const Member& me, const Member& o, bool other, bool, int, int) const {
+        cc += (other && pair_ok<FLAGS>(me, o)) ? 1 : 0;
+    }
+    __device__ __forceinline__ void park(Row& cc, int64_t k, int lane) const { pw_park_count(cc, k, lane, long_cnt); }
+    __device__ __forceinline__ Out finish(Row& cc, const Member& me, int64_t k, bool is_long) const { return out.finish(cc, me, k, is_long); }
+};
+template <int FLAGS>
+struct PairBpr : PwPlain {
+    struct Row { float w, la, ga; };
+    typedef double Out;
+    float factor;
+    float *long_la, *long_ga;
+    PwRowEnd<false, false> end;
+    __device__ __forceinline__ Row begin(const Member&, int64_t k, bool wave) const { return Row{wave ? 1.f : end.weight(k), 0.f, 0.f}; }
+    __device__ __forceinline__ void candidate(Row& r, const Member& me, const Member& o, bool other, bool, int, int) const {
+        bpr_term<FLAGS>(me, o, other, factor, r.la, r.ga);
+    }
+    __device__ __forceinline__ void park(Row& r, int64_t k, int lane) const { pw_park_sums(r.la, r.ga, k, lane, long_la, long_ga); }
+    __device__ __forceinline__ Out finish(Row& r, const Member& me, int64_t k, bool is_long) const { return end.finish(me, k, is_long, r.w, r.la, r.ga, false); }
+};
+
 template <int FLAGS, int MODE>                     // MODE 0: pair counts;  1: BPR loss and gradient terms
 __global__ void __launch_bounds__(256)
 k_pair_long(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, const int32_t* __restrict__ seg_first, int64_t B,
             float factor, int32_t* __restrict__ long_cnt, float* __restrict__ long_la, float* __restrict__ long_ga) {
     __shared__ Member staged[PW_STAGE];
-    const int64_t k0 = (int64_t)blockIdx.x * 64;
-    if (k0 >= B) return;
-    const int64_t kl = min(B, k0 + 64) - 1;
-    const int g0 = seg_id[k0], g1 = seg_id[kl];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // the only segments of these 64 rows that can be long: the first row's and the last row's (everything below is block-uniform)
-    bool staged_used = false;
-    for (int phase = 0; phase < 2; ++phase) {
-        if (phase == 1 && g1 == g0) break;
-        const int g = phase == 0 ? g0 : g1;
-        const int s = seg_first[g], e = seg_first[g + 1];
-        if (e - s <= PW_LONG) continue;
-        // members of the segment through LDS when they fit (32 KB): lanes then read consecutive 16-byte records at LDS speed and
-        // the walk is bound by its ~25 VALU instructions per candidate; from global memory it was bound by the read latency
-        const bool in_lds = e - s <= PW_STAGE;
-        if (in_lds) {
-            if (staged_used) __syncthreads();                       // every wave is done with the first segment
-            for (int i = threadIdx.x; i < e - s; i += 256) staged[i] = mem[s + i];
-            __syncthreads();
-            staged_used = true;
-        }
-        const int64_t ka = k0 > s ? k0 : (int64_t)s, kb = kl < (int64_t)e - 1 ? kl : (int64_t)e - 1;
-        for (int64_t k = ka + w; k <= kb; k += 4) {                 // waves take the segment's rows of this block in turn
-            const Member me = mem[k];
-            int cc = 0;
-            float la = 0.f, ga = 0.f;
-            PW_WALK_STRIDED(in_lds, staged, s, mem, s + lane, e, j, o, {
-                if (MODE != 1) cc += (j != (int)k && pair_ok<FLAGS>(me, o)) ? 1 : 0;
-                if (MODE != 0) bpr_term<FLAGS>(me, o, j != (int)k, factor, la, ga);
-            });
-            if (MODE != 1) {
-                cc = wave_sum(cc);
-                if (lane == 0) long_cnt[k] = cc;
-            }
-            if (MODE != 0) {
-                la = wave_sum(la);
-                ga = wave_sum(ga);
-                if (lane == 0) {
-                    long_la[k] = la;
-                    long_ga[k] = ga;
-                }
-            }
-        }
+    if constexpr (MODE == 0) {
+        const PairCount<FLAGS> p = {{}, long_cnt, {}};
+        pw_wave_rows(mem, seg_id, seg_first, B, staged, p);
+    } else {
+        const PairBpr<FLAGS> p = {{}, factor, long_la, long_ga, {}};
+        pw_wave_rows(mem, seg_id, seg_first, B, staged, p);
     }
 }
 
@@ -123,24 +112,8 @@ k_pair_count(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id,
              unsigned long long* __restrict__ cnt_super, unsigned long long* __restrict__ n_pair) {
     __shared__ long long red[16];
     __shared__ Member staged[PW_STAGE];
-    int sbase;
-    const bool in_lds = stage_members(mem, seg_id, seg_first, B, staged, &sbase);
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    long long c = 0;
-    if (k < B) {
-        const Member me = mem[k];
-        const int g = seg_id[k];
-        const int s = seg_first[g], e = seg_first[g + 1];
-        const bool is_long = e - s > PW_LONG;       // walked by k_pair_long
-        int cc = 0;
-        PW_WALK(in_lds, staged, sbase, mem, (is_long ? e : s), e, j, o, { cc += (j != (int)k && pair_ok<FLAGS>(me, o)) ? 1 : 0; });
-        if (is_long) cc = long_cnt[k];
-        cnt_row[me.row] = cc;
-        if (cc) atomicAdd(&cnt_super[super_id[k]], (unsigned long long)cc);   // integer atomics: order-independent
-        c = cc;
-    }
-    c = block_sum<long long>(c, red);
-    if (threadIdx.x == 0 && c) atomicAdd(n_pair, (unsigned long long)c);
+    const PairCount<FLAGS> p = {{}, nullptr, {long_cnt, cnt_row, super_id, cnt_super}};
+    pw_add_pairs(pw_thread_rows(mem, seg_id, seg_first, B, staged, p), red, n_pair);
 }
 
 // ---- emit ----------------------------------------------------------------------------------------
@@ -184,33 +157,9 @@ k_pair_bpr(const Member* __restrict__ mem, const int32_t* __restrict__ seg_id, c
            float* __restrict__ dscores) {
     __shared__ double red[16];
     __shared__ Member staged[PW_STAGE];
-    int sbase;
-    const bool in_lds = stage_members(mem, seg_id, seg_first, B, staged, &sbase);
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    double lsum = 0.0;
-    if (k < B) {
-        const Member me = mem[k];
-        const int g = seg_id[k];
-        const int s = seg_first[g], e = seg_first[g + 1];
-        float w = 1.f;
-        if (power != 0.f) {
-            const float cnt = (float)cnt_super[super_id[k]];
-            // cnt == 0: this row takes part in no pair, its weight is never used (avoid 0**negative = inf -> inf*0)
-            w = (cnt == 0.f) ? 1.f : ((power == 1.f) ? cnt : powf(cnt, power));
-        }
-        const bool is_long = e - s > PW_LONG;       // walked by k_pair_long
-        float la = 0.f, ga = 0.f;
-        PW_WALK(in_lds, staged, sbase, mem, (is_long ? e : s), e, j, o, { bpr_term<FLAGS>(me, o, j != (int)k, factor, la, ga); });
-        if (is_long) {
-            la = long_la[k];
-            ga = long_ga[k];
-        }
-        const float denom = reduce_mean ? ((float)(*n_pair) + 1.0e-10f) : 1.f;
-        dscores[me.row] = w * factor * ga / denom;
-        lsum = (double)(w * la);
-    }
-    lsum = block_sum<double>(lsum, red);
-    if (threadIdx.x == 0) block_loss[blockIdx.x] = lsum;
+    const PairBpr<FLAGS> p = {{}, factor, nullptr, nullptr,
+                              {super_id, cnt_super, n_pair, nullptr, factor, power, reduce_mean, nullptr, long_la, long_ga, dscores}};
+    pw_store_block_loss(pw_thread_rows(mem, seg_id, seg_first, B, staged, p), red, block_loss);
 }
 
 // One pass for the loss without occurrence weights (click_occurance_power == 0, the default): the pair count of a row and its BPR
@@ -520,10 +469,16 @@ extern "C" size_t recnow_pairwise_workspace_bytes(int64_t B) {
 
 
 // The Member array lives at the start of the pairwise workspace; every entry point re-packs it (B x 16 B).
-static int pack_members(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, int64_t B,
-                        Member* mem, hipStream_t st, int64_t* zero_b = nullptr, int64_t* zero_1 = nullptr) {
+int rn_pack_members(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, int64_t B, Member* mem, hipStream_t st,
+                    int64_t* zero_b, int64_t* zero_1) {
     hipLaunchKernelGGL(k_pack_members, rn_cdiv(B, 256), 256, 0, st, scores, labels, mask, order, B, mem,
                        (unsigned long long*)zero_b, (unsigned long long*)zero_1);
+    RN_LAUNCH_CHECK();
+    return RECNOW_OK;
+}
+
+int rn_loss_finalize(const double* part, int n, const int64_t* n_pair, int reduce_mean, float* loss, hipStream_t st) {
+    hipLaunchKernelGGL(k_loss_finalize, 1, 1024, 0, st, part, n, (const unsigned long long*)n_pair, (int64_t)0, reduce_mean, loss);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
 }
@@ -543,7 +498,7 @@ extern "C" int recnow_pair_count(const float* scores, const float* labels, const
     const PairWs pw = pair_ws(ws, ws_bytes, B);
     Member* mem = pw.mem;
     // RECNOW_PAIR_MEMBERS_PACKED: recnow_group_pack_small has packed the members into `ws` and cleared the counters
-    int rc = (flags & RECNOW_PAIR_MEMBERS_PACKED) ? RECNOW_OK : pack_members(scores, labels, mask, order, B, mem, st, cnt_super, n_pair);      // also clears cnt_super[0..B) and *n_pair
+    int rc = (flags & RECNOW_PAIR_MEMBERS_PACKED) ? RECNOW_OK : rn_pack_members(scores, labels, mask, order, B, mem, st, cnt_super, n_pair);      // also clears cnt_super[0..B) and *n_pair
     if (rc) return rc;
     const int G = rn_cdiv(B, RN_PW_T);
     RN_DISPATCH_LONG(0, mem, seg_id, seg_first, B, 1.f, pw.long_cnt, pw.long_la, pw.long_ga);
@@ -573,7 +528,7 @@ extern "C" int recnow_pair_emit(const float* scores, const float* labels, const 
     if (ws_bytes < recnow_pairwise_workspace_bytes(B)) return RECNOW_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Member* mem = (Member*)ws;
-    int rc = pack_members(scores, labels, mask, order, B, mem, st);
+    int rc = rn_pack_members(scores, labels, mask, order, B, mem, st);
     if (rc) return rc;
     const int G = rn_cdiv(B, RN_PW_T);
     RN_DISPATCH_FLAGS(k_pair_emit, mem, seg_id, seg_first, B, offsets, pos_idx, neg_idx, capacity);
@@ -603,14 +558,13 @@ extern "C" int recnow_pair_bpr_fwdbwd(const float* scores, const float* labels, 
     const int G = rn_cdiv(B, RN_PW_T);
     double* part = pw.part;
     // RECNOW_PAIR_MEMBERS_PACKED: `ws` still holds the members recnow_pair_count packed from these very inputs
-    int rc = (flags & RECNOW_PAIR_MEMBERS_PACKED) ? RECNOW_OK : pack_members(scores, labels, mask, order, B, mem, st);
+    int rc = (flags & RECNOW_PAIR_MEMBERS_PACKED) ? RECNOW_OK : rn_pack_members(scores, labels, mask, order, B, mem, st);
     if (rc) return rc;
     RN_DISPATCH_LONG(1, mem, seg_id, seg_first, B, factor, pw.long_cnt, pw.long_la, pw.long_ga);
     RN_DISPATCH_FLAGS(k_pair_bpr, mem, seg_id, seg_first, super_id, (const unsigned long long*)cnt_super,
                       (const unsigned long long*)n_pair, B, factor, power, reduce_mean, pw.long_la, pw.long_ga, part, dscores);
-    hipLaunchKernelGGL(k_loss_finalize, 1, 1024, 0, st, part, G, (const unsigned long long*)n_pair, (int64_t)0, reduce_mean, loss);
     RN_LAUNCH_CHECK();
-    return RECNOW_OK;
+    return rn_loss_finalize(part, G, n_pair, reduce_mean, loss, st);
 }
 
 // part_out != NULL (library-internal: the loss stage of recnow_dcn_mix_step): the per-workgroup loss partials are NOT summed here -- the caller's next
@@ -639,7 +593,7 @@ int rn_pair_bpr_onepass(const float* scores, const float* labels, const uint8_t*
     if (unpacked) {
         if (!(flags & RN_PAIR_NPAIR_ZEROED)) RN_HIP(hipMemsetAsync(n_pair, 0, sizeof(int64_t), st));
     } else if (!(flags & RECNOW_PAIR_MEMBERS_PACKED)) {
-        rc = pack_members(scores, labels, mask, order, B, pw.mem, st, nullptr, n_pair);
+        rc = rn_pack_members(scores, labels, mask, order, B, pw.mem, st, nullptr, n_pair);
     }
     if (rc) return rc;
     // Four lanes per row while the one-lane grid would leave most of the chip idle (B <= 32 768: at most 128 workgroups).  Measured (tools/layer_bench.py, GPU
