@@ -209,6 +209,38 @@ int recnow_pair_lambda_fwdbwd(const int32_t* seg_id, const int32_t* seg_first, c
                               float factor, float power, int reduce_mean, float* loss, float* dscores, void* ws, size_t ws_bytes,
                               void* stream);
 
+/* In-batch GAUC: the AUC of every list, averaged over the lists, from exact integer pair counts (one compare-only traversal of each segment).
+ * Lists and rows.  A list is one segment of build_segments(groups).  Only rows that take part are looked at.  A row takes part when mask is
+ *   true, or when no mask is given.
+ * Pairs.  For two distinct taking-part rows i, j of one list, (i, j) is a pair
+ *   - under the graded rule (binary == 0), when label_i > label_j: the concordance index for graded labels; for 0/1 labels the AUC;
+ *   - under the binary rule (binary != 0), when label_i > th and not (label_j > th), th = pos_neg_th, a finite float.
+ *   Comparisons are float32 and IEEE: a NaN label is in no pair under the graded rule and is a negative under the binary rule.
+ * Per-row counts, kept by row i as the higher side of the pair, int32:  n_i = number of j for which (i, j) is a pair, c_i = number of pairs
+ *   with s_i > s_j, t_i = number of pairs with s_i == s_j.  A NaN score makes both comparisons false, so that pair counts as discordant.  A
+ *   row that does not take part holds 0, 0, 0.
+ * Per-list counts.  N, C, T are the int64 sums of n_i, c_i, t_i over the list, R is the number of taking-part rows.  The list's AUC is
+ *   (2C + T) / (2N), formed in fp64 from the integers, for lists with N > 0.  Lists with N = 0 have no AUC and are left out of every batch mean.
+ * Batch metric.  sum_L w_L AUC_L / sum_L w_L over the lists with N > 0;  w_L = R (RECNOW_AUC_WEIGHT_ROWS: impressions-weighted GAUC), N
+ *   (RECNOW_AUC_WEIGHT_PAIRS: the pooled share of correctly ordered pairs) or 1 (RECNOW_AUC_WEIGHT_UNIFORM).  0 when no list has N > 0.  The
+ *   sums are fp64 in a fixed order.
+ * Outputs, each optional (NULL): row_n / row_c / row_t [B] int32 by ORIGINAL row; list_n / list_c / list_t / list_rows [B] int64 by segment
+ *   (the first n_seg entries are written); auc [1] float32; weighted_sum / weight_sum [1] fp64 (numerator and denominator of auc);
+ *   n_lists [1] int64 = the number of lists with N > 0.
+ * flags: 0 -- the rows are packed here from scores / labels / mask / order --, or RECNOW_PAIR_MEMBERS_PACKED: ws is the workspace
+ *   recnow_pair_count / recnow_pair_table_count just used on these inputs (scores, labels, mask and order are then not looked at).
+ * Workspace: recnow_pair_auc_workspace_bytes(B) (it begins with the pairwise workspace).  RECNOW_EINVAL: an unknown weight kind, any other flag,
+ *   a non-finite pos_neg_th with binary, NULL segment arrays with B > 0; RECNOW_EWORKSPACE: a workspace that is too small.  B == 0 writes
+ *   auc = 0, zero sums and n_lists = 0.  No host synchronisation; bitwise reproducible. */
+#define RECNOW_AUC_WEIGHT_ROWS 0
+#define RECNOW_AUC_WEIGHT_PAIRS 1
+#define RECNOW_AUC_WEIGHT_UNIFORM 2
+size_t recnow_pair_auc_workspace_bytes(int64_t B);
+int recnow_pair_auc_terms(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, const int32_t* seg_id,
+                          const int32_t* seg_first, int64_t B, int flags, int binary, float pos_neg_th, int weight_kind, int32_t* row_n,
+                          int32_t* row_c, int32_t* row_t, int64_t* list_n, int64_t* list_c, int64_t* list_t, int64_t* list_rows, float* auc,
+                          double* weighted_sum, double* weight_sum, int64_t* n_lists, void* ws, size_t ws_bytes, void* stream);
+
 /* pairwise_loss(outputs, labels, groups) with the reference's defaults (pairloss_func = bpr_loss_func, click_occurance_power = 0,
  * one group tensor; rec_block/pairwise_loss_from_batch.py:228-279) as ONE call: grouping (the single-launch front end when
  * recnow_pairwise_small_supported, else keys + radix sort + segments), the one-walk loss and the gradient

@@ -15,5 +15,6 @@
 // recnow_key_words / recnow_group_keys / recnow_listwise_loss (a version-15 build answers it with RECNOW_EINVAL), fp64 per-list sums (seg_lse, seg_ysum,
 // seg_psum, seg_pdot) in recnow_listwise_segments / _loss_fwdbwd / _dense; 17: recnow_pair_table_count / recnow_pair_table_bpr_fwdbwd
 // (LabelPairWeightTable: the fused pairwise loss with per-label-pair weights); 18: recnow_pair_kind_fwdbwd (hinge, squared-hinge and margin-logistic
-// pair terms on the fused route); 19: recnow_pair_lambda_terms / _fwdbwd / _workspace_bytes (the NDCG pair weight on the fused route, in-batch NDCG).
-extern "C" int recnow_abi_version(void) { return 19; }
+// pair terms on the fused route); 19: recnow_pair_lambda_terms / _fwdbwd / _workspace_bytes (the NDCG pair weight on the fused route, in-batch NDCG);
+// 20: recnow_pair_auc_terms / _workspace_bytes (in-batch GAUC from exact pair counts).
+extern "C" int recnow_abi_version(void) { return 20; }

@@ -56,6 +56,20 @@ def global_listwise_loss(local_loss_sum, local_n_valid):
     return local_loss_sum / denom, stats[0] / denom, stats[1]
 
 
+def global_gauc(weighted_sum, weight_sum, n_lists):
+    """Combine the per-rank parts of `rec_block.auc.in_batch_gauc` (its `weighted_sum`, `weight_sum` and `n_lists`, 0-dim tensors) into the
+    global metric: ONE SUM all-reduce of the three values (as fp64: exact for the list count below 2**53) when `is_dist()`.
+    Returns (gauc, n_lists): gauc = sum of the weighted sums / sum of the weight sums as a 0-dim fp64 tensor, 0 where the weight sum is 0;
+    n_lists as a 0-dim int64 tensor.  Ranks hold whole groups (`shard_rows_by_group`), so every list is counted on exactly one rank with its
+    own weight: the result is the exact global metric, not a mean of per-rank means.  Without a process group it is the local ratio."""
+    stats = torch.stack([weighted_sum.detach().to(torch.float64), weight_sum.detach().to(torch.float64), n_lists.detach().to(torch.float64)])
+    if is_dist():
+        dist.all_reduce(stats, op=dist.ReduceOp.SUM)
+    den = stats[1]
+    gauc = torch.where(den > 0, stats[0] / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+    return gauc, stats[2].to(torch.int64)
+
+
 def gathered_pairwise_loss(outputs, labels, groups, loss_fn=None, **kwargs):
     """The EXACT in-batch pairwise loss for rows that arrive ARBITRARILY sharded (groups split across ranks), SURVEY.md section 8e
     variant C3: one all-gather of the (score, label, group) triples (12 bytes per row: 0.8 MB at B = 65 536), then every rank

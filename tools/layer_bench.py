@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -251,6 +251,69 @@ def pair_lambda():
     if all(r[1] for r in bl + hl + b0 + h0):
         print('   spread between the two runs, GPU: BPR lambda %.4f ms, hinge lambda %.4f ms, BPR table route %.4f ms, hinge fused %.4f ms'
               % (abs(bl[0][1] - bl[1][1]), abs(hl[0][1] - hl[1][1]), abs(b0[0][1] - b0[1][1]), abs(h0[0][1] - h0[1][1])))
+
+
+def pair_auc():
+    """in_batch_gauc at the shape of pair_lambda() (B = 65 536, 1024 groups, four label levels): the fused metric under the graded rule and
+    under the binary rule (pos_neg_th = 1.5), in_batch_ndcg on the same batch as the yardstick (the same single compare-only traversal plus
+    the same kind of segment and metric kernels), and the same metric from pair_indices plus torch ops (pairs materialised, one host
+    synchronisation -- not capturable, so wall time only).  Wall time per call and GPU time (the call replayed from a HIP graph); the routes
+    are measured in turn, twice, so the spread between the two passes stands beside every ratio."""
+    from rec_now_amd.rec_block.auc import in_batch_gauc
+    from rec_now_amd.rec_block.ndcg import in_batch_ndcg
+    from rec_now_amd.rec_block.pairwise_loss_from_batch import pair_indices
+    B, G = 65536, 1024
+    rng = np.random.default_rng(2)
+    g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+    y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+    s = torch.randn(B, device=dev)
+    out = [None]
+
+    def host_route():
+        """impressions-weighted GAUC under the graded rule from the materialised pair list"""
+        pos, neg = pair_indices(s, y, g)
+        pos, neg = pos.long(), neg.long()
+        _, lid = torch.unique(g, return_inverse=True)
+        n_list = int(lid.max().item()) + 1
+        sp, sn, lp = s[pos], s[neg], lid[pos]
+        N = torch.bincount(lp, minlength=n_list).double()
+        C = torch.bincount(lp, weights=(sp > sn).double(), minlength=n_list)
+        T = torch.bincount(lp, weights=(sp == sn).double(), minlength=n_list)
+        R = torch.bincount(lid, minlength=n_list).double()
+        ok = N > 0
+        out[0] = ((R[ok] * (2 * C[ok] + T[ok]) / (2 * N[ok])).sum() / R[ok].sum()).float()
+
+    def fused(**kw):
+        def step():
+            out[0] = in_batch_gauc(s, y, g, **kw).auc
+        return step
+
+    def ndcg():
+        out[0] = in_batch_ndcg(s, y, g)[0]
+    rows = (('in_batch_gauc graded', fused(), True), ('in_batch_gauc pos_neg_th=1.5', fused(pos_neg_th=1.5), True),
+            ('in_batch_ndcg (yardstick)', ndcg, True), ('GAUC graded from pair_indices + torch ops (host route)', host_route, False))
+    res = {tag: [] for tag, _, _ in rows}
+    for run in (1, 2):
+        for tag, step, capture in rows:
+            ms = timeit(step)
+            value = float(out[0].item())
+            mg = timeit_graph(step) if capture else None
+            res[tag].append((ms, mg))
+            print('run %d  %s B=%d groups=%d value=%.7f : wall %.3f ms per call, GPU %s' % (
+                run, tag, B, G, value, ms, ('%.4f ms (graph replay)' % mg) if mg else 'time not separable (host synchronisation: no capture)'))
+    gr, bi, nd, ho = (res[tag] for tag, _, _ in rows)
+    for run in (0, 1):
+        line = '   run %d  wall: host route / gauc graded = %.1fx, gauc graded / ndcg = %.2fx, gauc binary / ndcg = %.2fx' % (
+            run + 1, ho[run][0] / gr[run][0], gr[run][0] / nd[run][0], bi[run][0] / nd[run][0])
+        if all(r[run][1] for r in (gr, bi, nd)):
+            line += ';  GPU: gauc graded / ndcg = %.2fx, gauc binary / ndcg = %.2fx, host route wall / gauc graded GPU = %.1fx' % (
+                gr[run][1] / nd[run][1], bi[run][1] / nd[run][1], ho[run][0] / gr[run][1])
+        print(line)
+    print('   spread between the two runs, wall: gauc graded %.3f ms, gauc binary %.3f ms, ndcg %.3f ms, host route %.3f ms'
+          % tuple(abs(r[0][0] - r[1][0]) for r in (gr, bi, nd, ho)))
+    if all(r[1] for r in gr + bi + nd):
+        print('   spread between the two runs, GPU: gauc graded %.4f ms, gauc binary %.4f ms, ndcg %.4f ms'
+              % tuple(abs(r[0][1] - r[1][1]) for r in (gr, bi, nd)))
 
 
 def listwise():
@@ -948,6 +1011,8 @@ if __name__ == '__main__':
         pair_kind()
     if 'pair_lambda' in which:
         pair_lambda()
+    if 'pair_auc' in which:
+        pair_auc()
     if 'list' in which:
         listwise()
     if 'cin' in which:
