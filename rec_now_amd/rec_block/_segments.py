@@ -1,4 +1,5 @@
-"""Group rows of a mini-batch by id on the GPU: canonical keys -> stable radix sort -> segments.
+"""Group rows of a mini-batch by id on the GPU: canonical keys -> stable radix sort -> segments; and the flat row inputs (scores, labels, mask)
+every entry that walks those segments takes.
 
 Host-side counterpart of `recnow_group_keys` / `recnow_group_segments` (include/recnow.h).  It replaces the dense
 (B,B) mask of /root/reference/rec_now/rec_block/pairwise_loss_from_batch.py:16-74 and `tf.unique_with_counts` of
@@ -10,6 +11,7 @@ from .. import _lib
 
 _KEY_F32, _KEY_F64, _KEY_I32, _KEY_I64 = 0, 1, 2, 3
 _KEY_INF_EQUAL = 256      # RECNOW_KEY_INF_EQUAL: tf.unique equality of float ids (equal infinities are one group, only NaN rows are alone)
+_FLAG_MEMBERS_PACKED = 256      # RECNOW_PAIR_MEMBERS_PACKED: the workspace holds the members an earlier call packed from these very inputs
 
 
 def _as_key_tensor(g):
@@ -90,3 +92,28 @@ def build_segments(groups, inf_equal=False):
               _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(seg.n_seg), _lib.ptr(ws),
               ws.numel(), st)
     return seg
+
+
+def _flat_f32(t, B, what):
+    t = _lib.f32c(t, what).reshape(-1)
+    if t.numel() != B:
+        raise ValueError('%s must have %d elements, got %d' % (what, B, t.numel()))
+    return t
+
+
+def _flat_mask(mask, B):
+    if mask is None:
+        return None
+    _lib.require_gpu(mask, 'mask')
+    m = (mask.reshape(-1) != 0).to(torch.uint8).contiguous()
+    if m.numel() != B:
+        raise ValueError('mask must have %d elements' % B)
+    return m
+
+
+def _inputs(outputs, labels, groups, mask, segments):
+    """(segments, scores, labels, mask) as the library takes them, cut off from autograd: what the metrics and the pair list start from.
+    segments: a precomputed `build_segments(groups)` (`groups` is then not looked at), or None."""
+    seg = segments if segments is not None else build_segments(groups)
+    B = seg.B
+    return seg, _flat_f32(outputs, B, 'outputs').detach(), _flat_f32(labels, B, 'labels').detach(), _flat_mask(mask, B)

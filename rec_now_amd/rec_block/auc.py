@@ -40,7 +40,7 @@ import numbers
 import torch
 
 from .. import _lib
-from ._segments import build_segments
+from ._segments import _inputs
 
 _WEIGHT_CODE = {'rows': 0, 'pairs': 1, 'uniform': 2}          # RECNOW_AUC_WEIGHT_* of include/recnow.h
 
@@ -60,13 +60,6 @@ AUCTerms = collections.namedtuple('AUCTerms', ['row_pairs', 'row_concordant', 'r
 def auc_workspace(B, device):
     """The workspace of recnow_pair_auc_terms; a count call in front of it may share it (recnow_pair_auc_workspace_bytes)."""
     return _lib.workspace(_lib.load().recnow_pair_auc_workspace_bytes(B), device)
-
-
-def _inputs(outputs, labels, groups, mask, segments):
-    from .pairwise_loss_from_batch import _flat_f32, _flat_mask          # (that module imports rec_block modules of its own)
-    seg = segments if segments is not None else build_segments(groups)
-    B = seg.B
-    return seg, _flat_f32(outputs, B, 'outputs').detach(), _flat_f32(labels, B, 'labels').detach(), _flat_mask(mask, B)
 
 
 def _call(seg, scores, labs, m, pos_neg_th, weight, rows, lists, metric):

@@ -18,10 +18,9 @@ import collections
 import torch
 
 from .. import _lib
-from ._segments import build_segments
+from ._segments import _FLAG_MEMBERS_PACKED, _inputs
 
 _GAIN_CODE = {'exp2': 0, 'linear': 1}          # RECNOW_NDCG_GAIN_* of include/recnow.h
-_FLAG_MEMBERS_PACKED = 256                     # RECNOW_PAIR_MEMBERS_PACKED
 
 
 def _check_options(gain, topn):
@@ -74,13 +73,6 @@ def rank_terms_packed(seg, ws, gain, topn):
     _lib.call('recnow_pair_lambda_terms', None, None, None, _lib.ptr(seg.order), _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), seg.B,
               _FLAG_MEMBERS_PACKED, _GAIN_CODE[gain], int(topn or 0), None, None, None, None, None, None, None, None, _lib.ptr(ws), ws.numel(),
               _lib.stream())
-
-
-def _inputs(outputs, labels, groups, mask, segments):
-    from .pairwise_loss_from_batch import _flat_f32, _flat_mask          # (that module imports this one)
-    seg = segments if segments is not None else build_segments(groups)
-    B = seg.B
-    return seg, _flat_f32(outputs, B, 'outputs').detach(), _flat_f32(labels, B, 'labels').detach(), _flat_mask(mask, B)
 
 
 def ndcg_rank_terms(outputs, labels, groups, mask=None, gain='exp2', topn=None, segments=None):

@@ -16,23 +16,22 @@ Two execution paths:
                reference's own test uses, tests/rec_block/test_pairwise_loss_from_batch.py:51-53); callables that
                inspect the (B,B) *shape* are not supported.
 """
+import collections
 import functools
 import math
 import numbers
+import os
 
 import torch
 
 from .. import _lib
-from ._segments import _as_key_tensor, build_segments
+from ._segments import _FLAG_MEMBERS_PACKED, _KEY_F64, _KEY_I64, Segments, _as_key_tensor, _flat_f32, _flat_mask, _inputs, build_segments
 from .ndcg import NDCGLambdaWeight, lambda_workspace, ndcg_rank_terms, rank_terms_packed
 
 SMALL_POSIVITE_FLOAT = 1.0E-10   # reference :13 (spelling kept)
 
-import os as _os
-
-_ONE_CALL = _os.environ.get('RECNOW_PAIR_ONE_CALL', '1') != '0'      # A/B switch: '0' keeps the piecewise host route
+_ONE_CALL = os.environ.get('RECNOW_PAIR_ONE_CALL', '1') != '0'      # A/B switch: '0' keeps the piecewise host route
 _FLAG_LABEL_GT, _FLAG_WRONG_ORDER = 1, 2
-_FLAG_MEMBERS_PACKED = 256          # RECNOW_PAIR_MEMBERS_PACKED: the workspace of _count is handed straight to the loss kernel
 
 
 def _generate_pair_mask(sample_group_idx_var, only_upper_band=False):
@@ -157,46 +156,55 @@ def occurance_power_weight(group_id, power=0.0):
     return w[:seg.B]
 
 
-def _flat_f32(t, B, what):
-    t = _lib.f32c(t, what).reshape(-1)
-    if t.numel() != B:
-        raise ValueError('%s must have %d elements, got %d' % (what, B, t.numel()))
-    return t
+def _pair_flags(table, wrong, label_cond=True):
+    """The predicate flags of a pair rule: a LabelPairWeightTable carries its own label rule, the default rule is label_i > label_j."""
+    return (_FLAG_LABEL_GT if table is None and label_cond else 0) | (_FLAG_WRONG_ORDER if wrong else 0)
 
 
-def _flat_mask(mask, B):
-    if mask is None:
-        return None
-    _lib.require_gpu(mask, 'mask')
-    m = (mask.reshape(-1) != 0).to(torch.uint8).contiguous()
-    if m.numel() != B:
-        raise ValueError('mask must have %d elements' % B)
-    return m
+def _table_args(table, device):
+    """(label_values, n_values, weights) of a LabelPairWeightTable as a library entry takes them; (NULL, 0, NULL) without one."""
+    if table is None:
+        return None, 0, None
+    vals, w = table.on_device(device)
+    return _lib.ptr(vals), table.n_values, _lib.ptr(w)
 
 
-def _count(scores, labels, mask, seg, flags):
+def _pair_workspace(B, device):
+    return _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), device)
+
+
+def _counters(B, device):
+    """(cnt_super, n_pair): the pair counts per main group and of the batch."""
+    return torch.empty(max(B, 1), dtype=torch.int64, device=device), torch.empty(1, dtype=torch.int64, device=device)
+
+
+def _count(seg, scores, labs, m, table, wrong, extra_flags, ws, label_cond=True, counters=None):
+    """The counting entry of the pair rule on `ws` -- recnow_pair_table_count with a LabelPairWeightTable, else recnow_pair_count -- and the
+    only call site of both.  extra_flags: _FLAG_MEMBERS_PACKED after recnow_group_pack_small on the same `ws`, which has then cleared the
+    `counters` (cnt_super, n_pair) as well; without them they are allocated here.  Returns (flags, cnt_row, cnt_super, n_pair): the predicate
+    flags, and the pair counts per row / main group / batch; the members stay packed in `ws` for the loss entry that follows."""
     B, dev = seg.B, seg.device
     cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-    cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
-    n_pair = torch.empty(1, dtype=torch.int64, device=dev)
-    ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), dev)
-    _lib.call('recnow_pair_count', _lib.ptr(scores), _lib.ptr(labels), _lib.ptr(mask), _lib.ptr(seg.order),
-              _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(cnt_row),
-              _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), _lib.stream())
-    return cnt_row, cnt_super, n_pair, ws
+    cnt_super, n_pair = counters if counters is not None else _counters(B, dev)
+    flags = _pair_flags(table, wrong, label_cond)
+    P = _lib.ptr
+    rows = (P(scores), P(labs), P(m), P(seg.order), P(seg.seg_id), P(seg.seg_first), P(seg.super_id), B, flags | extra_flags)
+    outs = (P(cnt_row), P(cnt_super), P(n_pair), P(ws), ws.numel(), _lib.stream())
+    if table is None:
+        _lib.call('recnow_pair_count', *rows, *outs)
+    else:
+        _lib.call('recnow_pair_table_count', *rows, *_table_args(table, dev), *outs)
+    return flags, cnt_row, cnt_super, n_pair
 
 
 def pair_indices(outputs, labels, groups, only_use_wrong_order_pair=False, mask=None, use_label_cond=True):
     """(pos_idx, neg_idx) int32 tensors of the surviving pairs in the reference's order: ascending positive row i,
     then ascending negative row j (= tf.boolean_mask over the row-major flattened (B,B) mask, reference :217,272-273).
     Host-synchronises once to size the output."""
-    seg = build_segments(groups)
+    seg, scores, labs, m = _inputs(outputs, labels, groups, mask, None)
     B = seg.B
-    scores = _flat_f32(outputs, B, 'outputs').detach()
-    labs = _flat_f32(labels, B, 'labels').detach()
-    m = _flat_mask(mask, B)
-    flags = (_FLAG_LABEL_GT if use_label_cond else 0) | (_FLAG_WRONG_ORDER if only_use_wrong_order_pair else 0)
-    cnt_row, _, n_pair, ws = _count(scores, labs, m, seg, flags)
+    ws = _pair_workspace(B, seg.device)
+    flags, cnt_row, _, n_pair = _count(seg, scores, labs, m, None, only_use_wrong_order_pair, 0, ws, label_cond=use_label_cond)
     offsets = torch.empty(B + 1, dtype=torch.int64, device=seg.device)
     _lib.call('recnow_pair_offsets', _lib.ptr(cnt_row), B, _lib.ptr(offsets), _lib.ptr(ws), ws.numel(), _lib.stream())
     P = int(n_pair.item())
@@ -208,21 +216,6 @@ def pair_indices(outputs, labels, groups, only_use_wrong_order_pair=False, mask=
     return pos[:P], neg[:P]
 
 
-def _onepass(ctx, outputs, scores, labs, m, order, seg_id, seg_first, B, dev, flags, factor, reduce_mean, ws, n_pair):
-    """Loss without occurrence weights (click_occurance_power == 0): counts and BPR terms from ONE walk per row
-    (recnow_pair_bpr_onepass); the gradient stays unnormalised until the incoming gradient is multiplied in (backward)."""
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
-    _lib.call('recnow_pair_bpr_onepass', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(order), _lib.ptr(seg_id),
-              _lib.ptr(seg_first), B, flags, float(factor), 1 if reduce_mean else 0, _lib.ptr(loss), _lib.ptr(dscores), _lib.ptr(n_pair),
-              _lib.ptr(ws), ws.numel(), _lib.stream())
-    ctx.save_for_backward(dscores[:B], n_pair)
-    ctx.shape = outputs.shape
-    ctx.onepass = True
-    ctx.reduce_mean = bool(reduce_mean)
-    return loss, _n_pair_out(ctx, n_pair)
-
-
 def _n_pair_out(ctx, n_pair):
     """The pair count as the float32 0-dim tensor the reference returns -- only when the caller asked for it (one conversion kernel
     and its host time less on the default `pairwise_loss(...)` path)."""
@@ -231,48 +224,6 @@ def _n_pair_out(ctx, n_pair):
     n_pair_f = n_pair.to(torch.float32).reshape(())
     ctx.mark_non_differentiable(n_pair_f)
     return n_pair_f
-
-
-def _onepass_backward(ctx, g):
-    dscores, n_pair = ctx.saved_tensors
-    gd = g.detach().to(torch.float32).reshape(1).contiguous()
-    out = torch.empty_like(dscores)
-    _lib.call('recnow_pair_scale_grad', _lib.ptr(dscores), _lib.ptr(gd), _lib.ptr(n_pair) if ctx.reduce_mean else None, 1.0e-10,
-              dscores.numel(), _lib.ptr(out), _lib.stream())
-    return out.reshape(ctx.shape)
-
-
-class _PairBprFused(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, outputs, labels, mask, seg, flags, factor, power, reduce_mean, want_np=True):
-        B = seg.B
-        ctx.want_np = bool(want_np)
-        scores = _flat_f32(outputs, B, 'outputs')
-        labs = _flat_f32(labels, B, 'labels')
-        m = _flat_mask(mask, B)
-        ctx.onepass = False
-        if float(power) == 0.0:
-            n_pair = torch.empty(1, dtype=torch.int64, device=seg.device)
-            ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), seg.device)
-            return _onepass(ctx, outputs, scores, labs, m, seg.order, seg.seg_id, seg.seg_first, B, seg.device, flags, factor,
-                            reduce_mean, ws, n_pair)
-        cnt_row, cnt_super, n_pair, ws = _count(scores, labs, m, seg, flags)
-        loss = torch.empty((), dtype=torch.float32, device=seg.device)
-        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=seg.device)
-        _lib.call('recnow_pair_bpr_fwdbwd', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order),
-                  _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super),
-                  _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED, float(factor), float(power), 1 if reduce_mean else 0, _lib.ptr(loss),
-                  _lib.ptr(dscores), _lib.ptr(ws), ws.numel(), _lib.stream())
-        ctx.save_for_backward(dscores[:B])
-        ctx.shape = outputs.shape
-        return loss, _n_pair_out(ctx, n_pair)
-
-    @staticmethod
-    def backward(ctx, g, _g_np):
-        if ctx.onepass:
-            return _onepass_backward(ctx, g), None, None, None, None, None, None, None, None
-        (dscores,) = ctx.saved_tensors
-        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None
 
 
 class LabelPairWeightTable(object):
@@ -339,178 +290,93 @@ class LabelPairWeightTable(object):
         return torch.where(hit_p.any(-1) & hit_n.any(-1), out, torch.full_like(out, float('nan')))
 
 
-class _PairBprTable(torch.autograd.Function):
-    """The fused route with a LabelPairWeightTable: recnow_pair_table_count (members with class ids, pair counts per row / main group /
-    batch) then recnow_pair_table_bpr_fwdbwd on the same workspace.  No host synchronisation, nothing sized by the number of pairs."""
+# What a fused call computes, apart from its rows and their grouping.  table: a LabelPairWeightTable or None (label_i > label_j); wrong:
+# only_use_wrong_order_pair; kind: a _KIND_* code, or None for the BPR term; lam: an NDCGLambdaWeight or None (then kind is never None: BPR is
+# the margin-logistic kind at margin 0 there); power: click_occurance_power.
+_PairPlan = collections.namedtuple('_PairPlan', ['table', 'wrong', 'kind', 'margin', 'factor', 'power', 'reduce_mean', 'lam'])
+
+
+def _pack_small(gkey, gdt, scores, labs, m, counters, ws):
+    """Keys, grouping and member packing of B <= 8192 rows of one float32 / int32 group tensor in ONE launch (recnow_group_pack_small); it
+    clears `counters` as well, so what follows on `ws` runs with _FLAG_MEMBERS_PACKED.  Returns the Segments."""
+    seg = Segments()
+    B, dev = gkey.numel(), gkey.device
+    seg.B, seg.device = B, dev
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)      # noqa: E731
+    seg.order, seg.seg_id, seg.seg_first, seg.super_id, seg.n_seg = i32(max(B, 1)), i32(max(B, 1)), i32(B + 1), i32(max(B, 1)), i32(2)
+    _lib.call('recnow_group_pack_small', _lib.ptr(gkey), gdt, _lib.ptr(labs), _lib.ptr(scores), _lib.ptr(m), B, _lib.ptr(seg.order),
+              _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(seg.n_seg), _lib.ptr(counters[0]),
+              _lib.ptr(counters[1]), _lib.ptr(ws), ws.numel(), _lib.stream())
+    return seg
+
+
+class _PairFused(torch.autograd.Function):
+    """Every fused route that walks segments.  grouping: a Segments, or the (key tensor, dtype code) of `_small_route`, grouped here by
+    `_pack_small`.  plan: a _PairPlan.  Then, all on ONE workspace, with no host synchronisation and nothing sized by the number of pairs:
+      * plain BPR without occurrence weights (power == 0): counts and terms from ONE walk per row (recnow_pair_bpr_onepass); the gradient stays
+        unnormalised until backward multiplies the incoming gradient in (recnow_pair_scale_grad);
+      * otherwise `_count`, the rank pre-pass (recnow_pair_lambda_terms) when the plan has a lambda weight, and the one loss entry of the
+        plan: recnow_pair_lambda_fwdbwd, recnow_pair_kind_fwdbwd, recnow_pair_table_bpr_fwdbwd or recnow_pair_bpr_fwdbwd, on the packed
+        members the count left behind.  The lambda route's workspace is the larger one of its walk, from the count on."""
 
     @staticmethod
-    def forward(ctx, outputs, labels, mask, seg, table, flags, factor, power, reduce_mean, want_np=True):
-        B, dev = seg.B, seg.device
+    def forward(ctx, outputs, labels, mask, grouping, plan, want_np=True):
+        small = not isinstance(grouping, Segments)
+        B, dev = (grouping[0].numel(), grouping[0].device) if small else (grouping.B, grouping.device)
         ctx.want_np = bool(want_np)
-        scores = _flat_f32(outputs, B, 'outputs')
-        labs = _flat_f32(labels, B, 'labels')
-        m = _flat_mask(mask, B)
-        vals, w = table.on_device(dev)
-        K = table.n_values
-        cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-        cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
-        n_pair = torch.empty(1, dtype=torch.int64, device=dev)
-        ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), dev)
-        st = _lib.stream()
-        _lib.call('recnow_pair_table_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
-                  _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(vals), K, _lib.ptr(w), _lib.ptr(cnt_row),
-                  _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
-        _lib.call('recnow_pair_table_bpr_fwdbwd', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
-                  _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super), _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED,
-                  _lib.ptr(vals), K, _lib.ptr(w), float(factor), float(power), 1 if reduce_mean else 0, _lib.ptr(loss), _lib.ptr(dscores),
-                  _lib.ptr(ws), ws.numel(), st)
-        ctx.save_for_backward(dscores[:B])
         ctx.shape = outputs.shape
-        return loss, _n_pair_out(ctx, n_pair)
-
-    @staticmethod
-    def backward(ctx, g, _g_np):
-        (dscores,) = ctx.saved_tensors
-        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None
-
-
-class _PairKindFused(torch.autograd.Function):
-    """The fused route of hinge_loss_func / squared_hinge_loss_func / margin_bpr_loss_func (csrc/pairwise_kind.hip): the counting entry of the
-    pair rule -- recnow_pair_table_count with a LabelPairWeightTable, recnow_pair_count for label_i > label_j -- then recnow_pair_kind_fwdbwd
-    on the same workspace.  No host synchronisation, nothing sized by the number of pairs."""
-
-    @staticmethod
-    def forward(ctx, outputs, labels, mask, seg, table, wrong, kind, margin, factor, power, reduce_mean, want_np=True):
-        B, dev = seg.B, seg.device
-        ctx.want_np = bool(want_np)
         scores = _flat_f32(outputs, B, 'outputs')
         labs = _flat_f32(labels, B, 'labels')
         m = _flat_mask(mask, B)
-        st = _lib.stream()
-        if table is not None:
-            vals, w = table.on_device(dev)
-            K = table.n_values
-            flags = _FLAG_WRONG_ORDER if wrong else 0
-            cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-            cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
-            n_pair = torch.empty(1, dtype=torch.int64, device=dev)
-            ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), dev)
-            _lib.call('recnow_pair_table_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
-                      _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(vals), K, _lib.ptr(w), _lib.ptr(cnt_row),
-                      _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
+        table, lam = plan.table, plan.lam
+        ws = lambda_workspace(B, dev) if lam is not None else _pair_workspace(B, dev)
+        ctx.onepass = plan.kind is None and table is None and float(plan.power) == 0.0
+        counters, packed = None, 0
+        if small:
+            counters, packed = _counters(B, dev), _FLAG_MEMBERS_PACKED
+            seg = _pack_small(grouping[0], grouping[1], scores, labs, m, counters, ws)
         else:
-            vals, w, K = None, None, 0
-            flags = _FLAG_LABEL_GT | (_FLAG_WRONG_ORDER if wrong else 0)
-            _, cnt_super, n_pair, ws = _count(scores, labs, m, seg, flags)
+            seg = grouping
+        P, st = _lib.ptr, _lib.stream()
+        rows = (P(scores), P(labs), P(m), P(seg.order))
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
-        _lib.call('recnow_pair_kind_fwdbwd', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
-                  _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super), _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED,
-                  int(kind), float(margin), _lib.ptr(vals), K, _lib.ptr(w), float(factor), float(power), 1 if reduce_mean else 0,
-                  _lib.ptr(loss), _lib.ptr(dscores), _lib.ptr(ws), ws.numel(), st)
-        ctx.save_for_backward(dscores[:B])
-        ctx.shape = outputs.shape
-        return loss, _n_pair_out(ctx, n_pair)
-
-    @staticmethod
-    def backward(ctx, g, _g_np):
-        (dscores,) = ctx.saved_tensors
-        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None, None, None
-
-
-class _PairLambdaFused(torch.autograd.Function):
-    """The fused route with an NDCGLambdaWeight (csrc/pairwise_lambda.hip), every call on ONE workspace: the counting entry of the pair rule --
-    recnow_pair_table_count with a LabelPairWeightTable, recnow_pair_count for label_i > label_j --, the rank pre-pass
-    (recnow_pair_lambda_terms) and recnow_pair_lambda_fwdbwd.  BPR is the margin-logistic kind at margin 0.  No pair list, no host
-    synchronisation, nothing sized by the number of pairs."""
-
-    @staticmethod
-    def forward(ctx, outputs, labels, mask, seg, table, wrong, kind, margin, factor, power, reduce_mean, lam, want_np=True):
-        B, dev = seg.B, seg.device
-        ctx.want_np = bool(want_np)
-        scores = _flat_f32(outputs, B, 'outputs')
-        labs = _flat_f32(labels, B, 'labels')
-        m = _flat_mask(mask, B)
-        st = _lib.stream()
-        cnt_row = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-        cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
-        n_pair = torch.empty(1, dtype=torch.int64, device=dev)
-        ws = lambda_workspace(B, dev)
-        if table is not None:
-            vals, w = table.on_device(dev)
-            K = table.n_values
-            flags = _FLAG_WRONG_ORDER if wrong else 0
-            _lib.call('recnow_pair_table_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
-                      _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(vals), K, _lib.ptr(w), _lib.ptr(cnt_row),
-                      _lib.ptr(cnt_super), _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
-        else:
-            w, K = None, 0
-            flags = _FLAG_LABEL_GT | (_FLAG_WRONG_ORDER if wrong else 0)
-            _lib.call('recnow_pair_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(seg.order), _lib.ptr(seg.seg_id),
-                      _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), B, flags, _lib.ptr(cnt_row), _lib.ptr(cnt_super), _lib.ptr(n_pair),
-                      _lib.ptr(ws), ws.numel(), st)
-        rank_terms_packed(seg, ws, lam.gain, lam.topn)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
-        _lib.call('recnow_pair_lambda_fwdbwd', _lib.ptr(seg.seg_id), _lib.ptr(seg.seg_first), _lib.ptr(seg.super_id), _lib.ptr(cnt_super),
-                  _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED, int(kind), float(margin), K, _lib.ptr(w), float(factor), float(power),
-                  1 if reduce_mean else 0, _lib.ptr(loss), _lib.ptr(dscores), _lib.ptr(ws), ws.numel(), st)
-        ctx.save_for_backward(dscores[:B])
-        ctx.shape = outputs.shape
-        return loss, _n_pair_out(ctx, n_pair)
-
-    @staticmethod
-    def backward(ctx, g, _g_np):
-        (dscores,) = ctx.saved_tensors
-        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None, None, None, None
-
-
-class _PairBprSmall(torch.autograd.Function):
-    """B <= 8192 rows, one float32 / int32 group tensor: keys, grouping and member packing in ONE launch
-    (recnow_group_pack_small), then the counting and loss kernels of the general route on the packed members."""
-
-    @staticmethod
-    def forward(ctx, outputs, labels, mask, gkey, gdt, flags, factor, power, reduce_mean, want_np=True):
-        B = gkey.numel()
-        ctx.want_np = bool(want_np)
-        scores = _flat_f32(outputs, B, 'outputs')
-        labs = _flat_f32(labels, B, 'labels')
-        m = _flat_mask(mask, B)
-        dev = gkey.device
-        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)      # noqa: E731
-        order, seg_id, seg_first, super_id, n_seg = i32(max(B, 1)), i32(max(B, 1)), i32(B + 1), i32(max(B, 1)), i32(2)
-        cnt_row = i32(max(B, 1))
-        cnt_super = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
-        n_pair = torch.empty(1, dtype=torch.int64, device=dev)
-        ws = _lib.workspace(_lib.load().recnow_pairwise_workspace_bytes(B), dev)
-        st = _lib.stream()
-        _lib.call('recnow_group_pack_small', _lib.ptr(gkey), gdt, _lib.ptr(labs), _lib.ptr(scores), _lib.ptr(m), B, _lib.ptr(order),
-                  _lib.ptr(seg_id), _lib.ptr(seg_first), _lib.ptr(super_id), _lib.ptr(n_seg), _lib.ptr(cnt_super), _lib.ptr(n_pair),
-                  _lib.ptr(ws), ws.numel(), st)
-        ctx.onepass = False
-        if float(power) == 0.0:
-            return _onepass(ctx, outputs, scores, labs, m, order, seg_id, seg_first, B, dev, flags | _FLAG_MEMBERS_PACKED, factor,
-                            reduce_mean, ws, n_pair)
-        _lib.call('recnow_pair_count', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(order), _lib.ptr(seg_id),
-                  _lib.ptr(seg_first), _lib.ptr(super_id), B, flags | _FLAG_MEMBERS_PACKED, _lib.ptr(cnt_row), _lib.ptr(cnt_super),
-                  _lib.ptr(n_pair), _lib.ptr(ws), ws.numel(), st)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dscores = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
-        _lib.call('recnow_pair_bpr_fwdbwd', _lib.ptr(scores), _lib.ptr(labs), _lib.ptr(m), _lib.ptr(order), _lib.ptr(seg_id),
-                  _lib.ptr(seg_first), _lib.ptr(super_id), _lib.ptr(cnt_super), _lib.ptr(n_pair), B, flags | _FLAG_MEMBERS_PACKED,
-                  float(factor), float(power), 1 if reduce_mean else 0, _lib.ptr(loss), _lib.ptr(dscores), _lib.ptr(ws), ws.numel(), st)
-        ctx.save_for_backward(dscores[:B])
-        ctx.shape = outputs.shape
-        return loss, _n_pair_out(ctx, n_pair)
-
-    @staticmethod
-    def backward(ctx, g, _g_np):
+        rm = 1 if plan.reduce_mean else 0
         if ctx.onepass:
-            return _onepass_backward(ctx, g), None, None, None, None, None, None, None, None, None
-        (dscores,) = ctx.saved_tensors
-        return (dscores * g).reshape(ctx.shape), None, None, None, None, None, None, None, None, None
+            n_pair = counters[1] if small else torch.empty(1, dtype=torch.int64, device=dev)
+            _lib.call('recnow_pair_bpr_onepass', *rows, P(seg.seg_id), P(seg.seg_first), B, _pair_flags(None, plan.wrong) | packed,
+                      float(plan.factor), rm, P(loss), P(dscores), P(n_pair), P(ws), ws.numel(), st)
+            ctx.save_for_backward(dscores[:B], n_pair)
+            ctx.reduce_mean = bool(plan.reduce_mean)
+            return loss, _n_pair_out(ctx, n_pair)
+        flags, _, cnt_super, n_pair = _count(seg, scores, labs, m, table, plan.wrong, packed, ws, counters=counters)
+        segs = (P(seg.seg_id), P(seg.seg_first), P(seg.super_id), P(cnt_super), P(n_pair), B, flags | _FLAG_MEMBERS_PACKED)
+        outs = (float(plan.factor), float(plan.power), rm, P(loss), P(dscores), P(ws), ws.numel(), st)
+        targs = _table_args(table, dev)
+        if lam is not None:
+            rank_terms_packed(seg, ws, lam.gain, lam.topn)
+            _lib.call('recnow_pair_lambda_fwdbwd', *segs, int(plan.kind), float(plan.margin), targs[1], targs[2], *outs)
+        elif plan.kind is not None:
+            _lib.call('recnow_pair_kind_fwdbwd', *rows, *segs, int(plan.kind), float(plan.margin), *targs, *outs)
+        elif table is not None:         # its own entry, not the kind entry at margin 0
+            _lib.call('recnow_pair_table_bpr_fwdbwd', *rows, *segs, *targs, *outs)
+        else:
+            _lib.call('recnow_pair_bpr_fwdbwd', *rows, *segs, *outs)
+        ctx.save_for_backward(dscores[:B])
+        return loss, _n_pair_out(ctx, n_pair)
+
+    @staticmethod
+    def backward(ctx, g, _g_np):
+        saved = ctx.saved_tensors
+        dscores = saved[0]
+        if ctx.onepass:
+            gd = g.detach().to(torch.float32).reshape(1).contiguous()
+            grad = torch.empty_like(dscores)
+            _lib.call('recnow_pair_scale_grad', _lib.ptr(dscores), _lib.ptr(gd), _lib.ptr(saved[1]) if ctx.reduce_mean else None, 1.0e-10,
+                      dscores.numel(), _lib.ptr(grad), _lib.stream())
+        else:
+            grad = dscores * g
+        return grad.reshape(ctx.shape), None, None, None, None, None
 
 
 class _PairLossOneCall(torch.autograd.Function):
@@ -565,19 +431,10 @@ def _one_call_route(groups):
 
 def _small_route(groups):
     """(key tensor, dtype code) when the single-launch route applies: one group tensor of B <= 8192 float / int32-able ids."""
-    if isinstance(groups, (list, tuple)):
-        if len(groups) != 1:
-            return None
-        groups = groups[0]
-    if not isinstance(groups, torch.Tensor) or not groups.is_cuda or groups.dtype in (torch.float64, torch.int64):
+    one = _one_call_route(groups)
+    if one is None or one[1] in (_KEY_F64, _KEY_I64) or not _lib.load().recnow_pairwise_small_supported(one[0].numel(), one[1]):
         return None
-    try:
-        key, dt = _as_key_tensor(groups)
-    except TypeError:
-        return None
-    if not _lib.load().recnow_pairwise_small_supported(key.numel(), dt):
-        return None
-    return key, dt
+    return one
 
 
 def group_rows(groups):
@@ -600,49 +457,37 @@ def pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair=False
     (csrc/pairwise_kind.hip).  margin (keyword only): a finite Python number.
     lambda_weight (keyword only): None, or an `NDCGLambdaWeight` -- every pair's weight is multiplied by the LambdaRank weight |delta NDCG| of
     the pair (rec_block/ndcg.py); the pair set, the pair count and the occurrence counts stay what they are without it.  The call then takes
-    the segments route: count, rank pre-pass, lambda walk (csrc/pairwise_lambda.hip)."""
+    the segments route: count, rank pre-pass, lambda walk (csrc/pairwise_lambda.hip).
+    Routes, in this precedence: lambda, kind, table -- each on `segments` or `build_segments(groups)` --, then for plain BPR the one-call
+    entry (power 0, one group tensor, no `segments`), the small route (`_small_route`), the segments route."""
     if label_pair_weights is not None and not isinstance(label_pair_weights, LabelPairWeightTable):
         raise TypeError('label_pair_weights must be a LabelPairWeightTable, got %s' % type(label_pair_weights))
-    if lambda_weight is not None:
-        if not isinstance(lambda_weight, NDCGLambdaWeight):
-            raise TypeError('lambda_weight must be an NDCGLambdaWeight, got %s' % type(lambda_weight))
-        if kind is None:
-            if margin != 0.0:
-                raise ValueError('margin needs a kind: the BPR term has none')
-            kind_code, margin = _KIND_MARGIN_LOGISTIC, 0.0            # softplus(-factor (s_i - s_j))
-        else:
-            if kind not in _KIND_OF_NAME:
-                raise ValueError("kind must be None, 'hinge', 'squared_hinge' or 'margin_bpr', got %r" % (kind,))
-            kind_code, margin = _KIND_OF_NAME[kind], _finite_number(margin, 'margin')
+    if lambda_weight is not None and not isinstance(lambda_weight, NDCGLambdaWeight):
+        raise TypeError('lambda_weight must be an NDCGLambdaWeight, got %s' % type(lambda_weight))
+    if kind is None:
+        if margin != 0.0:
+            raise ValueError('margin needs a kind: the BPR term has none')
+        kind_code = _KIND_MARGIN_LOGISTIC if lambda_weight is not None else None      # the lambda walk: softplus(-factor (s_i - s_j))
+        margin = 0.0
+    elif kind not in _KIND_OF_NAME:
+        raise ValueError("kind must be None, 'hinge', 'squared_hinge' or 'margin_bpr', got %r" % (kind,))
+    else:
+        kind_code, margin = _KIND_OF_NAME[kind], _finite_number(margin, 'margin')
+    if kind_code is not None:          # the kind and lambda entries demand a finite Python number; the BPR entries take float(factor)
         factor = _finite_number(factor, 'factor')
-        seg = segments if segments is not None else build_segments(groups)
-        return _PairLambdaFused.apply(outputs, labels, mask, seg, label_pair_weights, bool(only_use_wrong_order_pair), kind_code, margin, factor,
-                                      click_occurance_power, reduce_mean, lambda_weight, return_num_pair)
-    if kind is not None:
-        if kind not in _KIND_OF_NAME:
-            raise ValueError("kind must be None, 'hinge', 'squared_hinge' or 'margin_bpr', got %r" % (kind,))
-        margin, factor = _finite_number(margin, 'margin'), _finite_number(factor, 'factor')
-        seg = segments if segments is not None else build_segments(groups)
-        return _PairKindFused.apply(outputs, labels, mask, seg, label_pair_weights, bool(only_use_wrong_order_pair), _KIND_OF_NAME[kind], margin,
-                                    factor, click_occurance_power, reduce_mean, return_num_pair)
-    if margin != 0.0:
-        raise ValueError('margin needs a kind: the BPR term has none')
-    if label_pair_weights is not None:
-        seg = segments if segments is not None else build_segments(groups)
-        return _PairBprTable.apply(outputs, labels, mask, seg, label_pair_weights, _FLAG_WRONG_ORDER if only_use_wrong_order_pair else 0,
-                                   factor, click_occurance_power, reduce_mean, return_num_pair)
-    flags = _FLAG_LABEL_GT | (_FLAG_WRONG_ORDER if only_use_wrong_order_pair else 0)
-    if segments is None and float(click_occurance_power) == 0.0 and _ONE_CALL:
-        one = _one_call_route(groups)
-        if one is not None and one[0].numel() > 0:
-            return _PairLossOneCall.apply(outputs, labels, mask, one[0], one[1], flags, factor, reduce_mean, return_num_pair)
-    if segments is None:
-        small = _small_route(groups)
-        if small is not None:
-            return _PairBprSmall.apply(outputs, labels, mask, small[0], small[1], flags, factor, click_occurance_power, reduce_mean,
-                                       return_num_pair)
-    seg = segments if segments is not None else build_segments(groups)
-    return _PairBprFused.apply(outputs, labels, mask, seg, flags, factor, click_occurance_power, reduce_mean, return_num_pair)
+    wrong = bool(only_use_wrong_order_pair)
+    plan = _PairPlan(label_pair_weights, wrong, kind_code, margin, factor, click_occurance_power, reduce_mean, lambda_weight)
+    grouping = segments
+    if grouping is None and kind_code is None and label_pair_weights is None:
+        if float(click_occurance_power) == 0.0 and _ONE_CALL:
+            one = _one_call_route(groups)
+            if one is not None and one[0].numel() > 0:
+                return _PairLossOneCall.apply(outputs, labels, mask, one[0], one[1], _pair_flags(None, wrong), factor, reduce_mean,
+                                              return_num_pair)
+        grouping = _small_route(groups)
+    if grouping is None:
+        grouping = build_segments(groups)
+    return _PairFused.apply(outputs, labels, mask, grouping, plan, return_num_pair)
 
 
 def _bpr_options(pairloss_func):
@@ -674,6 +519,17 @@ def _kind_options(pairloss_func):
         return None
     return (name, _finite_number(kw.get('margin', 1.0), 'margin'), _finite_number(kw.get('factor', 1.0), 'factor'),
             bool(kw.get('reduce_mean', True)))
+
+
+def _fused_options(pairloss_func):
+    """The keyword arguments of `pairwise_loss_fused` that compute `pairloss_func` (`_bpr_options`, then `_kind_options`), else None."""
+    bpr = _bpr_options(pairloss_func)
+    if bpr is not None:
+        return {'factor': bpr[0], 'reduce_mean': bpr[1]}
+    kopt = _kind_options(pairloss_func)
+    if kopt is not None:
+        return {'kind': kopt[0], 'margin': kopt[1], 'factor': kopt[2], 'reduce_mean': kopt[3]}
+    return None
 
 
 def _merge_weights_by_mul(weights1, weights2):
@@ -712,17 +568,10 @@ def pairwise_loss(outputs, labels, groups,
     table = label_pair_to_weight_func if isinstance(label_pair_to_weight_func, LabelPairWeightTable) else None
     if table is not None and kwargs:
         raise ValueError('a LabelPairWeightTable took its keyword arguments when it was built; got %s' % sorted(kwargs))
-    bpr = _bpr_options(pairloss_func)
-    if bpr is not None and (label_pair_to_weight_func is None or table is not None):
+    opts = _fused_options(pairloss_func) if (label_pair_to_weight_func is None or table is not None) else None
+    if opts is not None:
         loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
-                                           factor=bpr[0], reduce_mean=bpr[1], return_num_pair=return_num_pair, label_pair_weights=table,
-                                           lambda_weight=lambda_weight)
-        return (loss, n_pair) if return_num_pair else loss
-    kopt = _kind_options(pairloss_func) if (label_pair_to_weight_func is None or table is not None) else None
-    if kopt is not None:
-        loss, n_pair = pairwise_loss_fused(outputs, labels, groups, only_use_wrong_order_pair, click_occurance_power, mask,
-                                           factor=kopt[2], reduce_mean=kopt[3], return_num_pair=return_num_pair, label_pair_weights=table,
-                                           kind=kopt[0], margin=kopt[1], lambda_weight=lambda_weight)
+                                           return_num_pair=return_num_pair, label_pair_weights=table, lambda_weight=lambda_weight, **opts)
         return (loss, n_pair) if return_num_pair else loss
 
     # general path: materialise the pair list, then run the user's callables on (P,) vectors

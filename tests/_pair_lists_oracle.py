@@ -35,6 +35,13 @@ def w_sym(a, b, **k):                            # both directions, tied labels 
     return (a - b).abs() + 0.5
 
 
+def no_general_route(monkeypatch, M):
+    """Patch `pair_indices`, the door to the general route of `M.pairwise_loss`, to raise: a case that must stay fused says so."""
+    def refuse(*a, **k):
+        raise AssertionError('the general route (pair_indices) was taken')
+    monkeypatch.setattr(M, 'pair_indices', refuse)
+
+
 # ---- lists -------------------------------------------------------------------------------------------------------------------------------
 def _as_list(g):
     return list(g) if isinstance(g, (list, tuple)) else [g]

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import _lambda_oracle as O
+from _pair_lists_oracle import no_general_route as _no_general_route
 
 pytestmark = pytest.mark.gpu
 
@@ -55,12 +56,6 @@ def _groups_of(g, variant):
     if variant == 'i64':
         return g.astype(np.int64) * 3000000007 - 5            # ids that need all 64 bits; same partition
     return g
-
-
-def _no_general_route(monkeypatch, M):
-    def refuse(*a, **k):
-        raise AssertionError('the general route (pair_indices) was taken')
-    monkeypatch.setattr(M, 'pair_indices', refuse)
 
 
 # ---- pre-pass and metric -------------------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from _pair_lists_oracle import no_general_route as _no_general_route
 import dense_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -153,12 +154,6 @@ def _oracle(batch_key, g, s, y, mask, kind, margin, factor, wf, power, wrong, re
     if batch_key is not None:
         _ORACLES[key] = out
     return out
-
-
-def _no_general_route(monkeypatch, M):
-    def refuse(*a, **k):
-        raise AssertionError('the general route (pair_indices) was taken')
-    monkeypatch.setattr(M, 'pair_indices', refuse)
 
 
 def _run(M, dev, g, s, y, mask, power, wrong, upstream=None, **kw):

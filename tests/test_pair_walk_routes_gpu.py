@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import _pair_lists_oracle as O
+from _pair_lists_oracle import no_general_route as _no_general_route
 
 pytestmark = pytest.mark.gpu
 
@@ -45,12 +46,6 @@ def _ndcg():
 
 def _t(a):
     return torch.from_numpy(np.array(a))         # a copy: the shared layouts and references stay as they are
-
-
-def _no_general_route(monkeypatch, M):
-    def refuse(*a, **k):
-        raise AssertionError('the general route (pair_indices) was taken')
-    monkeypatch.setattr(M, 'pair_indices', refuse)
 
 
 def _groups(name, variant):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from _pair_lists_oracle import no_general_route as _no_general_route
 import dense_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -79,12 +80,6 @@ def _oracle(g, s, y, mask, wf, wkw, power, wrong, factor=1.0):
                                 label_pair_to_weight_func=wf, **wkw)
     rloss.backward()
     return rloss.item(), rn, s64.grad.numpy()
-
-
-def _no_general_route(monkeypatch, M):
-    def refuse(*a, **k):
-        raise AssertionError('the general route (pair_indices) was taken')
-    monkeypatch.setattr(M, 'pair_indices', refuse)
 
 
 def _run(M, dev, g, s, y, mask, power, wrong, **kw):
