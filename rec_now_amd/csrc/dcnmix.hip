@@ -20,6 +20,7 @@
 #include <mutex>
 #include "dcnmix_layout.hpp"
 #include "prof.hpp"
+#include "grouping.hpp"
 
 // Wc1[d][n*S+s] = U[n][d][s];  Wc1[d][NS+n] = K[d][n];  pad columns = 0
 __global__ void k_pack_w1(const float* __restrict__ U, const float* __restrict__ K, int D, int S, int N, int LDT, float* __restrict__ Wc1) {
@@ -676,13 +677,6 @@ extern "C" int recnow_dcn_mix_score_supported(int64_t B, int D, int S, int N, in
 int rn_pair_bpr_onepass(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, const int32_t* seg_id,
                         const int32_t* seg_first, int64_t B, int flags, float factor, int reduce_mean, float* loss, float* dscores_unnorm,
                         int64_t* n_pair, void* ws, size_t ws_bytes, void* stream, const double** part_out, int* nparts_out);      // pairwise.hip
-// scan_sort.hip; pack != NULL: the launch also writes the weight packs of the row-block kernels on further workgroups (k_front_small / k_front_mid)
-// zero1 / zeroed: a front kernel also clears one 64-bit word (the step's pair counter) and reports it
-int rn_group_small_raw(const void* group, int dtype, int64_t B, int32_t* order, int32_t* seg_id, int32_t* seg_first, int32_t* super_id,
-                       int32_t* n_seg, hipStream_t st, const RnTileFwd* pack, unsigned long long* zero1, int* zeroed, int* packed);
-int rn_group_mid_raw(const void* group, int dtype, int64_t B, uint8_t* solo, int32_t* order, int32_t* seg_id, int32_t* seg_first, int32_t* super_id,
-                     int32_t* n_seg, void* ws, size_t ws_bytes, hipStream_t st, const RnTileFwd* pack, unsigned long long* zero1, int* zeroed, int* packed);
-
 extern "C" int recnow_dcn_mix_tile_route(int64_t B, int D, int S, int N, int L) {
     if (B <= 0 || D < 1 || S < 1 || N < 1 || L < 1 || N > 64) return 0;
     const MixDims m = mix_dims(B, D, S, N, L);
@@ -1353,7 +1347,7 @@ k_step_dscore(const float* __restrict__ dsu, const unsigned long long* __restric
     // row of dscore * T2g, so that the backward products, which run over all BP rows, add exactly nothing for them
     __shared__ float sds[STEP_ROWS];
     const float P = (float)(*n_pair);
-    // n_seg[0] < 0: the cooperative grouping launch timed out at a grid barrier and left the identity grouping (scan_sort.hip) -- zero
+    // n_seg[0] < 0: the cooperative grouping launch timed out at a grid barrier and left the identity grouping (group_mid.hpp) -- zero
     // pairs would read as "loss 0, all-zero gradients" with RECNOW_OK.  Poisoned instead: loss, statistics and d loss / d scores are NaN.
     const bool bad = n_seg[0] < 0;
     const float sc = bad ? __int_as_float(0x7fc00000) : (reduce_mean ? 1.f / (P + eps) : 1.f);
@@ -1433,19 +1427,12 @@ extern "C" int recnow_dcn_mix_step(const recnow_dcn_mix_step_desc* d, int phases
         tl_step_tile_packed = nullptr;
         // (the loss stage of THIS call adds into *n_pair: a front kernel clears it on the way)
         unsigned long long* zero1 = ((phases & RECNOW_STEP_LOSS) && d->n_pair) ? (unsigned long long*)d->n_pair : nullptr;
-        int packs_written = 0;          // the grouping launch also wrote the row-block kernels' weight packs (only the front kernels do)
-        rc = rn_group_small_raw(d->groups, d->group_dtype, B, w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, st, pack, zero1, &npair_zeroed, &packs_written);
-        // larger batches: the cooperative launch forms keys and solo flags from the id tensor as well
-        if (rc == RECNOW_EUNSUPPORTED)
-            rc = rn_group_mid_raw(d->groups, d->group_dtype, B, w.solo, w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, w.grp, w.grp_bytes, st, pack, zero1,
-                                  &npair_zeroed, &packs_written);
-        if (rc == RECNOW_OK && pack && packs_written) tl_step_tile_packed = w.saved;
-        if (rc == RECNOW_EUNSUPPORTED) {
-            RN_HIP(hipMemsetAsync(w.solo, 0, (size_t)B, st));
-            if ((rc = recnow_group_keys(d->groups, d->group_dtype, B, w.words, w.solo, stream))) return rc;
-            rc = recnow_group_segments(w.words, w.solo, B, w.n_words, w.n_words, w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, w.grp,
-                                       w.grp_bytes, stream);
-        }
+        // one launch straight from the id tensor where one fits (<= 8192 rows: one workgroup; above: cooperative), else keys + segments: grouping.hpp
+        RnGroupFront fr = {pack, zero1, 0, 0};
+        const RnGroupBufs gb = {w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, w.words, w.solo, w.n_words};
+        rc = rn_group_rows(d->groups, d->group_dtype, B, gb, w.grp, w.grp_bytes, st, &fr);
+        npair_zeroed = fr.zeroed;
+        if (rc == RECNOW_OK && pack && fr.packed) tl_step_tile_packed = w.saved;      // (only a front kernel writes the packs)
         if (rc) return rc;
         rn_prof_end(pr, st);
     }

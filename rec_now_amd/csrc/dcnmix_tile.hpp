@@ -45,7 +45,7 @@ int rn_mix_tile_fwd_split(const RnTileFwd& p, hipStream_t st);
 // P4_l[g][h][d][i] = U_l[n][d][s],  n S + s = 8 g + 4 h + i                 (16 x 2 x D float4)       backward g_l product, A fragments
 // VT_l[n][t][s]    = V_l[n][s][t]                                                                      backward dA product, B fragments
 // One thread per 16-byte output piece (the four i of a piece are four rows (P1, P2) or four consecutive elements (P3, P4) of the source), pieces first,
-// first + stride, ...: the body of k_tile_pack (dcnmix_tile.hip) and of the pack workgroups of the step's front kernels (scan_sort.hip).
+// first + stride, ...: the body of k_tile_pack (dcnmix_tile.hip) and of the pack workgroups of the step's front kernels (grouping.hip).
 __device__ __forceinline__ void tl_pack_range(const RnTileFwd& p, int64_t first, int64_t stride) {
     const int D = p.D, L = p.L;
     const int64_t per4 = (int64_t)D * TL_NS / 4, lay4 = TL_PACK_FLOATS(D) / 4, total4 = (int64_t)L * lay4;

@@ -1,5 +1,5 @@
 // Single-workgroup grouping of a small batch (B <= 8192 rows, one 32-bit key word) on LDS-resident keys: shared by
-// k_group_small (scan_sort.hip) and the fused small pairwise loss (pairwise.hip).
+// k_group_small (grouping.hip) and the fused small pairwise loss (pairwise.hip).
 #pragma once
 #include "common.hpp"
 

@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "scan.hpp"
 #include "group_small.hpp"
+#include "grouping.hpp"
 #include "pairwise_walk.hpp"
 
 
@@ -782,7 +783,7 @@ __global__ void __launch_bounds__(256)
 k_pair_norm_grad(const float* __restrict__ d, const unsigned long long* __restrict__ n_pair, int reduce_mean, float eps, int64_t B,
                  float* __restrict__ out, float* __restrict__ loss, float* __restrict__ out2, const int32_t* __restrict__ n_seg) {
     const float P = (float)(*n_pair);
-    // n_seg[0] < 0: the cooperative grouping launch timed out (scan_sort.hip) and left the identity grouping: NaN, never a silent zero
+    // n_seg[0] < 0: the cooperative grouping launch timed out (group_mid.hpp) and left the identity grouping: NaN, never a silent zero
     const bool bad = n_seg[0] < 0;
     const float sc = bad ? __int_as_float(0x7fc00000) : (reduce_mean ? 1.f / (P + eps) : 1.f);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -791,9 +792,6 @@ k_pair_norm_grad(const float* __restrict__ d, const unsigned long long* __restri
     }
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B; i += (int64_t)gridDim.x * 256) out[i] = d[i] * sc;
 }
-struct RnTileFwd;
-int rn_group_mid_raw(const void* group, int dtype, int64_t B, uint8_t* solo, int32_t* order, int32_t* seg_id, int32_t* seg_first, int32_t* super_id,
-                     int32_t* n_seg, void* ws, size_t ws_bytes, hipStream_t st, const RnTileFwd* pack, unsigned long long* zero1, int* zeroed, int* packed);       // scan_sort.hip
 extern "C" int recnow_pairwise_loss(const void* groups, int key_dtype, const float* labels, const float* scores, const uint8_t* mask,
                                     int64_t B, int flags, float factor, int reduce_mean, float* loss, int64_t* n_pair, float* out2,
                                     float* dscores, void* ws, size_t ws_bytes, void* stream) {
@@ -817,16 +815,9 @@ extern "C" int recnow_pairwise_loss(const void* groups, int key_dtype, const flo
                                           n_pair, w.pair, w.pair_bytes, stream)))
             return rc;
         f |= RECNOW_PAIR_MEMBERS_PACKED;
-    } else if ((rc = rn_group_mid_raw(groups, key_dtype, B, w.solo, w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, w.grp, w.grp_bytes, st, nullptr, nullptr, nullptr, nullptr)) !=
-               RECNOW_EUNSUPPORTED) {
-        // (one float32 / int32 id tensor: keys and solo flags formed inside the cooperative grouping launch, scan_sort.hip)
-        if (rc) return rc;
     } else {
-        RN_HIP(hipMemsetAsync(w.solo, 0, (size_t)B, st));
-        if ((rc = recnow_group_keys(groups, key_dtype, B, w.words, w.solo, stream))) return rc;
-        if ((rc = recnow_group_segments(w.words, w.solo, B, w.n_words, w.n_words, w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, w.grp, w.grp_bytes,
-                                        stream)))
-            return rc;
+        const RnGroupBufs gb = {w.order, w.seg_id, w.seg_first, w.super_id, w.n_seg, w.words, w.solo, w.n_words};
+        if ((rc = rn_group_rows(groups, key_dtype, B, gb, w.grp, w.grp_bytes, st, nullptr))) return rc;
     }
     if ((rc = recnow_pair_bpr_onepass(scores, labels, mask, w.order, w.seg_id, w.seg_first, B, f, factor, reduce_mean, loss, w.dsu, n_pair, w.pair,
                                       w.pair_bytes, stream)))

@@ -108,7 +108,7 @@ def test_step_with_mask_and_wrong_order_pairs(dev):
 @pytest.mark.parametrize('B,kind', [(4096, 'f32'), (9216, 'f32'), (9216, 'i32'), (16384, 'f32')])
 def test_step_grouping_from_raw_ids_equals_the_two_call_form(dev, B, kind):
     """The step's GROUP phase forms canonical keys and solo flags INSIDE its grouping launch (k_front_small up to 8192 rows, k_front_mid<RAW> above:
-    csrc/scan_sort.hip), with the row-block weight packs on the launch's other workgroups; `pairwise_loss` goes through recnow_group_keys +
+    csrc/grouping.hip), with the row-block weight packs on the launch's other workgroups; `pairwise_loss` goes through recnow_group_keys +
     recnow_group_segments.  Ids with -0.0 / +0.0 (one group), NaN and +-inf (rows that pair with nobody: g_i - g_j is NaN in the reference,
     rec_block/pairwise_loss_from_batch.py:33-35) and negative values must give the same loss, pair count and gradients bit for bit."""
     from rec_now_amd.fused import score_params

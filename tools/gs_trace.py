@@ -1,4 +1,4 @@
-"""GPU box: phase stamps of the one-workgroup grouping kernel (csrc/scan_sort.hip k_group_small) from the diagnostic build
+"""GPU box: phase stamps of the one-workgroup grouping kernel (csrc/grouping.hip k_group_small) from the diagnostic build
     python tools/build_variant.py gstrace -DRN_GS_TRACE
     RECNOW_LIB_PATH=rec_now_amd/librecnow_hip.gstrace.so python tools/gs_trace.py [rows] [groups]
 Prints the microseconds between the stamps of thread 0 (100 MHz wall clock): load | varying bits | sort | heads + scan | writes."""
