@@ -496,6 +496,14 @@ int recnow_dcn_step_fwd(const float* x0, const float* xl, const float* w, const 
 int recnow_dcn_step_bwd(const float* x0, const float* xl, const float* w, const float* z, const float* c, const float* dz,
                         int64_t B, int D, int act, float* dx0, float* dxl, float* dw, float* db, void* ws, size_t ws_bytes,
                         void* stream);
+/* Which kernels recnow_dcn_fwd (which = 0) / recnow_dcn_bwd (which = 1) launch for a call of this shape: the ONE statement of that choice (both
+ * drivers call the function behind it); nothing is launched.  has_csave: csave != NULL (it moves the backward only).  align_mask: one bit per
+ * tensor that starts OFF a 16-byte boundary -- 1 x, 2 y (forward) / dy (backward), 4 dx (backward), 8 kernels, 16 biases (NULL: clear).
+ * Returns family * 100000 + tpr * 100 + vec * 10 + nv, (tpr, vec, nv) the threads per row, floats per access and register images per thread of
+ * the kernel template (0, 0, 0 on the general path).  family, forward: 1 k_dcn_fwd_general, 2 k_dcn_fwd, 3 k_dcn_fwd_fast; backward: 1 the
+ * general rows + columns kernels, 2 k_dcn_bwd (recompute, no csave), 3 k_dcn_bwd_saved, 4 k_dcn_bwd_saved_wl, 5 k_dcn_bwd_fast.  B = 0: 0 (no
+ * launch).  RECNOW_EINVAL: which outside {0, 1}, B < 0, D < 1, L < 1 or align_mask outside 0 .. 31. */
+int recnow_dcn_route(int which, int64_t B, int D, int L, int has_csave, int align_mask);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DCNMixLayer (DCN-v2 mixture of low-rank experts, reference variant without residual):

@@ -79,6 +79,7 @@ SIGNATURES = {
     'recnow_dcn_workspace_bytes': (_Z, [_L, _I, _I]),
     'recnow_dcn_fwd': (_I, [_P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
     'recnow_dcn_bwd': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'recnow_dcn_route': (_I, [_I, _L, _I, _I, _I, _I]),
     'recnow_dcn_step_workspace_bytes': (_Z, [_L, _I]),
     'recnow_dcn_step_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     'recnow_dcn_step_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
@@ -190,7 +191,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 20  # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 21  # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -501,7 +501,8 @@ k_dcn_fwd_fast(const float* __restrict__ x, const float* __restrict__ kernels, c
     }
 }
 
-// TPR = 64 (a wave per row, D <= 512) or 128 (two waves per row, D = 1024: half the accumulator registers per lane)
+// TPR = 64 (a wave per row: D = 256 with NV = 1, D = 1024 with NV = 4) or 128 (two waves per row, D = 1024 with NV = 2: half the accumulator
+// registers per lane).  D = TPR * 4 * NV exactly; dcn_route_bwd takes D = 256 and D = 1024 only.
 template <int TPR, int NV, int L, int ACT>
 __global__ void __launch_bounds__(256)
 k_dcn_bwd_fast(const float* __restrict__ x, const float* __restrict__ kernels, const float* __restrict__ biases, const float* __restrict__ dy,
@@ -725,8 +726,9 @@ k_dcn_bwd_cols_general(const float* __restrict__ x, const float* __restrict__ ke
 struct DcnCfg {
     int tpr, vec, nv;
 };
-static bool dcn_pick(int D, const void* a, const void* b, const void* c, DcnCfg* cfg) {
-    const bool aligned = (D % 4 == 0) && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0);
+// ptrs_aligned: the three tensors the call streams (forward x, y, kernels; backward x, dy, dx) all start on a 16-byte boundary
+static bool dcn_pick(int D, bool ptrs_aligned, DcnCfg* cfg) {
+    const bool aligned = (D % 4 == 0) && ptrs_aligned;
     if (aligned) {
         if (D <= 256) { *cfg = {64, 4, 1}; return true; }
         if (D <= 1024) { *cfg = {64, 4, 4}; return true; }
@@ -740,10 +742,78 @@ static bool dcn_pick(int D, const void* a, const void* b, const void* c, DcnCfg*
 
 // backward keeps 2*L accumulator rows per thread: with one wave per 1024-wide row that is 270 VGPRs (1 wave/SIMD on a
 // latency-bound loop, 1.1 TB/s measured); one 256-thread workgroup per row needs ~70 (8 waves/SIMD).
-static bool dcn_pick_bwd(int D, const void* a, const void* b, const void* c, DcnCfg* cfg) {
-    if (!dcn_pick(D, a, b, c, cfg)) return false;
+static bool dcn_pick_bwd(int D, bool ptrs_aligned, DcnCfg* cfg) {
+    if (!dcn_pick(D, ptrs_aligned, cfg)) return false;
     if (cfg->tpr == 64 && cfg->vec == 4 && cfg->nv == 4) *cfg = {256, 4, 1};
     return true;
+}
+
+// ---- the route choice of the two drivers: pure host functions of the sizes, of whether csave is given and of which tensors start off a
+// 16-byte boundary.  recnow_dcn_fwd / recnow_dcn_bwd launch what these return; recnow_dcn_route answers the same question without a launch
+// (tests/_dcn_routes.py mirrors it).  The occupancy cap on the grid of k_dcn_bwd_fast is a launch parameter, not part of the route.
+#define DCN_MIS_X 1        /* x */
+#define DCN_MIS_Y 2        /* forward: y; backward: dy */
+#define DCN_MIS_DX 4       /* backward: dx */
+#define DCN_MIS_K 8        /* kernels */
+#define DCN_MIS_B 16       /* biases (NULL is aligned) */
+enum { DCN_FWD_GENERAL = 1, DCN_FWD_TEMPLATED = 2, DCN_FWD_FAST = 3 };
+enum { DCN_BWD_GENERAL = 1, DCN_BWD_RECOMPUTE = 2, DCN_BWD_SAVED = 3, DCN_BWD_SAVED_WL = 4, DCN_BWD_FAST = 5 };
+struct DcnRoute {
+    int family;
+    DcnCfg cfg;            // {0, 0, 0} on the general path
+};
+static inline int dcn_mis_mask(const void* x, const void* y, const void* dx, const void* kernels, const void* biases) {
+    return (((uintptr_t)x & 15) ? DCN_MIS_X : 0) | (((uintptr_t)y & 15) ? DCN_MIS_Y : 0) | (((uintptr_t)dx & 15) ? DCN_MIS_DX : 0) |
+           (((uintptr_t)kernels & 15) ? DCN_MIS_K : 0) | (((uintptr_t)biases & 15) ? DCN_MIS_B : 0);
+}
+
+static DcnRoute dcn_route_fwd(int64_t B, int D, int L, int mis) {
+    DcnRoute r = {DCN_FWD_GENERAL, {0, 0, 0}};
+    DcnCfg cfg;
+    if (!dcn_pick(D, !(mis & (DCN_MIS_X | DCN_MIS_Y | DCN_MIS_K)), &cfg) || ((mis & DCN_MIS_B) && cfg.vec == 4)) return r;
+    r.cfg = cfg;
+    const bool fast = cfg.vec == 4 && cfg.tpr == 64 && D == 256 * cfg.nv && B % 4 == 0 && L <= DCN_MAX_L &&
+                      (size_t)2 * L * D * sizeof(float) <= 48 * 1024;        // k_dcn_fwd_fast<NV, L, ..>: NV in {1, 4}, L = 1 .. 4
+    r.family = fast ? DCN_FWD_FAST : DCN_FWD_TEMPLATED;
+    return r;
+}
+
+// the k_dcn_bwd_fast<TPR, NV, L, ..> instantiations (recnow_dcn_bwd: BWD_FAST)
+static inline bool dcn_bwd_fast_built(const DcnCfg& cfg, int L) {
+    if (cfg.tpr == 64 && cfg.nv == 1) return L >= 1 && L <= 4;
+    if (cfg.tpr == 128 && cfg.nv == 2) return L >= 1 && L <= 4;
+    if (cfg.tpr == 64 && cfg.nv == 4) return L >= 1 && L <= 3;
+    return false;
+}
+
+static DcnRoute dcn_route_bwd(int64_t B, int D, int L, bool has_csave, int mis) {
+    DcnRoute r = {DCN_BWD_GENERAL, {0, 0, 0}};
+    DcnCfg cfg;
+    const bool ptrs_aligned = !(mis & (DCN_MIS_X | DCN_MIS_Y | DCN_MIS_DX));
+    // with the saved scalars a wave per row fits the register file (no recompute state); without them one workgroup per row
+    if (L > DCN_MAX_L || !(has_csave ? dcn_pick(D, ptrs_aligned, &cfg) : dcn_pick_bwd(D, ptrs_aligned, &cfg)) ||
+        (cfg.vec == 4 && (mis & (DCN_MIS_K | DCN_MIS_B))))
+        return r;               // general path: any L, D, alignment (see k_dcn_bwd_rows_general)
+    // D = 1024: a wave per row up to three cross layers (row sums are shuffles, no barrier in the row loop: the two-waves-per-row form
+    // waits on a workgroup barrier per layer and row: 176 vs 166 us at B = 65 536, L = 3, both on one resident wave of workgroups); deeper: 2 waves per row, half the
+    // accumulator registers per lane.
+    if (has_csave && cfg.tpr == 64 && cfg.vec == 4 && cfg.nv == 4 && L > 3) cfg = {128, 4, 2};
+    r.cfg = cfg;
+    const size_t comb = cfg.tpr < 256 ? (size_t)(256 / cfg.tpr) * D * sizeof(float) : 0;      // the cross-wave combine rows
+    const size_t wl_bytes = (size_t)2 * L * D * sizeof(float);            // kernels + biases of every layer, staged in LDS when they fit
+    if (!has_csave) r.family = DCN_BWD_RECOMPUTE;
+    else if (cfg.vec == 4 && D == cfg.tpr * 4 * cfg.nv && B % (256 / cfg.tpr) == 0 && (cfg.tpr == 64 || cfg.tpr == 128) &&
+             comb + wl_bytes <= 48 * 1024 && dcn_bwd_fast_built(cfg, L))
+        r.family = DCN_BWD_FAST;
+    else r.family = comb + wl_bytes <= 48 * 1024 ? DCN_BWD_SAVED_WL : DCN_BWD_SAVED;
+    return r;
+}
+
+extern "C" int recnow_dcn_route(int which, int64_t B, int D, int L, int has_csave, int align_mask) {
+    if ((which != 0 && which != 1) || B < 0 || D < 1 || L < 1 || align_mask < 0 || align_mask > 31) return RECNOW_EINVAL;
+    if (B == 0) return 0;
+    const DcnRoute r = which == 0 ? dcn_route_fwd(B, D, L, align_mask) : dcn_route_bwd(B, D, L, has_csave != 0, align_mask);
+    return r.family * 100000 + r.cfg.tpr * 100 + r.cfg.vec * 10 + r.cfg.nv;
 }
 
 static int dcn_occupancy(const void* kernel, size_t shm) {
@@ -783,14 +853,15 @@ extern "C" int recnow_dcn_fwd(const float* x, const float* kernels, const float*
     if (B < 0 || D < 1 || L < 1) return RECNOW_EINVAL;
     if (B == 0) return RECNOW_OK;
     if (!x || !kernels || !y) return RECNOW_EINVAL;
-    DcnCfg cfg;
     hipStream_t st = (hipStream_t)stream;
-    if (!dcn_pick(D, x, y, kernels, &cfg) || (biases && (((uintptr_t)biases & 15) != 0) && cfg.vec == 4)) {
+    const DcnRoute route = dcn_route_fwd(B, D, L, dcn_mis_mask(x, y, nullptr, kernels, biases));
+    const DcnCfg cfg = route.cfg;
+    if (route.family == DCN_FWD_GENERAL) {
         hipLaunchKernelGGL(k_dcn_fwd_general, (int)(B < 4096 ? B : 4096), 256, 0, st, x, kernels, biases, B, D, L, act, y, csave);
         RN_LAUNCH_CHECK();
         return RECNOW_OK;
     }
-    if (cfg.vec == 4 && cfg.tpr == 64 && D == 256 * cfg.nv && B % 4 == 0 && L <= DCN_MAX_L && (size_t)2 * L * D * sizeof(float) <= 48 * 1024) {
+    if (route.family == DCN_FWD_FAST) {
         const int G = dcn_grid(B, 64);
         const size_t shm = (size_t)2 * L * D * sizeof(float);
 #define FWD_FAST(NV_, L_)                                                                                                          \
@@ -826,7 +897,6 @@ extern "C" int recnow_dcn_bwd(const float* x, const float* kernels, const float*
     }
     if (!x || !kernels || !dy || !dx || !dkernels || !ws) return RECNOW_EINVAL;
     if (ws_bytes < recnow_dcn_workspace_bytes(B, D, L)) return RECNOW_EWORKSPACE;
-    DcnCfg cfg;
     RnCarver c(ws, ws_bytes);
     float* part = c.take<float>((size_t)2048 * 2 * L * D);
     float* sums = c.take<float>((size_t)2 * L * D);
@@ -834,9 +904,9 @@ extern "C" int recnow_dcn_bwd(const float* x, const float* kernels, const float*
     float* cs_own = c.take<float>((size_t)B * L);
     void* cs_ws = c.base + c.off;
     const size_t cs_bytes = ws_bytes - c.off;
-    // with the saved scalars a wave per row fits the register file (no recompute state); without them one workgroup per row
-    if (L > DCN_MAX_L || !(csave ? dcn_pick(D, x, dy, dx, &cfg) : dcn_pick_bwd(D, x, dy, dx, &cfg)) ||
-        (cfg.vec == 4 && ((((uintptr_t)kernels | (uintptr_t)biases) & 15) != 0))) {
+    const DcnRoute route = dcn_route_bwd(B, D, L, csave != nullptr, dcn_mis_mask(x, dy, dx, kernels, biases));
+    const DcnCfg cfg = route.cfg;
+    if (route.family == DCN_BWD_GENERAL) {
         // general path: any L, D, alignment (see k_dcn_bwd_rows_general)
         const int GR = (int)(B < 4096 ? B : 4096);
         if (!csave) {
@@ -858,16 +928,12 @@ extern "C" int recnow_dcn_bwd(const float* x, const float* kernels, const float*
         if (dbiases) RN_HIP(hipMemcpyAsync(dbiases, sums + (size_t)L * D, (size_t)L * D * sizeof(float), hipMemcpyDeviceToDevice, st));
         return RECNOW_OK;
     }
-    // D = 1024: a wave per row up to three cross layers (row sums are shuffles, no barrier in the row loop: the two-waves-per-row form
-    // waits on a workgroup barrier per layer and row: 176 vs 166 us at B = 65 536, L = 3, both on one resident wave of workgroups); deeper: 2 waves per row, half the
-    // accumulator registers per lane.
-    if (csave && cfg.tpr == 64 && cfg.vec == 4 && cfg.nv == 4 && L > 3) cfg = {128, 4, 2};
     bool fast_done = false;
     int G = dcn_grid(B, cfg.tpr);
-    if (csave && cfg.vec == 4 && D == cfg.tpr * 4 * cfg.nv && B % (256 / cfg.tpr) == 0 && (cfg.tpr == 64 || cfg.tpr == 128)) {
+    if (route.family == DCN_BWD_FAST) {
         const size_t shm = ((size_t)(256 / cfg.tpr) * D + (size_t)2 * L * D) * sizeof(float);
 #define BWD_FAST(TPR_, NV_, L_)                                                                                                    \
-        if (!fast_done && shm <= 48 * 1024 && cfg.tpr == TPR_ && cfg.nv == NV_ && L == L_) {                                       \
+        if (!fast_done && cfg.tpr == TPR_ && cfg.nv == NV_ && L == L_) {                                                           \
             /* one resident wave of workgroups (rows are grid-strided): every workgroup beyond it costs a weight fill, a combine  \
                and a 2*L*D slab that the column sum reads back (2048 slabs = 50 MB at D = 1024, L = 3) */                        \
             if (act == RECNOW_ACT_LINEAR) {                                                                                        \
@@ -887,11 +953,11 @@ extern "C" int recnow_dcn_bwd(const float* x, const float* kernels, const float*
 #undef BWD_FAST
     }
     const size_t shmem = cfg.tpr < 256 ? (size_t)(256 / cfg.tpr) * D * sizeof(float) : 0;
-    const size_t wl_bytes = (size_t)2 * L * D * sizeof(float);            // kernels + biases of every layer, staged in LDS when they fit
+    const size_t wl_bytes = (size_t)2 * L * D * sizeof(float);            // kernels + biases of every layer, staged in LDS (DCN_BWD_SAVED_WL)
     if (fast_done) {
-    } else if (csave && shmem + wl_bytes <= 48 * 1024) DCN_DISPATCH(k_dcn_bwd_saved_wl, shmem + wl_bytes, x, kernels, biases, dy, csave, B, D, L, act, dx, part);
-    else if (csave) DCN_DISPATCH(k_dcn_bwd_saved, shmem, x, kernels, biases, dy, csave, B, D, L, act, dx, part);
-    else DCN_DISPATCH(k_dcn_bwd, shmem, x, kernels, biases, dy, B, D, L, act, dx, part);
+    } else if (route.family == DCN_BWD_RECOMPUTE) DCN_DISPATCH(k_dcn_bwd, shmem, x, kernels, biases, dy, B, D, L, act, dx, part);
+    else if (route.family == DCN_BWD_SAVED) DCN_DISPATCH(k_dcn_bwd_saved, shmem, x, kernels, biases, dy, csave, B, D, L, act, dx, part);
+    else DCN_DISPATCH(k_dcn_bwd_saved_wl, shmem + wl_bytes, x, kernels, biases, dy, csave, B, D, L, act, dx, part);
     RN_LAUNCH_CHECK();
     int rc = rn_colsum(part, nullptr, 0, 0, G, (int64_t)2 * L * D, (int64_t)2 * L * D, sums, 0, cs_ws, cs_bytes, st);
     if (rc) return rc;

@@ -254,7 +254,11 @@ def test_dcn_reference_golden(dev, golden):
                                                 (600, 1024, 6, 'tanh', True), (300, 8192, 6, None, True), (257, 8200, 2, 'tanh', False),
                                                 (100, 1030, 5, 'sigmoid', True), (33, 4100, 1, 'relu', True), (2100, 64, 9, 'tanh', True),
                                                 # user callables as activation (keras.activations.get): per-layer route
-                                                (300, 96, 3, 'softsign', True), (128, 5000, 2, 'gelu', False)])
+                                                (300, 96, 3, 'softsign', True), (128, 5000, 2, 'gelu', False),
+                                                # the fast kernels through autograd (D in {256, 1024} aligned, B % 4 == 0; csrc/dcn.hip
+                                                # k_dcn_fwd_fast / k_dcn_bwd_fast; route by route: tests/test_dcn_routes_gpu.py)
+                                                (8, 256, 1, None, True), (8, 256, 2, None, True), (8, 256, 3, None, True), (8, 256, 4, None, True),
+                                                (1000, 1024, 3, None, True), (1000, 1024, 4, 'tanh', True)])
 def test_dcn_fwd_bwd_vs_oracle(dev, B, D, L, act, use_bias):
     act = {'softsign': torch.nn.functional.softsign, 'gelu': torch.nn.functional.gelu}.get(act, act)
     from rec_now_amd.layers.dcn_layer import DCNLayer
