@@ -241,6 +241,28 @@ int recnow_pair_auc_terms(const float* scores, const float* labels, const uint8_
                           int32_t* row_c, int32_t* row_t, int64_t* list_n, int64_t* list_c, int64_t* list_t, int64_t* list_rows, float* auc,
                           double* weighted_sum, double* weight_sum, int64_t* n_lists, void* ws, size_t ws_bytes, void* stream);
 
+/* The same counts and metric WITHOUT a walk over the pairs (ABI 22): every list is sorted by score (recnow_group_segments on the key words
+ * {seg_id, order-preserving image of the score}, called inside on this entry's workspace) and the counts of a row are differences of per-class
+ * prefix counts at the ends of its list and of its run of tied scores.  O(B log B) whatever the list lengths; the walk is quadratic in them.
+ * Arguments, definitions, outputs, return codes and the B == 0 case are those of recnow_pair_auc_terms, and for every input it accepts the
+ * integers are the same, so the fp64 sums and the metric are bit-identical too.  Differences:
+ *   - flags must be 0: RECNOW_PAIR_MEMBERS_PACKED is refused (RECNOW_EINVAL) -- this route reads no member records.
+ *   - classes.  Binary rule: two classes, any labels.  Graded rule: the classes are the distinct non-NaN label values of the taking-part rows of
+ *     the batch (-0.0 == +0.0), found on the device; up to 16 are supported.
+ *   - poisoning.  With more than 16 values, or when the inner grouping call reports a grid-barrier time-out (its n_seg[0] < 0), the host cannot
+ *     be told without a synchronisation, so every output asked for is overwritten: auc, weighted_sum, weight_sum = NaN, n_lists = -1, and all B
+ *     entries of every per-row and per-list count = -1.
+ * Workspace: recnow_pair_auc_sorted_workspace_bytes(B) (its own layout: it does NOT begin with the pairwise workspace; at most 16 int32 per row
+ *   beside the sort's).  No host synchronisation; integer counting only; bitwise reproducible; every launch can be captured in a HIP graph.
+ * RECNOW_AUC_SORT_TILE: positions of the (list, score) order per workgroup of the prefix-count kernels (tests restate their census from it). */
+#define RECNOW_AUC_SORT_TILE 1024
+size_t recnow_pair_auc_sorted_workspace_bytes(int64_t B);
+int recnow_pair_auc_sorted_terms(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, const int32_t* seg_id,
+                                 const int32_t* seg_first, int64_t B, int flags, int binary, float pos_neg_th, int weight_kind, int32_t* row_n,
+                                 int32_t* row_c, int32_t* row_t, int64_t* list_n, int64_t* list_c, int64_t* list_t, int64_t* list_rows,
+                                 float* auc, double* weighted_sum, double* weight_sum, int64_t* n_lists, void* ws, size_t ws_bytes,
+                                 void* stream);
+
 /* pairwise_loss(outputs, labels, groups) with the reference's defaults (pairloss_func = bpr_loss_func, click_occurance_power = 0,
  * one group tensor; rec_block/pairwise_loss_from_batch.py:228-279) as ONE call: grouping (the single-launch front end when
  * recnow_pairwise_small_supported, else keys + radix sort + segments), the one-walk loss and the gradient

@@ -47,6 +47,8 @@ SIGNATURES = {
     'recnow_pair_lambda_fwdbwd': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _P, _F, _F, _I, _P, _P, _P, _Z, _P]),
     'recnow_pair_auc_workspace_bytes': (_Z, [_L]),
     'recnow_pair_auc_terms': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_pair_auc_sorted_workspace_bytes': (_Z, [_L]),
+    'recnow_pair_auc_sorted_terms': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_pairwise_loss_workspace_bytes': (_Z, [_L, _I]),
     'recnow_pairwise_loss': (_I, [_P, _I, _P, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_pairwise_small_supported': (_I, [_L, _I]),
@@ -191,7 +193,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 21  # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 22  # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

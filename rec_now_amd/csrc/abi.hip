@@ -16,5 +16,6 @@
 // seg_psum, seg_pdot) in recnow_listwise_segments / _loss_fwdbwd / _dense; 17: recnow_pair_table_count / recnow_pair_table_bpr_fwdbwd
 // (LabelPairWeightTable: the fused pairwise loss with per-label-pair weights); 18: recnow_pair_kind_fwdbwd (hinge, squared-hinge and margin-logistic
 // pair terms on the fused route); 19: recnow_pair_lambda_terms / _fwdbwd / _workspace_bytes (the NDCG pair weight on the fused route, in-batch NDCG);
-// 20: recnow_pair_auc_terms / _workspace_bytes (in-batch GAUC from exact pair counts); 21: recnow_dcn_route (the route choice of recnow_dcn_fwd / _bwd, queryable).
-extern "C" int recnow_abi_version(void) { return 21; }
+// 20: recnow_pair_auc_terms / _workspace_bytes (in-batch GAUC from exact pair counts); 21: recnow_dcn_route (the route choice of recnow_dcn_fwd / _bwd, queryable);
+// 22: recnow_pair_auc_sorted_terms / _sorted_workspace_bytes (in-batch GAUC and AUC by sort and per-class prefix counts).
+extern "C" int recnow_abi_version(void) { return 22; }

@@ -61,7 +61,9 @@ def global_gauc(weighted_sum, weight_sum, n_lists):
     global metric: ONE SUM all-reduce of the three values (as fp64: exact for the list count below 2**53) when `is_dist()`.
     Returns (gauc, n_lists): gauc = sum of the weighted sums / sum of the weight sums as a 0-dim fp64 tensor, 0 where the weight sum is 0;
     n_lists as a 0-dim int64 tensor.  Ranks hold whole groups (`shard_rows_by_group`), so every list is counted on exactly one rank with its
-    own weight: the result is the exact global metric, not a mean of per-rank means.  Without a process group it is the local ratio."""
+    own weight: the result is the exact global metric, not a mean of per-rank means.  Without a process group it is the local ratio.
+    The plain AUC of the batch (`rec_block.auc.in_batch_auc`) is NOT a sum of per-rank parts: its one list spans the ranks, so pairs cross
+    them.  Summing the ranks' parts of it here gives the pooled AUC of the pairs inside each rank, not the global AUC (that is not built)."""
     stats = torch.stack([weighted_sum.detach().to(torch.float64), weight_sum.detach().to(torch.float64), n_lists.detach().to(torch.float64)])
     if is_dist():
         dist.all_reduce(stats, op=dist.ReduceOp.SUM)

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -314,6 +314,58 @@ def pair_auc():
     if all(r[1] for r in gr + bi + nd):
         print('   spread between the two runs, GPU: gauc graded %.4f ms, gauc binary %.4f ms, ndcg %.4f ms'
               % tuple(abs(r[0][1] - r[1][1]) for r in (gr, bi, nd)))
+
+
+def pair_auc_sort():
+    """The two routes of the in-batch GAUC / AUC, walk against sort (rec_block/auc.py, route=): the shape of pair_auc() (B = 65 536, 1024 groups,
+    four label levels) under the graded and the binary rule; ONE list (in_batch_auc, graded rule, four levels) at every power of two from 1024
+    to 262 144 rows, which is the sweep `AUC_SORT_FROM` is set from; one list of 1 048 576 rows on the sort route alone (the walk would look at
+    1e12 candidates).  Wall time per call and GPU time (the call replayed from a HIP graph); the routes are measured in turn, twice, so the
+    spread between the two passes stands beside every ratio.  The walk gets few repetitions on the long lists."""
+    from rec_now_amd.rec_block.auc import in_batch_auc, in_batch_gauc
+    rng = np.random.default_rng(2)
+    out = [None]
+
+    def measure(tag, cases, n):
+        res = {name: [] for name, _ in cases}
+        for run in (1, 2):
+            for name, step in cases:
+                ms = timeit(step, n=n, warm=2)
+                value = float(out[0].item())
+                mg = timeit_graph(step, n=n)
+                res[name].append((ms, mg))
+                print('run %d  %s %s value=%.7f : wall %.3f ms per call, GPU %s' % (
+                    run, tag, name, value, ms, ('%.4f ms (graph replay)' % mg) if mg else 'not measured (no capture)'))
+        if 'walk' in res and 'sort' in res:
+            w, so = res['walk'], res['sort']
+            line = '   %s  walk / sort, wall: %.2fx, %.2fx' % (tag, w[0][0] / so[0][0], w[1][0] / so[1][0])
+            if all(r[1] for r in w + so):
+                line += ';  GPU: %.2fx, %.2fx;  spread between the two runs, GPU: walk %.4f ms, sort %.4f ms' % (
+                    w[0][1] / so[0][1], w[1][1] / so[1][1], abs(w[0][1] - w[1][1]), abs(so[0][1] - so[1][1]))
+            print(line)
+        return res
+
+    B, G = 65536, 1024
+    g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+    y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+    s = torch.randn(B, device=dev)
+
+    def gauc(route, **kw):
+        def step():
+            out[0] = in_batch_gauc(s, y, g, route=route, **kw).auc
+        return step
+    measure('in_batch_gauc graded B=%d groups=%d' % (B, G), (('walk', gauc('walk')), ('sort', gauc('sort'))), reps)
+    measure('in_batch_gauc pos_neg_th=1.5 B=%d groups=%d' % (B, G), (('walk', gauc('walk', pos_neg_th=1.5)), ('sort', gauc('sort', pos_neg_th=1.5))), reps)
+
+    def auc(route, s1, y1):
+        def step():
+            out[0] = in_batch_auc(s1, y1, route=route).auc
+        return step
+    for B1 in [1 << k for k in range(10, 19)] + [1 << 20]:
+        y1 = torch.from_numpy(rng.integers(0, 4, B1).astype(np.float32)).to(dev)
+        s1 = torch.randn(B1, device=dev)
+        cases = (('walk', auc('walk', s1, y1)), ('sort', auc('sort', s1, y1))) if B1 <= 262144 else (('sort', auc('sort', s1, y1)),)
+        measure('in_batch_auc graded, one list of B=%d' % B1, cases, reps if B1 <= 16384 else max(2, min(reps, (1 << 21) // B1)))
 
 
 def listwise():
@@ -1013,6 +1065,8 @@ if __name__ == '__main__':
         pair_lambda()
     if 'pair_auc' in which:
         pair_auc()
+    if 'pair_auc_sort' in which:
+        pair_auc_sort()
     if 'list' in which:
         listwise()
     if 'cin' in which:
