@@ -348,6 +348,36 @@ int recnow_softmax_ce_rows_fwd(const float* labels, const float* logits, int64_t
 int recnow_softmax_ce_rows_bwd(const float* labels, const float* logits, const float* row_lse, const float* row_psum,
                                const float* grow, int64_t G, int64_t N, float* dlogits, void* stream);
 
+/* In-batch ListMLE (ABI 23): the negative log-likelihood of the label-sorted permutation of every list under the Plackett-Luce model, on the
+ * caller's sorted segments (order / seg_id / seg_first / n_seg of recnow_group_segments on the lists' keys).  The reference has no such loss.
+ *   taking part   mask byte non-zero (mask may be NULL) and label not NaN; other rows get gradient 0 and influence nothing
+ *   permutation   the taking-part rows of a list by label descending (-0.0 == +0.0), ties by ascending row index; n rows, logits s_1 .. s_n
+ *   valid list    n >= 2 and at least two label values among the taking-part rows; valid lists are ranked by first occurrence in the batch
+ *   K             n when topn == 0, else min(topn, n)
+ *   list loss     l = sum_{p <= K} (lse_p - s_p), lse_p = log sum_{q >= p} exp(s_q); times 1 / K when list_mean; times weights[valid rank]
+ *   gradient      dl/ds_q = exp(s_q + logA_q) - [q <= K], logA_q = log sum_{p <= min(q, K)} exp(-lse_p); same factors
+ *   non-finite    a non-finite logit of a taking-part row makes its list's loss non-finite and its taking-part rows' gradients NaN, nothing else
+ * Every output is optional (NULL):
+ *   loss [1]        mean of the valid lists' losses, 0 when there is none          n_valid [1]   number of valid lists
+ *   dbase [B]       per original row: d (list loss) / d logit, 0 outside valid lists; divided by n_valid when `reduce` != 0
+ *   row_rank [B]    per original row: valid rank of its list, or -1                group_loss [B] per valid rank: the list's loss (first n_valid)
+ *   position [B]    per original row: 0-based place in its list's permutation, -1 when it does not take part
+ *   row_lse [B]     per original row: lse_p of its place, NaN when it does not take part
+ *   list_loss [B], list_valid [B]   per SEGMENT (sorted numbering, first n_seg): l before 1 / K and weight; validity
+ * weights: [B] readable entries, indexed by valid rank, or NULL.  The key words {seg_id, complement of the order-preserving image of the label}
+ * are sorted by recnow_group_segments inside, on this entry's workspace; two fp64 segmented scans (logaddexp from each list's end, then from its
+ * start) run over tiles of RECNOW_LISTMLE_TILE positions.  Where the caller's grouping or the inner one reported a grid-barrier time-out
+ * (n_seg[0] < 0), loss, every entry of dbase and of group_loss are NaN and n_valid = -1.
+ * RECNOW_EINVAL: B < 0, topn < 0, NULL order / seg_id / seg_first / n_seg / labels / logits / ws with B > 0; RECNOW_EWORKSPACE: ws_bytes below
+ * recnow_listmle_workspace_bytes(B).  B == 0 writes loss = 0 and n_valid = 0.  No host synchronisation, no atomics, bitwise reproducible, every
+ * launch can be captured in a HIP graph. */
+#define RECNOW_LISTMLE_TILE 1024
+size_t recnow_listmle_workspace_bytes(int64_t B);
+int recnow_listmle_fwdbwd(const float* labels, const float* logits, const uint8_t* mask, const float* weights, const int32_t* order,
+                          const int32_t* seg_id, const int32_t* seg_first, const int32_t* n_seg, int64_t B, int topn, int list_mean, int reduce,
+                          float* loss, int32_t* n_valid, float* dbase, int32_t* row_rank, float* group_loss, int32_t* position, double* row_lse,
+                          double* list_loss, int32_t* list_valid, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * FMLayer: rec_now/layers/fm_layer.py:24-42.   HBM-bound (12*B*F*D bytes fwd+bwd).
  *   y[b] = 0.5 * sum_d [ (sum_f x_f[b][d])^2 - sum_f x_f[b][d]^2 ]

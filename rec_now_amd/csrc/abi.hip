@@ -17,5 +17,6 @@
 // (LabelPairWeightTable: the fused pairwise loss with per-label-pair weights); 18: recnow_pair_kind_fwdbwd (hinge, squared-hinge and margin-logistic
 // pair terms on the fused route); 19: recnow_pair_lambda_terms / _fwdbwd / _workspace_bytes (the NDCG pair weight on the fused route, in-batch NDCG);
 // 20: recnow_pair_auc_terms / _workspace_bytes (in-batch GAUC from exact pair counts); 21: recnow_dcn_route (the route choice of recnow_dcn_fwd / _bwd, queryable);
-// 22: recnow_pair_auc_sorted_terms / _sorted_workspace_bytes (in-batch GAUC and AUC by sort and per-class prefix counts).
-extern "C" int recnow_abi_version(void) { return 22; }
+// 22: recnow_pair_auc_sorted_terms / _sorted_workspace_bytes (in-batch GAUC and AUC by sort and per-class prefix counts);
+// 23: recnow_listmle_fwdbwd / _workspace_bytes (in-batch ListMLE on segmented fp64 log-sum-exp scans).
+extern "C" int recnow_abi_version(void) { return 23; }

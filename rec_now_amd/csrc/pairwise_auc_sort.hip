@@ -27,6 +27,7 @@
 // Integer ballots, counts and compare-and-swaps only; no float atomics; prefix counts are int32 (B < 2**31), list sums int64; bitwise reproducible.
 #include <cmath>
 #include "common.hpp"
+#include "float_key.hpp"
 #include "pairwise_auc.hpp"
 
 #define AS_T RECNOW_AUC_SORT_TILE
@@ -80,13 +81,9 @@ SortAucWs as_ws(void* ws, int64_t B) {
     return a;
 }
 
-// order-preserving uint32 image of a float: a < b <=> key(a) < key(b), -0.0 and +0.0 share a key, every NaN has the one largest key
-__device__ __forceinline__ uint32_t as_key(float v) {
-    if (v != v) return AS_EMPTY;
-    if (v == 0.f) return 0x80000000u;
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// order-preserving uint32 image of a float (float_key.hpp): a < b <=> key(a) < key(b), -0.0 and +0.0 share a key, every NaN has the one largest key
+static_assert(AS_EMPTY == RN_FLOAT_KEY_NAN, "the key of a NaN is the empty slot of the value table");
+__device__ __forceinline__ uint32_t as_key(float v) { return rn_float_key(v); }
 
 // `key` into a 17-slot set: the first free slot, unless the key is there already.  A full set drops the key: slot 16 is then filled, which is the overflow flag.
 __device__ __forceinline__ void as_insert(uint32_t* tab, uint32_t key) {

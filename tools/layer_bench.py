@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -384,6 +384,79 @@ def listwise():
     mg = timeit_graph(step)
     if mg:
         print('   replayed from a HIP graph (GPU time of the step): %.3f ms  %.1f M rows/s' % (mg, B / mg / 1e3))
+
+
+def _listmle_torch(g, y, s):
+    """The ListMLE loss (all rows take part, no topn, mean over the valid lists) from torch operators: sort by (list, -label), pad to (G, Lmax),
+    torch.logcumsumexp, autograd -- what a user writes without rec_block/listmle.py.  One host synchronisation (Lmax) and another for G."""
+    B = s.numel()
+    _, inv = torch.unique(g, return_inverse=True)
+    o = torch.argsort(-y, stable=True)
+    o = o[torch.argsort(inv[o], stable=True)]                      # by list, inside a list by label descending, ties by row
+    lst, ys, ss = inv[o], y[o], s[o]
+    cnt = torch.bincount(lst)
+    G, lmax = cnt.numel(), int(cnt.max().item())
+    first = torch.cumsum(cnt, 0) - cnt
+    col = torch.arange(B, device=s.device) - first[lst]
+    pad = torch.full((G, lmax), float('-inf'), device=s.device, dtype=torch.float64)
+    pad = pad.index_put((lst, col), ss.double())
+    lse = torch.logcumsumexp(pad.flip(1), 1).flip(1)
+    per = torch.zeros(G, device=s.device, dtype=torch.float64).index_add(0, lst, lse[lst, col] - ss.double())
+    ymax = torch.full((G,), float('-inf'), device=s.device).scatter_reduce(0, lst, ys, 'amax')
+    ymin = torch.full((G,), float('inf'), device=s.device).scatter_reduce(0, lst, ys, 'amin')
+    valid = (cnt >= 2) & (ymax > ymin)
+    return (per * valid).sum() / valid.sum().clamp(min=1)
+
+
+def listmle():
+    """In-batch ListMLE (rec_block/listmle.py) forward + backward beside two yardsticks measured in the same run: the fused softmax
+    listwise_loss_from_batch, and the same ListMLE loss from torch operators (_listmle_torch).  Shapes: B = 65 536 in 1024 groups with four label
+    levels (the shape of the ranking blocks), and ONE list of 65 536 rows.  Wall time per call and GPU time (the call replayed from a HIP graph;
+    the torch composition synchronises the host and cannot be captured); the routes are measured in turn, twice."""
+    from rec_now_amd.rec_block.listmle import listmle_loss_from_batch
+    from rec_now_amd.rec_block.listwise_loss_from_batch import listwise_loss_from_batch
+    rng = np.random.default_rng(6)
+    B = 65536
+    out = [None]
+    for G in (1024, 1):
+        g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+        y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+        s = torch.randn(B, device=dev, requires_grad=True)
+
+        def fused():
+            s.grad = None
+            loss = listmle_loss_from_batch(g, y, s)
+            loss.backward()
+            out[0] = loss.detach()          # (no reference to the autograd graph stays behind: a capture after an eager step would not end otherwise)
+
+        def softmax():
+            s.grad = None
+            loss = listwise_loss_from_batch(g, (y > 1.5).float(), s)
+            loss.backward()
+            out[0] = loss.detach()
+
+        def composed():
+            s.grad = None
+            loss = _listmle_torch(g, y, s)
+            loss.backward()
+            out[0] = loss.detach()
+        cases = (('listmle fused', fused, True), ('softmax listwise fused', softmax, True), ('listmle torch operators', composed, False))
+        res = {name: [] for name, _, _ in cases}
+        for run in (1, 2):
+            for name, step, capture in cases:
+                ms = timeit(step)
+                value = float(out[0].item())
+                mg = timeit_graph(step) if capture else None
+                res[name].append((ms, mg))
+                print('run %d  %s B=%d groups=%d value=%.7f : wall %.3f ms per call, GPU %s' % (
+                    run, name, B, G, value, ms, ('%.4f ms (graph replay)' % mg) if mg else 'time not separable (host synchronisation: no capture)'))
+        f, so, to = (res[name] for name, _, _ in cases)
+        print('   groups=%d  wall: torch operators / fused = %.2fx, %.2fx;  fused / softmax = %.2fx, %.2fx;  spread between the two runs, wall: fused %.3f ms, '
+              'torch operators %.3f ms' % (G, to[0][0] / f[0][0], to[1][0] / f[1][0], f[0][0] / so[0][0], f[1][0] / so[1][0], abs(f[0][0] - f[1][0]),
+                                        abs(to[0][0] - to[1][0])))
+        if all(r[1] for r in f + so):
+            print('   groups=%d  GPU: fused / softmax = %.2fx, %.2fx;  spread between the two runs, GPU: fused %.4f ms' % (
+                G, f[0][1] / so[0][1], f[1][1] / so[1][1], abs(f[0][1] - f[1][1])))
 
 
 def cin():
@@ -1069,6 +1142,8 @@ if __name__ == '__main__':
         pair_auc_sort()
     if 'list' in which:
         listwise()
+    if 'listmle' in which:
+        listmle()
     if 'cin' in which:
         cin()
     if 'ple' in which:
