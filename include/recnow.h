@@ -378,6 +378,37 @@ int recnow_listmle_fwdbwd(const float* labels, const float* logits, const uint8_
                           float* loss, int32_t* n_valid, float* dbase, int32_t* row_rank, float* group_loss, int32_t* position, double* row_lse,
                           double* list_loss, int32_t* list_valid, void* ws, size_t ws_bytes, void* stream);
 
+/* In-batch ApproxNDCG (ABI 24; Qin, Liu and Li 2010): a differentiable NDCG loss on the caller's sorted segments (order / seg_id / seg_first /
+ * n_seg of recnow_group_segments), by two pair walks on the skeletons of the pairwise losses.  The reference has no such loss.
+ *   lists and rows   a list is one segment; a row takes part when its mask byte is non-zero (mask may be NULL).  Rows that do not take part
+ *                    influence nothing and get gradient exactly 0.
+ *   temperature      tau, a finite float greater than 0
+ *   soft position    R_i = sum_{j in the list, taking part, j != i} sigma((s_j - s_i) / tau), 0-based as D(r) = 1 / log2(2 + r)
+ *   gain             G(y) = 2**y - 1 (RECNOW_NDCG_GAIN_EXP2) or y (RECNOW_NDCG_GAIN_LINEAR)
+ *   ideal DCG        IDCG = sum G(y_i) D(q_i), q_i the label position of recnow_pair_lambda_terms (ties to the smaller original row index); no topn
+ *   valid list       IDCG > 0 (a NaN label of a taking-part row makes the comparison false: the list is invalid)
+ *   list loss        l = -ADCG / IDCG, ADCG = sum_i G(y_i) / log2(2 + R_i); the batch loss is the mean of l over the valid lists, 0 when none
+ *   gradient         c_i = G(y_i) ln 2 / ((2 + R_i) ln^2(2 + R_i));  sigma'_kj = sigma(x) (1 - sigma(x)), x = (s_j - s_k) / tau;
+ *                    dl/ds_k = (1 / (tau IDCG)) sum_{j != k, taking part} sigma'_kj (c_j - c_k); rows of an invalid list get exactly 0 (a select)
+ *   NaN scores       a NaN score of a taking-part row makes its own list's loss NaN (and so the batch mean) and that list's taking-part rows'
+ *                    gradients NaN; every other list's gradient bits stay as they were.  A row that does not take part may hold anything.
+ * Every output is optional (NULL):
+ *   loss [1]         float32 mean over the valid lists            loss_sum [1]   fp64 sum of l over the valid lists
+ *   n_lists [1]      int64 number of valid lists                  dscores [B]    per original row: d loss / d score (already divided by n_lists)
+ *   approx_rank [B]  fp64 per original row: R_i, NaN for a row that does not take part
+ *   list_adcg [B], list_idcg [B]   fp64 per SEGMENT (sorted numbering, first n_seg)
+ * float32 sigmoids from the hardware exp2 / rcp, the same bits for both rows of a pair; fp64 accumulators of R, fp64 per-row logarithms and
+ * list sums in fixed order; no pair list, no float atomics, no host synchronisation, bitwise reproducible, capturable in a HIP graph.
+ * Where the grouping reported a grid-barrier time-out (n_seg[0] < 0): loss, loss_sum and every entry of dscores NaN, n_lists = -1.
+ * RECNOW_EINVAL: B < 0, an unknown gain, a temperature that is not finite and > 0, NULL scores / labels / order / seg_id / seg_first / n_seg /
+ * ws with B > 0; RECNOW_EWORKSPACE: ws_bytes below recnow_approx_ndcg_workspace_bytes(B) (it begins with the pairwise workspace).  B == 0 writes
+ * loss = 0, loss_sum = 0 and n_lists = 0. */
+size_t recnow_approx_ndcg_workspace_bytes(int64_t B);
+int recnow_approx_ndcg_fwdbwd(const float* scores, const float* labels, const uint8_t* mask, const int32_t* order, const int32_t* seg_id,
+                              const int32_t* seg_first, const int32_t* n_seg, int64_t B, int gain, float temperature, float* loss,
+                              double* loss_sum, int64_t* n_lists, float* dscores, double* approx_rank, double* list_adcg, double* list_idcg,
+                              void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * FMLayer: rec_now/layers/fm_layer.py:24-42.   HBM-bound (12*B*F*D bytes fwd+bwd).
  *   y[b] = 0.5 * sum_d [ (sum_f x_f[b][d])^2 - sum_f x_f[b][d]^2 ]

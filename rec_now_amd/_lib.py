@@ -67,6 +67,8 @@ SIGNATURES = {
     'recnow_softmax_ce_rows_bwd': (_I, [_P, _P, _P, _P, _P, _L, _L, _P, _P]),
     'recnow_listmle_workspace_bytes': (_Z, [_L]),
     'recnow_listmle_fwdbwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_approx_ndcg_workspace_bytes': (_Z, [_L]),
+    'recnow_approx_ndcg_fwdbwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_fm_fwd': (_I, [_P, _I, _L, _I, _P, _P, _P]),
     'recnow_fm_bwd': (_I, [_P, _P, _I, _L, _I, _P, _P, _P]),
     'recnow_gemm_workspace_bytes': (_Z, [_P]),
@@ -195,7 +197,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 23 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 24 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -18,5 +18,6 @@
 // pair terms on the fused route); 19: recnow_pair_lambda_terms / _fwdbwd / _workspace_bytes (the NDCG pair weight on the fused route, in-batch NDCG);
 // 20: recnow_pair_auc_terms / _workspace_bytes (in-batch GAUC from exact pair counts); 21: recnow_dcn_route (the route choice of recnow_dcn_fwd / _bwd, queryable);
 // 22: recnow_pair_auc_sorted_terms / _sorted_workspace_bytes (in-batch GAUC and AUC by sort and per-class prefix counts);
-// 23: recnow_listmle_fwdbwd / _workspace_bytes (in-batch ListMLE on segmented fp64 log-sum-exp scans).
-extern "C" int recnow_abi_version(void) { return 23; }
+// 23: recnow_listmle_fwdbwd / _workspace_bytes (in-batch ListMLE on segmented fp64 log-sum-exp scans);
+// 24: recnow_approx_ndcg_fwdbwd / _workspace_bytes (in-batch ApproxNDCG on the pair-walk skeletons).
+extern "C" int recnow_abi_version(void) { return 24; }

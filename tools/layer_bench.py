@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
 import os
 import sys
 
@@ -457,6 +457,90 @@ def listmle():
         if all(r[1] for r in f + so):
             print('   groups=%d  GPU: fused / softmax = %.2fx, %.2fx;  spread between the two runs, GPU: fused %.4f ms' % (
                 G, f[0][1] / so[0][1], f[1][1] / so[1][1], abs(f[0][1] - f[1][1])))
+
+
+def _approx_ndcg_torch(g, y, s, tau=0.1):
+    """The ApproxNDCG loss (all rows take part, exp2 gain, mean over the lists with IDCG > 0) from torch operators: sort by list, pad to
+    (G, Lmax), a (G, Lmax, Lmax) sigmoid tensor, autograd -- what a user writes without rec_block/approx_ndcg.py.  float32; one host
+    synchronisation (Lmax)."""
+    B = s.numel()
+    _, inv = torch.unique(g, return_inverse=True)
+    o = torch.argsort(inv, stable=True)
+    lst, ys, ss = inv[o], y[o], s[o]
+    cnt = torch.bincount(lst)
+    G, lmax = cnt.numel(), int(cnt.max().item())
+    first = torch.cumsum(cnt, 0) - cnt
+    col = torch.arange(B, device=s.device) - first[lst]
+    real = torch.zeros((G, lmax), dtype=torch.bool, device=s.device).index_put((lst, col), torch.ones((), dtype=torch.bool, device=s.device))
+    sp = torch.zeros((G, lmax), device=s.device).index_put((lst, col), ss)
+    gain = (torch.exp2(torch.zeros((G, lmax), device=s.device).index_put((lst, col), ys)) - 1.0) * real
+    ok = real[:, None, :] & real[:, :, None] & ~torch.eye(lmax, dtype=torch.bool, device=s.device)
+    R = (torch.sigmoid((sp[:, None, :] - sp[:, :, None]) / tau) * ok).sum(2)
+    adcg = (gain / torch.log2(2.0 + R)).sum(1)
+    idcg = (gain.sort(1, descending=True).values / torch.log2(2.0 + torch.arange(lmax, device=s.device))).sum(1)
+    valid = idcg > 0
+    return -((adcg / idcg.clamp(min=1e-30)) * valid).sum() / valid.sum().clamp(min=1)
+
+
+def approx_ndcg():
+    """In-batch ApproxNDCG (rec_block/approx_ndcg.py) forward + backward beside two yardsticks measured in the same run: the fused BPR loss with
+    the NDCG pair weight (pairwise_loss(lambda_weight=NDCGLambdaWeight()): one walk more, the same one exponential per candidate), and the same
+    ApproxNDCG loss from torch operators (_approx_ndcg_torch).  Shapes: B = 65 536 in 1024 groups with four label levels, and ONE list of
+    65 536 rows (quadratic in the list length on every route; the torch composition would need a 65 536 x 65 536 tensor there and is left
+    out).  Wall time per call and GPU time (the call replayed from a HIP graph; the torch composition synchronises the host and cannot be
+    captured); the routes are measured in turn, twice."""
+    from rec_now_amd.rec_block.approx_ndcg import approx_ndcg_loss
+    from rec_now_amd.rec_block.ndcg import NDCGLambdaWeight
+    from rec_now_amd.rec_block.pairwise_loss_from_batch import pairwise_loss
+    rng = np.random.default_rng(6)
+    B = 65536
+    lam = NDCGLambdaWeight()
+    out = [None]
+    for G in (1024, 1):
+        g = torch.from_numpy(rng.integers(0, G, B).astype(np.float32)).to(dev)
+        y = torch.from_numpy(rng.integers(0, 4, B).astype(np.float32)).to(dev)
+        s = torch.randn(B, device=dev, requires_grad=True)
+
+        def fused():
+            s.grad = None
+            loss = approx_ndcg_loss(s, y, g)
+            loss.backward()
+            out[0] = loss.detach()          # (no reference to the autograd graph stays behind: a capture after an eager step would not end otherwise)
+
+        def bpr_lambda():
+            s.grad = None
+            loss = pairwise_loss(s, y, g, lambda_weight=lam)
+            loss.backward()
+            out[0] = loss.detach()
+
+        def composed():
+            s.grad = None
+            loss = _approx_ndcg_torch(g, y, s)
+            loss.backward()
+            out[0] = loss.detach()
+        cases = [('approx_ndcg fused', fused, True), ('BPR + lambda fused', bpr_lambda, True)]
+        if G > 1:
+            cases.append(('approx_ndcg torch operators', composed, False))
+        res = {name: [] for name, _, _ in cases}
+        n = reps if G > 1 else max(3, reps // 10)
+        for run in (1, 2):
+            for name, step, capture in cases:
+                ms = timeit(step, n=n, warm=10 if G > 1 else 2)
+                value = float(out[0].item())
+                mg = timeit_graph(step, n=n) if capture else None
+                res[name].append((ms, mg))
+                print('run %d  %s B=%d groups=%d value=%.7f : wall %.3f ms per fwd+bwd, GPU %s' % (
+                    run, name, B, G, value, ms, ('%.4f ms (graph replay)' % mg) if mg else 'time not separable (host synchronisation: no capture)'))
+        f, bl = res['approx_ndcg fused'], res['BPR + lambda fused']
+        line = '   groups=%d  wall: approx_ndcg fused / BPR + lambda fused = %.2fx, %.2fx' % (G, f[0][0] / bl[0][0], f[1][0] / bl[1][0])
+        if G > 1:
+            to = res['approx_ndcg torch operators']
+            line += ';  torch operators / fused = %.2fx, %.2fx;  spread between the two runs, wall: fused %.3f ms, torch operators %.3f ms' % (
+                to[0][0] / f[0][0], to[1][0] / f[1][0], abs(f[0][0] - f[1][0]), abs(to[0][0] - to[1][0]))
+        print(line)
+        if all(r[1] for r in f + bl):
+            print('   groups=%d  GPU: approx_ndcg fused / BPR + lambda fused = %.2fx, %.2fx;  spread between the two runs, GPU: fused %.4f ms, '
+                  'BPR + lambda %.4f ms' % (G, f[0][1] / bl[0][1], f[1][1] / bl[1][1], abs(f[0][1] - f[1][1]), abs(bl[0][1] - bl[1][1])))
 
 
 def cin():
@@ -1144,6 +1228,8 @@ if __name__ == '__main__':
         listwise()
     if 'listmle' in which:
         listmle()
+    if 'approx_ndcg' in which:
+        approx_ndcg()
     if 'cin' in which:
         cin()
     if 'ple' in which:
