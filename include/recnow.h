@@ -1144,6 +1144,34 @@ int recnow_can_bwd(const float* x, const float* params, const float* g, const fl
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * BilinearInteractionLayer (ABI 25): the bilinear cross of FiBiNET (Huang, Zhang and Zhang 2019, arXiv 1905.09433, section 3.3).
+ * csrc/bilinear.hip.  fields / dfields: DEVICE arrays of F device pointers to contiguous (B, D) fp32 tensors, as for InnerPNN; the
+ * P = F(F-1)/2 pairs (i, j), i < j, in InnerPNN's i-major order, pair p at i*F - i(i+1)/2 + (j - i - 1).
+ *   out[b][p*D + d] = (x_i[b] W[w(p)])[d] * x_j[b][d],   out (B, P*D),   W (nW, D, D) row-major
+ *   type RECNOW_BILINEAR_ALL: w(p) = 0, nW = 1;  _EACH: w(p) = i, nW = F-1;  _INTERACTION: w(p) = p, nW = P.
+ * fp32 FMA on exact fp32 operands; U = X W is formed on chip and never written.  F == 1 or B == 0: RECNOW_OK without a launch
+ * from _fwd.  recnow_bilinear_bwd recomputes U and writes every row of every dfields[f] once (zeros for F == 1); with dW non-NULL
+ * it also writes the weight gradient (nW, D, D): fp32 sums per row chunk, the chunks combined in fp64 in a fixed order -- no
+ * float atomics, the same input gives the same bits on every run.  ws is only needed with dW: recnow_bilinear_workspace_bytes =
+ *   ['all', 'each': 4 B (F-1) D, the dU rows] + 4 G S D^2 (S = F-1 or P slots, G <= 256 row chunks, G S D^2 floats <= 32 MiB or
+ *   G = 1), each part rounded up to 256 bytes; it does not grow as B P D^2.
+ * recnow_bilinear_supported: host-only, 1 for 1 <= F <= 64, 1 <= D <= 64 and a known type; other shapes: RECNOW_EUNSUPPORTED from
+ * _fwd / _bwd.  16-byte accesses need D % 4 == 0 and 16-byte aligned tensors; anything else takes guarded 4-byte accesses in the
+ * same kernels.  recnow_bilinear_route: host-only, the kernel family of a direction (bwd 0 / 1): 0 one wave per sample with the
+ * weights resident in LDS, 1 the same with the weights read through L2 (they do not fit), 2 a tile of samples per workgroup with
+ * the weights of a batch of pairs staged per tile ('interaction').
+ * ---------------------------------------------------------------------------------------------------------- */
+#define RECNOW_BILINEAR_ALL 0
+#define RECNOW_BILINEAR_EACH 1
+#define RECNOW_BILINEAR_INTERACTION 2
+int recnow_bilinear_supported(int F, int D, int type);
+int recnow_bilinear_route(int F, int D, int type, int bwd);
+size_t recnow_bilinear_workspace_bytes(int64_t B, int F, int D, int type);
+int recnow_bilinear_fwd(const float* const* fields, int F, int64_t B, int D, int type, const float* W, float* out, void* stream);
+int recnow_bilinear_bwd(const float* const* fields, float* const* dfields, int F, int64_t B, int D, int type, const float* W,
+                        const float* dout, float* dW, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

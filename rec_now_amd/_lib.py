@@ -165,6 +165,11 @@ SIGNATURES = {
     'recnow_can_supported': (_I, [_I, _P, _I, _I]),
     'recnow_can_fwd': (_I, [_P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'recnow_can_bwd': (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'recnow_bilinear_supported': (_I, [_I, _I, _I]),
+    'recnow_bilinear_route': (_I, [_I, _I, _I, _I]),
+    'recnow_bilinear_workspace_bytes': (_Z, [_L, _I, _I, _I]),
+    'recnow_bilinear_fwd': (_I, [_P, _I, _L, _I, _I, _P, _P, _P]),
+    'recnow_bilinear_bwd': (_I, [_P, _P, _I, _L, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -197,7 +202,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 24 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 25 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

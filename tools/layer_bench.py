@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear]"""
 import os
 import sys
 
@@ -862,6 +862,72 @@ def can():
         torch.cuda.empty_cache()
 
 
+def bilinear_ref_eager(xs, W, kind, ii, jj):
+    """BilinearInteractionLayer from torch operators: the projection of the left fields in one matmul ('all') or one einsum over the stacked
+    weights ('each'), gathered to the pairs -- or, for 'interaction', an einsum over the gathered (B, P, D) left operands -- times the gathered
+    right operands."""
+    X = torch.stack(xs, 1)                                   # (B, F, D)
+    if kind == 'all':
+        up = (X[:, :-1] @ W[0])[:, ii]
+    elif kind == 'each':
+        up = torch.einsum('bfk,fkd->bfd', X[:, :-1], W)[:, ii]
+    else:
+        up = torch.einsum('bpk,pkd->bpd', X[:, ii], W)
+    return (up * X[:, jj]).reshape(X.shape[0], -1)
+
+
+def bilinear():
+    """BilinearInteractionLayer forward + backward (all gradients) at B = 65 536: F 24, D 16 for the three types, then F 40, D 32 for 'all'.  Wall
+    time and graph-replay GPU time, the cases in turn, twice, with the spread between the two passes; beside the same layer from torch operators
+    in the same run.  GB/s of the byte model: forward 4 B (F D + P D), backward 4 B (2 F D + P D) bytes."""
+    from rec_now_amd.layers.bilinear_interaction_layer import BilinearInteractionLayer
+    B = 65536
+    cases = [(24, 16, 'all'), (24, 16, 'each'), (24, 16, 'interaction'), (40, 32, 'all')]
+    seen = {}
+    for rnd in (1, 2):
+        for F, D, kind in cases:
+            P = F * (F - 1) // 2
+            xs = [torch.randn(B, D, device=dev, requires_grad=True) for _ in range(F)]
+            layer = BilinearInteractionLayer(kind)
+            layer([x[:2] for x in xs])
+            W = layer.bilinear_weight
+            gy = torch.randn(B, P * D, device=dev)
+            ii, jj = torch.triu_indices(F, F, 1, device=dev)
+            run, ref = (lambda: layer(xs)), (lambda: bilinear_ref_eager(xs, W, kind, ii, jj))
+            with torch.no_grad():
+                err = (run() - ref()).abs().max().item()
+
+            def fb_of(fn):
+                def step():
+                    return torch.autograd.grad(fn(), xs + [W], gy)
+                return step
+
+            def fwd_of(fn):
+                def step():
+                    with torch.no_grad():
+                        return fn()
+                return step
+            fwd_bytes, bwd_bytes = 4.0 * B * (F * D + P * D), 4.0 * B * (2 * F * D + P * D)
+            fb_bytes = fwd_bytes + bwd_bytes
+            ms_f, ms_fb = timeit(fwd_of(run)), timeit(fb_of(run))
+            gf, gfb = timeit_graph(fwd_of(run)), timeit_graph(fb_of(run))
+            rfb, rgfb = timeit(fb_of(ref)), timeit_graph(fb_of(ref))
+            gf, gfb, rgfb = gf or float('nan'), gfb or float('nan'), rgfb or float('nan')
+            print('pass %d BilinearInteraction %-11s B=%d F=%d D=%d P=%d : wall fwd %.3f ms %.0f GB/s, fwd+bwd %.3f ms %.0f GB/s | graph fwd %.3f ms %.0f GB/s, '
+                  'bwd %.3f ms %.0f GB/s, fwd+bwd %.3f ms %.0f GB/s | torch operators fwd+bwd: wall %.3f ms, graph %.3f ms -> fused is %.2fx (wall) %.2fx (graph) '
+                  '| max |y - torch| %.2g' % (rnd, kind, B, F, D, P, ms_f, fwd_bytes / ms_f / 1e6, ms_fb, fb_bytes / ms_fb / 1e6, gf, fwd_bytes / gf / 1e6,
+                                            gfb - gf, bwd_bytes / (gfb - gf) / 1e6, gfb, fb_bytes / gfb / 1e6, rfb, rgfb, rfb / ms_fb, rgfb / gfb, err), flush=True)
+            seen.setdefault((F, D, kind), []).append((gfb, rgfb))
+            del xs, gy, layer, W
+            torch.cuda.empty_cache()
+    for (F, D, kind), ((a, ra), (b, rb)) in seen.items():
+        spread = abs(a - b) / min(a, b)
+        worst = min(ra, rb) / max(a, b)
+        print('BilinearInteraction %-11s F=%d D=%d : fused fwd+bwd (graph) %.3f / %.3f ms, spread between the passes %.1f %%; torch %.3f / %.3f ms; '
+              'fused faster in both passes by at least %.1f %% -> %s' % (kind, F, D, a, b, 100 * spread, ra, rb, 100 * (worst - 1),
+                                                                       'faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread'))
+
+
 def gnn_ref_eager(x, indices, ws, L, F):
     """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
     from the weight vector, matmul, add, tanh; transpose back and flatten."""
@@ -1239,6 +1305,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear)):
         if name in which:
             fn()
