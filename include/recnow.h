@@ -1172,6 +1172,34 @@ int recnow_bilinear_bwd(const float* const* fields, float* const* dfields, int F
                         const float* dout, float* dW, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * InteractingLayer (ABI 26): the multi-head self-attention over the fields of AutoInt (Song et al. 2019, arXiv 1810.11921,
+ * section 4.3).  csrc/autoint.hip.  fields / dfields: DEVICE arrays of F device pointers; field f of sample b is the D floats at
+ * fields[f] + b * xstride (dfields[f] + b * dxstride), one row stride in floats for all fields, >= D -- a (B, F, D) tensor and the
+ * column views of a (B, F*D) tensor pass without a copy.  H heads of width d, E = H d; Wq, Wk, Wv, Wr (D, E) row-major, Wr NULL
+ * without the residual projection.
+ *   Q = X Wq, K = X Wk, V = X Wv;  S_h = Q_h K_h^T (times 1/sqrt(d) with scaling != 0);  A_h = softmax over the keys, row maximum
+ *   subtracted;  pre = concat_h A_h V_h (+ X Wr);  out[b][f*E + e] = relu(pre) (relu != 0) or pre,  out (B, F*E) contiguous.
+ * fp32 FMA on exact fp32 operands, the exponential through the hardware exp2; Q, K, V, S, A and pre stay on chip.  B == 0:
+ * RECNOW_OK without a launch.  recnow_autoint_bwd recomputes the chain from the fields and writes every row of every dfields[f]
+ * once; the ReLU subgradient at 0 is 0.  dWq, dWk, dWv (and dWr with Wr) are either all given or all NULL; NULL: no weight-gradient
+ * launch and ws is not read.  Otherwise fp32 partials per workgroup (a contiguous chunk of samples) are combined in fp64 in a
+ * fixed tree: no float atomics, the same input gives the same bits on every run.  recnow_autoint_workspace_bytes =
+ *   4 G nW D E rounded up to 256 bytes, nW = 3 + use_res, G = max(1, min(ceil(B / 8), 1024, 32 MiB / (4 nW D E))).
+ * recnow_autoint_supported: host-only, 1 for 1 <= F, D, E <= 64 and 1 <= H <= 8; other shapes: RECNOW_EUNSUPPORTED from _fwd /
+ * _bwd.  16-byte accesses need widths and row strides that are multiples of 4 floats and 16-byte aligned bases; anything else
+ * takes guarded 4-byte accesses in the same kernels.  recnow_autoint_route: host-only, for a direction (bwd 0 / 1): 0 the weights
+ * (and the backward's weight-gradient accumulators) resident in LDS, 1 read (accumulated) through L2 because they do not fit.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_autoint_supported(int F, int D, int H, int d);
+int recnow_autoint_route(int F, int D, int H, int d, int use_res, int bwd);
+size_t recnow_autoint_workspace_bytes(int64_t B, int F, int D, int H, int d, int use_res);
+int recnow_autoint_fwd(const float* const* fields, int64_t xstride, int F, int64_t B, int D, int H, int d, const float* Wq,
+                       const float* Wk, const float* Wv, const float* Wr, int scaling, int relu, float* out, void* stream);
+int recnow_autoint_bwd(const float* const* fields, int64_t xstride, float* const* dfields, int64_t dxstride, int F, int64_t B, int D,
+                       int H, int d, const float* Wq, const float* Wk, const float* Wv, const float* Wr, int scaling, int relu,
+                       const float* dout, float* dWq, float* dWk, float* dWv, float* dWr, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

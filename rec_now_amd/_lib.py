@@ -170,6 +170,11 @@ SIGNATURES = {
     'recnow_bilinear_workspace_bytes': (_Z, [_L, _I, _I, _I]),
     'recnow_bilinear_fwd': (_I, [_P, _I, _L, _I, _I, _P, _P, _P]),
     'recnow_bilinear_bwd': (_I, [_P, _P, _I, _L, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'recnow_autoint_supported': (_I, [_I, _I, _I, _I]),
+    'recnow_autoint_route': (_I, [_I, _I, _I, _I, _I, _I]),
+    'recnow_autoint_workspace_bytes': (_Z, [_L, _I, _I, _I, _I, _I]),
+    'recnow_autoint_fwd': (_I, [_P, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
+    'recnow_autoint_bwd': (_I, [_P, _L, _P, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -202,7 +207,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 25 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 26 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

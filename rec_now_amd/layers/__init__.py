@@ -3,5 +3,6 @@ from .bilinear_interaction_layer import BilinearInteractionLayer  # noqa: F401
 from .can_layer import CANLayer  # noqa: F401
 from .cartesian_product_layer import CartesianProductLayer, CrossedIds  # noqa: F401
 from .fix_length_layer import FixLengthLayer  # noqa: F401
+from .interacting_layer import InteractingLayer  # noqa: F401
 from .multi_hash_layer import FastMultiHashLayer, MultiHashLayer  # noqa: F401
 from .pooling_layer import PoolingLayer  # noqa: F401
