@@ -1200,6 +1200,35 @@ int recnow_autoint_bwd(const float* const* fields, int64_t xstride, float* const
                        const float* dout, float* dWq, float* dWk, float* dWv, float* dWr, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * AFMLayer (ABI 27): the attention-pooled pairwise interaction of AFM (Xiao et al. 2017, arXiv 1708.04617, section 3).
+ * csrc/afm.hip.  fields / dfields as for recnow_autoint_*: DEVICE arrays of F device pointers, field f of sample b at
+ * fields[f] + b * xstride, one row stride in floats for all fields, >= D.  A = attention_factor; W (D, A) row-major, b (A), h (A),
+ * p (D) or NULL without the projection.  Pairs k = (i, j), i < j, in InnerPNN's i-major order:
+ *   p_k = x_i * x_j;  z_k = W^T p_k + b;  e_k = <relu(z_k), h>;  a = softmax of e over the pairs (maximum subtracted);
+ *   v = sum_k a_k p_k;  out[b] = <v, p> (out (B, 1)) with p, else out[b][0 .. D) = v (out (B, D) contiguous).
+ * fp32 FMA on exact fp32 operands, the exponential through the hardware exp2; neither the pair products nor the hidden layer
+ * leave the chip.  B == 0: RECNOW_OK without a launch.  recnow_afm_bwd (dout shaped like out) recomputes the chain from the
+ * fields and writes every row of every dfields[f] once; the ReLU subgradient at 0 is 0.  dW, db, dh (and dp with p) are either
+ * all given or all NULL; NULL: no weight-gradient work, no reduce launch, and ws is not read.  Otherwise fp32 partials per
+ * workgroup (one wave over a contiguous chunk of samples) are combined in fp64 in a fixed tree: no float atomics, the same
+ * input gives the same bits on every run.  recnow_afm_workspace_bytes =
+ *   4 G n rounded up to 256 bytes, n = 4 ceil((D A + 2 A + D) / 4), G = max(1, min(ceil(B / 4), 4096, 32 MiB / (4 n))).
+ * recnow_afm_supported: host-only, 1 for 2 <= F <= 64 and 1 <= D, A <= 64; other shapes: RECNOW_EUNSUPPORTED from _fwd / _bwd
+ * (a single field has no pair: the layer answers it with zeros without a call).  16-byte accesses need widths and row strides
+ * that are multiples of 4 floats and 16-byte aligned bases; anything else takes guarded 4-byte accesses in the same kernels.
+ * recnow_afm_route: host-only, for a direction (bwd 0 / 1): 0, the one route built (one wave per sample, tiles in wave-private
+ * LDS, weights through the scalar cache), or RECNOW_EUNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_afm_supported(int F, int D, int A);
+int recnow_afm_route(int F, int D, int A, int bwd);
+size_t recnow_afm_workspace_bytes(int64_t B, int F, int D, int A);
+int recnow_afm_fwd(const float* const* fields, int64_t xstride, int F, int64_t B, int D, int A, const float* W, const float* b,
+                   const float* h, const float* p, float* out, void* stream);
+int recnow_afm_bwd(const float* const* fields, int64_t xstride, float* const* dfields, int64_t dxstride, int F, int64_t B, int D,
+                   int A, const float* W, const float* b, const float* h, const float* p, const float* dout, float* dW, float* db,
+                   float* dh, float* dp, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

@@ -175,6 +175,11 @@ SIGNATURES = {
     'recnow_autoint_workspace_bytes': (_Z, [_L, _I, _I, _I, _I, _I]),
     'recnow_autoint_fwd': (_I, [_P, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
     'recnow_autoint_bwd': (_I, [_P, _L, _P, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_afm_supported': (_I, [_I, _I, _I]),
+    'recnow_afm_route': (_I, [_I, _I, _I, _I]),
+    'recnow_afm_workspace_bytes': (_Z, [_L, _I, _I, _I]),
+    'recnow_afm_fwd': (_I, [_P, _L, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'recnow_afm_bwd': (_I, [_P, _L, _P, _L, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -207,7 +212,7 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 26 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 27 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -21,5 +21,6 @@
 // 23: recnow_listmle_fwdbwd / _workspace_bytes (in-batch ListMLE on segmented fp64 log-sum-exp scans);
 // 24: recnow_approx_ndcg_fwdbwd / _workspace_bytes (in-batch ApproxNDCG on the pair-walk skeletons);
 // 25: recnow_bilinear_fwd / _bwd / _supported / _route / _workspace_bytes (BilinearInteractionLayer);
-// 26: recnow_autoint_fwd / _bwd / _supported / _route / _workspace_bytes (InteractingLayer).
-extern "C" int recnow_abi_version(void) { return 26; }
+// 26: recnow_autoint_fwd / _bwd / _supported / _route / _workspace_bytes (InteractingLayer);
+// 27: recnow_afm_fwd / _bwd / _supported / _route / _workspace_bytes (AFMLayer).
+extern "C" int recnow_abi_version(void) { return 27; }

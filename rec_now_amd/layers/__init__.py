@@ -1,4 +1,5 @@
 """rec_now_amd.layers -- MI355X-native counterparts of rec_now/layers (same module and symbol names)."""
+from .afm_layer import AFMLayer  # noqa: F401
 from .bilinear_interaction_layer import BilinearInteractionLayer  # noqa: F401
 from .can_layer import CANLayer  # noqa: F401
 from .cartesian_product_layer import CartesianProductLayer, CrossedIds  # noqa: F401

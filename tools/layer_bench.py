@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm]"""
 import os
 import sys
 
@@ -990,6 +990,68 @@ def autoint():
                                                                            'faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread'))
 
 
+def afm_ref_eager(x, W, b, h, p, ii, jj):
+    """AFMLayer from torch operators: the gathered pair products (B, P, D), the hidden layer as one matmul, ReLU, the scores as a second matmul,
+    softmax over the pairs, the weighted sum and the projection."""
+    pk = x[:, ii] * x[:, jj]
+    a = torch.softmax(torch.relu(pk @ W + b) @ h, 1)        # (B, P, 1)
+    return (a * pk).sum(1) @ p
+
+
+def afm():
+    """AFMLayer forward + backward (all gradients) at B = 65 536 on a (B, F, D) input: F 24, D 16, A 16, then F 40, D 32, A 32.  Wall time and
+    graph-replay GPU time, the cases in turn, twice, with the spread between the two passes; beside the same layer from torch operators (gather,
+    matmul, softmax, autograd) in the same run.  GB/s of the byte model: forward 4 B (F D + D), backward 4 B (2 F D + D) bytes."""
+    from rec_now_amd.layers.afm_layer import AFMLayer
+    B = 65536
+    cases = [(24, 16, 16), (40, 32, 32)]
+    seen = {}
+    for rnd in (1, 2):
+        for F, D, A in cases:
+            x = torch.randn(B, F, D, device=dev, requires_grad=True)
+            layer = AFMLayer(A)
+            layer(x[:2].detach())
+            Ws = [layer.attention_W, layer.attention_b, layer.projection_h, layer.projection_p]
+            gy = torch.randn(B, 1, device=dev)
+            ii, jj = torch.triu_indices(F, F, 1, device=dev)
+            run, ref = (lambda: layer(x)), (lambda: afm_ref_eager(x, *Ws, ii, jj))
+            with torch.no_grad():
+                err = (run() - ref()).abs().max().item()
+
+            def fb_of(fn):
+                def step():
+                    return torch.autograd.grad(fn(), [x] + Ws, gy)
+                return step
+
+            def fwd_of(fn):
+                def step():
+                    with torch.no_grad():
+                        return fn()
+                return step
+            fwd_bytes, bwd_bytes = 4.0 * B * (F * D + D), 4.0 * B * (2 * F * D + D)
+            fb_bytes = fwd_bytes + bwd_bytes
+            ms_f, ms_fb = timeit(fwd_of(run)), timeit(fb_of(run))
+            gf, gfb = timeit_graph(fwd_of(run)), timeit_graph(fb_of(run))
+            rf, rfb, rgf, rgfb = timeit(fwd_of(ref)), timeit(fb_of(ref)), timeit_graph(fwd_of(ref)), timeit_graph(fb_of(ref))
+            gf, gfb, rgf, rgfb = (v or float('nan') for v in (gf, gfb, rgf, rgfb))
+            print('pass %d AFMLayer B=%d F=%d D=%d A=%d : wall fwd %.3f ms %.0f GB/s, fwd+bwd %.3f ms %.0f GB/s | graph fwd %.3f ms %.0f GB/s, '
+                  'bwd %.3f ms %.0f GB/s, fwd+bwd %.3f ms %.0f GB/s | torch operators: wall fwd %.3f ms, fwd+bwd %.3f ms, graph fwd %.3f ms, fwd+bwd %.3f ms '
+                  '-> fused is %.2fx (fwd, graph) %.2fx (bwd, graph) %.2fx (fwd+bwd, wall) %.2fx (fwd+bwd, graph) | max |y - torch| %.2g'
+                  % (rnd, B, F, D, A, ms_f, fwd_bytes / ms_f / 1e6, ms_fb, fb_bytes / ms_fb / 1e6, gf, fwd_bytes / gf / 1e6, gfb - gf,
+                     bwd_bytes / (gfb - gf) / 1e6, gfb, fb_bytes / gfb / 1e6, rf, rfb, rgf, rgfb, rgf / gf, (rgfb - rgf) / (gfb - gf), rfb / ms_fb,
+                     rgfb / gfb, err), flush=True)
+            seen.setdefault((F, D, A), []).append((gfb, rgfb, gf, rgf))
+            del x, gy, layer, Ws
+            torch.cuda.empty_cache()
+    for (F, D, A), ((a, ra, af, raf), (b, rb, bf, rbf)) in seen.items():
+        for what, (p, q, rp, rq) in (('fwd', (af, bf, raf, rbf)), ('bwd', (a - af, b - bf, ra - raf, rb - rbf)), ('fwd+bwd', (a, b, ra, rb))):
+            spread = abs(p - q) / min(p, q)
+            worst = min(rp, rq) / max(p, q)
+            print('AFMLayer F=%d D=%d A=%d : fused %s (graph) %.3f / %.3f ms, spread between the passes %.1f %%; torch %.3f / %.3f ms; '
+                  'fused faster in both passes by at least %.1f %% -> %s' % (F, D, A, what, p, q, 100 * spread, rp, rq, 100 * (worst - 1),
+                                                                           'faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread'))
+
+
 def gnn_ref_eager(x, indices, ws, L, F):
     """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
     from the weight vector, matmul, add, tanh; transpose back and flatten."""
@@ -1367,6 +1429,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm)):
         if name in which:
             fn()
