@@ -19,11 +19,12 @@
 // as csrc/autoint.hip does), dxt = dv * (a X), then per block of four hidden units: recompute z, write dz to qt, add (dz X) W^T to dxt.
 //
 // Weight gradient: the wave adds its samples' contributions, in sample order, into its own slab of the workspace (every element is owned by
-// one lane; the first sample stores, the others add); k_afm_dw_reduce adds the slabs of the G waves in fp64 in a fixed tree.  A slab is
+// one lane; the first sample stores, the others add); rn_part_reduce (partials.hpp) adds the slabs of the G waves in fp64 in a fixed tree.  A slab is
 // [dW (D A) | db (A) | dh (A) | dp (D)] padded to n = 4 ceil((D A + 2 A + D) / 4) floats.
-// Workspace (recnow_afm_workspace_bytes): G n floats rounded up to 256 bytes, G = max(1, min(ceil(B / AFM_DW_ROWS), AFM_MAXG, AFM_PART_BYTES / (4 n))).
+// Workspace (recnow_afm_workspace_bytes): G n floats rounded up to 256 bytes, G = rn_part_groups(B, AFM_DW_ROWS, AFM_MAXG, n) = max(1, min(ceil(B / AFM_DW_ROWS), AFM_MAXG, RN_PART_BYTES / (4 n))).
 #include "common.hpp"
-#include "wave_softmax.hpp"                     // AI_WAVE_SYNC, ai_wave_red4, ai_exp
+#include "wave_softmax.hpp"                     // ai_wave_red4, ai_exp
+#include "partials.hpp"
 #include <math.h>
 
 #define AFM_MAX_F 64
@@ -32,28 +33,13 @@
 #define AFM_LDS_BYTES (160 * 1024)
 #define AFM_MAXG 4096                           // waves (and weight-gradient partials) of a launch at the most
 #define AFM_DW_ROWS 4                           // samples of one wave at the least
-#define AFM_PART_BYTES (32u << 20)
 
 struct AfmDesc {
     int F, D, A, P, PP, DQ, DS, DQP, qsh, proj, nS;
     int64_t B, xs, dxs, rows;                   // xs / dxs: row strides of the fields / their gradients; rows: samples per wave
 };
 
-__device__ __forceinline__ bool afm_vec(const void* p, int width, int64_t stride) {
-    return (width & 3) == 0 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
-// up to four floats from p; n = valid floats at p (anything <= 0: none)
-__device__ __forceinline__ rn_f4 afm_ld4(const float* p, int n, bool vec) {
-    if (vec) return *reinterpret_cast<rn_gcf4>((rn_gcf)p);
-    rn_f4 v = {0.f, 0.f, 0.f, 0.f};
-    rn_gcf g = (rn_gcf)p;
-    if (n > 0) v.x = g[0];
-    if (n > 1) v.y = g[1];
-    if (n > 2) v.z = g[2];
-    if (n > 3) v.w = g[3];
-    return v;
-}
-// the same for an address that is the same in every lane of the wave and whose memory no kernel of the launch writes (weights, the upstream
+// rn_ld4 for an address that is the same in every lane of the wave and whose memory no kernel of the launch writes (weights, the upstream
 // gradient): read through the constant address space, the load goes to the scalar unit and its cache and costs no vector or LDS cycle
 typedef const float __attribute__((address_space(4)))* afm_ccf;
 typedef const rn_f4 __attribute__((address_space(4)))* afm_ccf4;
@@ -67,15 +53,6 @@ __device__ __forceinline__ rn_f4 afm_ldu4(const float* p, int n, bool vec) {
     if (n > 3) v.w = g[3];
     return v;
 }
-__device__ __forceinline__ void afm_st4(float* p, rn_f4 v, int n, bool vec) {
-    if (vec) { *reinterpret_cast<rn_gf4>((rn_gf)p) = v; return; }
-    rn_gf g = (rn_gf)p;
-    if (n > 0) g[0] = v.x;
-    if (n > 1) g[1] = v.y;
-    if (n > 2) g[2] = v.z;
-    if (n > 3) g[3] = v.w;
-}
-__device__ __forceinline__ float afm_dot4(rn_f4 a, rn_f4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
 __device__ __forceinline__ float afm_red_sum(float v) { return ai_wave_red4<false>(rn_f4{v, 0.f, 0.f, 0.f}, 64).x; }
 __device__ __forceinline__ float afm_red_max(float v) { return ai_wave_red4<true>(rn_f4{v, v, v, v}, 64).x; }
 // sum over the lanes lane, lane ^ DQP, lane ^ 2 DQP, ..: the fields of one column quad
@@ -123,7 +100,7 @@ template <bool UNI>
 __device__ __forceinline__ rn_f4 afm_dv4(const AfmDesc& c, const AfmW& w, const float* dout, int64_t b, float gb, int q, bool vg) {
     const float* src = c.proj ? w.p + 4 * q : dout + b * c.D + 4 * q;
     const bool vec = c.proj ? w.vp : vg;
-    const rn_f4 v = UNI ? afm_ldu4(src, c.D - 4 * q, vec) : afm_ld4(src, c.D - 4 * q, vec);
+    const rn_f4 v = UNI ? afm_ldu4(src, c.D - 4 * q, vec) : rn_ld4(src, c.D - 4 * q, vec);
     return c.proj ? gb * v : v;
 }
 // the fields of sample b -> xt
@@ -131,9 +108,9 @@ __device__ __forceinline__ void afm_load(const AfmDesc& c, const float* const* f
     for (int e = lane; e < c.F * c.DQ; e += 64) {
         const int f = e / c.DQ, q = e - f * c.DQ;
         const float* xf = fields[f];
-        *reinterpret_cast<rn_f4*>(xt + f * c.DS + 4 * q) = afm_ld4(xf + b * c.xs + 4 * q, c.D - 4 * q, afm_vec(xf, c.D, c.xs));
+        *reinterpret_cast<rn_f4*>(xt + f * c.DS + 4 * q) = rn_ld4(xf + b * c.xs + 4 * q, c.D - 4 * q, rn_vec4_ok(xf, c.D, c.xs));
     }
-    AI_WAVE_SYNC();
+    RN_LDS_WAVE_SYNC();
 }
 // st <- the attention a of the sample in xt; BWD: dt <- de = a (da - sum a da), da_k = <dv, p_k>
 template <bool BWD, bool FAST>
@@ -147,7 +124,7 @@ __device__ __forceinline__ void afm_attention(const AfmDesc& c, const AfmW& w, c
         const rn_f4* xj = reinterpret_cast<const rn_f4*>(xt + j * c.DS);
         if (BWD) {
             float da = 0.f;
-            for (int cq = 0; cq < c.DQ; ++cq) da += afm_dot4(afm_dv4<true>(c, w, dout, b, gb, cq, vg), xi[cq] * xj[cq]);
+            for (int cq = 0; cq < c.DQ; ++cq) da += rn_dot4(afm_dv4<true>(c, w, dout, b, gb, cq, vg), xi[cq] * xj[cq]);
             dt[k] = da;
         }
         float e = 0.f;
@@ -155,7 +132,7 @@ __device__ __forceinline__ void afm_attention(const AfmDesc& c, const AfmW& w, c
             rn_f4 z = afm_z4<FAST>(c, w, xi, xj, a0);
 #pragma unroll
             for (int u = 0; u < 4; ++u) z[u] = z[u] > 0.f ? z[u] : 0.f;
-            e += afm_dot4(z, afm_ldu4(w.h + a0, c.A - a0, w.vh));
+            e += rn_dot4(z, afm_ldu4(w.h + a0, c.A - a0, w.vh));
         }
         st[k] = e;
         m = e > m ? e : m;
@@ -186,7 +163,7 @@ __device__ __forceinline__ void afm_attention(const AfmDesc& c, const AfmW& w, c
         s2 = afm_red_sum(s2);
         for (int k = lane; k < c.P; k += 64) dt[k] = st[k] * (dt[k] - s2);
     }
-    AI_WAVE_SYNC();
+    RN_LDS_WAVE_SYNC();
 }
 // sum over j != i of s[pair(i, j)] * x_j[4 q .. 4 q + 3]
 __device__ __forceinline__ rn_f4 afm_mix1(const AfmDesc& c, const float* xt, const float* s, int i, int q) {
@@ -224,7 +201,7 @@ template <bool FAST>
 __device__ __forceinline__ AfmW afm_weights(const AfmDesc& c, const float* W, const float* bias, const float* h, const float* p) {
     AfmW w;
     w.W = W; w.b = bias; w.h = h; w.p = p;
-    w.vw = FAST || afm_vec(W, c.A, 0); w.vb = FAST || afm_vec(bias, c.A, 0); w.vh = FAST || afm_vec(h, c.A, 0); w.vp = c.proj && afm_vec(p, c.D, 0);
+    w.vw = FAST || rn_vec4_ok(W, c.A, 0); w.vb = FAST || rn_vec4_ok(bias, c.A, 0); w.vh = FAST || rn_vec4_ok(h, c.A, 0); w.vp = c.proj && rn_vec4_ok(p, c.D, 0);
     return w;
 }
 
@@ -239,7 +216,7 @@ k_afm_fwd(const float* const* __restrict__ fields, float* __restrict__ out, cons
     float* xt = afm_lds;
     float* st = xt + c.F * c.DS;
     const AfmW w = afm_weights<FAST>(c, W, bias, h, p);
-    const bool vo = afm_vec(out, c.D, 0);
+    const bool vo = rn_vec4_ok(out, c.D, 0);
     const int64_t r0 = (int64_t)blockIdx.x * c.rows, r1 = min(c.B, r0 + c.rows);
     for (int64_t b = r0; b < r1; ++b) {
         afm_load(c, fields, xt, b, lane);
@@ -252,12 +229,12 @@ k_afm_fwd(const float* const* __restrict__ fields, float* __restrict__ out, cons
         v = 0.5f * afm_red_fields(v, c.DQP);
         const bool owner = slot == 0 && q < c.DQ;
         if (c.proj) {
-            const float o = afm_red_sum(owner ? afm_dot4(v, afm_ld4(p + 4 * q, c.D - 4 * q, w.vp)) : 0.f);
+            const float o = afm_red_sum(owner ? rn_dot4(v, rn_ld4(p + 4 * q, c.D - 4 * q, w.vp)) : 0.f);
             if (lane == 0) out[b] = o;
         } else if (owner) {
-            afm_st4(out + b * c.D + 4 * q, v, c.D - 4 * q, vo);
+            rn_st4(out + b * c.D + 4 * q, v, c.D - 4 * q, vo);
         }
-        AI_WAVE_SYNC();                                     // tiles read before the next sample overwrites them
+        RN_LDS_WAVE_SYNC();                                     // tiles read before the next sample overwrites them
     }
 }
 
@@ -275,7 +252,7 @@ k_afm_bwd(const float* const* __restrict__ fields, float* const* __restrict__ df
     float* qt = dt + c.PP;
     float* st = qt;                                         // dead before qt is first written
     const AfmW w = afm_weights<FAST>(c, W, bias, h, p);
-    const bool vg = !c.proj && afm_vec(dout, D, 0);
+    const bool vg = !c.proj && rn_vec4_ok(dout, D, 0);
     const bool owner = slot == 0 && q < c.DQ;
     float* slab = part ? part + (int64_t)blockIdx.x * c.nS : nullptr;
     float* sb = slab + D * A;                               // db, then dh, then dp
@@ -301,10 +278,10 @@ k_afm_bwd(const float* const* __restrict__ fields, float* const* __restrict__ df
             v = 0.5f * afm_red_fields(v, c.DQP);
             if (owner) {
                 float* s = sb + 2 * A + 4 * q;
-                afm_st4(s, (first ? zero : afm_ld4(s, D - 4 * q, vsp)) + gb * v, D - 4 * q, vsp);
+                rn_st4(s, (first ? zero : rn_ld4(s, D - 4 * q, vsp)) + gb * v, D - 4 * q, vsp);
             }
         }
-        AI_WAVE_SYNC();                                     // st consumed: qt may be written
+        RN_LDS_WAVE_SYNC();                                     // st consumed: qt may be written
         for (int a0 = 0; a0 < A; a0 += 4) {
             const rn_f4 h4 = afm_ldu4(h + a0, A - a0, w.vh);
             rn_f4 dh4 = zero, db4 = zero;
@@ -327,17 +304,17 @@ k_afm_bwd(const float* const* __restrict__ fields, float* const* __restrict__ df
                 db4 = ai_wave_red4<false>(db4, 64);
                 if (lane == 0) {
                     float* s = sb + a0;
-                    afm_st4(s, (first ? zero : afm_ld4(s, A - a0, vsa)) + db4, A - a0, vsa);
+                    rn_st4(s, (first ? zero : rn_ld4(s, A - a0, vsa)) + db4, A - a0, vsa);
                     s += A;
-                    afm_st4(s, (first ? zero : afm_ld4(s, A - a0, vsa)) + dh4, A - a0, vsa);
+                    rn_st4(s, (first ? zero : rn_ld4(s, A - a0, vsa)) + dh4, A - a0, vsa);
                 }
             }
-            AI_WAVE_SYNC();
+            RN_LDS_WAVE_SYNC();
             // dxt_i += W[:, a] * (dz_a X)_i;  dW[:, a] += 1/2 x_i * (dz_a X)_i
             rn_f4 wr[4], dw[4];
 #pragma unroll
             for (int cc = 0; cc < 4; ++cc) {
-                wr[cc] = q < c.DQ && 4 * q + cc < D ? afm_ld4(W + (4 * q + cc) * A + a0, A - a0, w.vw) : zero;
+                wr[cc] = q < c.DQ && 4 * q + cc < D ? rn_ld4(W + (4 * q + cc) * A + a0, A - a0, w.vw) : zero;
                 dw[cc] = zero;
             }
             for (int i0 = 0; i0 < F; i0 += ipw) {
@@ -364,44 +341,18 @@ k_afm_bwd(const float* const* __restrict__ fields, float* const* __restrict__ df
                     dw[cc] = 0.5f * afm_red_fields(dw[cc], c.DQP);
                     if (owner && 4 * q + cc < D) {
                         float* s = slab + (4 * q + cc) * A + a0;
-                        afm_st4(s, (first ? zero : afm_ld4(s, A - a0, vsa)) + dw[cc], A - a0, vsa);
+                        rn_st4(s, (first ? zero : rn_ld4(s, A - a0, vsa)) + dw[cc], A - a0, vsa);
                     }
                 }
             }
-            AI_WAVE_SYNC();                                 // qt read before the next block overwrites it
+            RN_LDS_WAVE_SYNC();                                 // qt read before the next block overwrites it
         }
         for (int e = lane; e < F * c.DQ; e += 64) {
             const int f = e / c.DQ, qq = e - f * c.DQ;
             float* df = dfields[f];
-            afm_st4(df + b * c.dxs + 4 * qq, *reinterpret_cast<const rn_f4*>(dxt + f * DS + 4 * qq), D - 4 * qq, afm_vec(df, D, c.dxs));
+            rn_st4(df + b * c.dxs + 4 * qq, *reinterpret_cast<const rn_f4*>(dxt + f * DS + 4 * qq), D - 4 * qq, rn_vec4_ok(df, D, c.dxs));
         }
-        AI_WAVE_SYNC();
-    }
-}
-
-// One output element per group of 64 threads (4 per workgroup): thread c adds the partials c, c + 64, .. of the element in fp64, then the 64
-// sums are added in lane order by one thread -- a fixed tree.  Element e of a slab: dW [0, DA), db [DA, DA + A), dh, then dp.
-__global__ void __launch_bounds__(256)
-k_afm_dw_reduce(const float* __restrict__ part, float* __restrict__ dW, float* __restrict__ db, float* __restrict__ dh, float* __restrict__ dp,
-                int DA, int A, int n, int nS, int G) {
-    __shared__ double red[256];
-    const int c = threadIdx.x & 63, sub = threadIdx.x >> 6;
-    for (int e0 = blockIdx.x * 4; e0 < n; e0 += gridDim.x * 4) {
-        const int e = e0 + sub;
-        double acc = 0.0;
-        if (e < n)
-            for (int g = c; g < G; g += 64) acc += (double)part[(int64_t)g * nS + e];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        if (c == 0 && e < n) {
-            double tot = 0.0;
-            for (int g = 0; g < 64; ++g) tot += red[sub * 64 + g];
-            if (e < DA) dW[e] = (float)tot;
-            else if (e < DA + A) db[e - DA] = (float)tot;
-            else if (e < DA + 2 * A) dh[e - DA - A] = (float)tot;
-            else dp[e - DA - 2 * A] = (float)tot;
-        }
-        __syncthreads();
+        RN_LDS_WAVE_SYNC();
     }
 }
 
@@ -415,14 +366,7 @@ static inline bool afm_fast(int D, int A, const float* W, const float* b, const 
     return ((D | A) & 3) == 0 && ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(h)) & 15) == 0;
 }
 static inline int afm_slab(int D, int A) { return (D * A + 2 * A + D + 3) & ~3; }
-static int afm_groups(int64_t B, int D, int A) {
-    int64_t g = (B + AFM_DW_ROWS - 1) / AFM_DW_ROWS;
-    const int64_t cap = (int64_t)AFM_PART_BYTES / (4ll * afm_slab(D, A));
-    if (g > cap) g = cap;
-    if (g > AFM_MAXG) g = AFM_MAXG;
-    if (g < 1) g = 1;
-    return (int)g;
-}
+static int afm_groups(int64_t B, int D, int A) { return rn_part_groups(B, AFM_DW_ROWS, AFM_MAXG, afm_slab(D, A)); }
 static AfmDesc afm_desc(int F, int64_t B, int D, int A, int proj, int bwd, int64_t xs, int64_t dxs, size_t* lds, int* grid) {
     AfmDesc c;
     c.F = F; c.D = D; c.A = A; c.P = F * (F - 1) / 2; c.PP = (c.P + 3) & ~3;
@@ -442,19 +386,6 @@ static AfmDesc afm_desc(int F, int64_t B, int D, int A, int proj, int bwd, int64
     *grid = (int)((B + c.rows - 1) / c.rows);               // <= G (<= afm_groups in the backward), every wave has a sample
     return c;
 }
-// more than 64 KiB of dynamic LDS has to be asked for, once per device
-static int afm_big_lds() {
-    static bool done[64];
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        RN_HIP(hipFuncSetAttribute((const void*)k_afm_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AFM_LDS_BYTES));
-        RN_HIP(hipFuncSetAttribute((const void*)k_afm_bwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AFM_LDS_BYTES));
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return 0;
-}
-
 extern "C" int recnow_afm_supported(int F, int D, int A) { return afm_shape_ok(F, D, A) ? 1 : 0; }
 
 extern "C" int recnow_afm_route(int F, int D, int A, int bwd) {
@@ -499,15 +430,15 @@ extern "C" int recnow_afm_bwd(const float* const* fields, int64_t xstride, float
     int grid;
     size_t lds;
     const AfmDesc c = afm_desc(F, B, D, A, p ? 1 : 0, 1, xstride, dxstride, &lds, &grid);
-    if (lds > 64 * 1024) RN_HIP((hipError_t)afm_big_lds());
     hipStream_t st = (hipStream_t)stream;
-    if (afm_fast(D, A, W, b, h)) hipLaunchKernelGGL(k_afm_bwd<true>, grid, 64, lds, st, fields, dfields, dout, part, W, b, h, p, c);
+    const bool fast = afm_fast(D, A, W, b, h);
+    // F = D = 64: two F x DS tiles and five PP rows are 75 136 bytes
+    if (lds > 64 * 1024) RN_HIP(rn_lds_grant(fast ? (const void*)k_afm_bwd<true> : (const void*)k_afm_bwd<false>, AFM_LDS_BYTES));
+    if (fast) hipLaunchKernelGGL(k_afm_bwd<true>, grid, 64, lds, st, fields, dfields, dout, part, W, b, h, p, c);
     else hipLaunchKernelGGL(k_afm_bwd<false>, grid, 64, lds, st, fields, dfields, dout, part, W, b, h, p, c);
     RN_LAUNCH_CHECK();
-    if (part) {
-        const int n = D * A + 2 * A + (p ? D : 0);
-        hipLaunchKernelGGL(k_afm_dw_reduce, (n + 3) / 4, 256, 0, st, part, dW, db, dh, dp, D * A, A, n, c.nS, grid);
-        RN_LAUNCH_CHECK();
-    }
-    return RECNOW_OK;
+    if (!part) return RECNOW_OK;
+    const int DA = D * A;
+    const RnPartDst dst = {{dW, db, dh, dp}, {DA, DA + A, DA + 2 * A, DA + 2 * A + (p ? D : 0)}};
+    return rn_part_reduce(part, dst.end[3], 1, grid, c.nS, 0, dst, st);
 }

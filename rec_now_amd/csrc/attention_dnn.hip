@@ -391,11 +391,7 @@ DnPlan dn_plan(int64_t B, int L, int D, int nl, const int* dims, bool bwd) {
 
 template <int NH, bool BWD>
 int dn_launch(const DnArgs& a, const DnPlan& p, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        RN_HIP(hipFuncSetAttribute((const void*)k_din<NH, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
+    RN_HIP(rn_lds_grant((const void*)k_din<NH, BWD>, 160 * 1024));        // the input tile of every layer stays in LDS: above 64 KiB from D = 256 on
     hipLaunchKernelGGL((k_din<NH, BWD>), dim3((unsigned)p.grid), DN_THREADS, p.lds, st, a);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;

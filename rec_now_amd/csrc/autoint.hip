@@ -19,11 +19,12 @@
 // workgroup's slab of the workspace (every element is owned by one thread: a fixed order either way).
 //
 // Weight gradient: after every batch of `waves` samples the whole workgroup adds  X^T dQ, X^T dK, X^T dV, X^T dpre  of those samples, in
-// sample then field order, to its fp32 partial; k_ai_dw_reduce adds the partials of the G workgroups in fp64 in a fixed tree.
+// sample then field order, to its fp32 partial; rn_part_reduce (partials.hpp) adds the partials of the G workgroups in fp64 in a fixed tree.
 // Workspace (recnow_autoint_workspace_bytes): G * nW * D * E floats rounded up to 256 bytes, nW = 3 + use_res,
-//   G = max(1, min(ceil(B / AI_DW_ROWS), AI_MAXG, AI_PART_BYTES / (4 nW D E))).
+//   G = rn_part_groups(B, AI_DW_ROWS, AI_MAXG, nW D E) = max(1, min(ceil(B / AI_DW_ROWS), AI_MAXG, RN_PART_BYTES / (4 nW D E))).
 #include "common.hpp"
-#include "wave_softmax.hpp"                     // AI_WAVE_SYNC, ai_wave_red4, ai_exp
+#include "wave_softmax.hpp"                     // ai_wave_red4, ai_exp
+#include "partials.hpp"
 #include <math.h>
 
 #define AI_ROUTE_LDS 0
@@ -35,7 +36,6 @@
 #define AI_LDS_BYTES (160 * 1024)
 #define AI_MAXG 1024                            // workgroups (and weight-gradient partials) of a launch at the most
 #define AI_DW_ROWS 8                            // samples of one workgroup at the least
-#define AI_PART_BYTES (32u << 20)
 
 struct AiDesc {
     int F, D, E, H, d, DQ, EQ, DP, EP, ES, FS, fp2, nW, wres, relu, bwd, wavefl;
@@ -47,41 +47,14 @@ struct AiTiles {
     float *xt, *qt, *kt, *vt, *gt, *pt, *at;    // gt: dqt, dkt, dvt (backward only); at: the 4-row tile
 };
 
-__device__ __forceinline__ bool ai_vec(const void* p, int width, int64_t stride) {
-    return (width & 3) == 0 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
-// up to four floats from p; n = valid floats at p (anything <= 0: none)
-__device__ __forceinline__ rn_f4 ai_ld4(const float* p, int n, bool vec) {
-    if (vec) return *reinterpret_cast<rn_gcf4>((rn_gcf)p);
-    rn_f4 v = {0.f, 0.f, 0.f, 0.f};
-    rn_gcf g = (rn_gcf)p;
-    if (n > 0) v.x = g[0];
-    if (n > 1) v.y = g[1];
-    if (n > 2) v.z = g[2];
-    if (n > 3) v.w = g[3];
-    return v;
-}
-__device__ __forceinline__ void ai_st4(float* p, rn_f4 v, int n, bool vec) {
-    if (vec) { *reinterpret_cast<rn_gf4>((rn_gf)p) = v; return; }
-    rn_gf g = (rn_gf)p;
-    if (n > 0) g[0] = v.x;
-    if (n > 1) g[1] = v.y;
-    if (n > 2) g[2] = v.z;
-    if (n > 3) g[3] = v.w;
-}
-__device__ __forceinline__ void ai_st4_stream(float* p, rn_f4 v, int n, bool vec) {
-    if (vec) { RN_ST_STREAM(reinterpret_cast<rn_gf4>((rn_gf)p), v); return; }
-    ai_st4(p, v, n, false);
-}
-__device__ __forceinline__ float ai_dot4(rn_f4 a, rn_f4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
 __device__ __forceinline__ const float* ai_wptr(const AiDesc& c, int m) { return m == 0 ? c.Wq : m == 1 ? c.Wk : m == 2 ? c.Wv : c.Wr; }
 // W_m[k][e .. e+3], zeros past E
 __device__ __forceinline__ rn_f4 ai_w4(const AiDesc& c, const float* wl, int m, int k, int e, bool vw) {
     if (c.wres) return *reinterpret_cast<const rn_f4*>(wl + (m * c.D + k) * c.ES + e);
-    return ai_ld4(ai_wptr(c, m) + k * c.E + e, c.E - e, vw);
+    return rn_ld4(ai_wptr(c, m) + k * c.E + e, c.E - e, vw);
 }
 __device__ __forceinline__ bool ai_w_vec(const AiDesc& c) {
-    return ai_vec(c.Wq, c.E, 0) && ai_vec(c.Wk, c.E, 0) && ai_vec(c.Wv, c.E, 0) && (c.nW < 4 || ai_vec(c.Wr, c.E, 0));
+    return rn_vec4_ok(c.Wq, c.E, 0) && rn_vec4_ok(c.Wk, c.E, 0) && rn_vec4_ok(c.Wv, c.E, 0) && (c.nW < 4 || rn_vec4_ok(c.Wr, c.E, 0));
 }
 __device__ __forceinline__ AiTiles ai_tiles(const AiDesc& c, float* base) {
     const int T = c.EP * c.FS;
@@ -105,7 +78,7 @@ __device__ __forceinline__ void ai_prologue(const AiDesc& c, float* lds, int nwa
         for (int e = threadIdx.x; e < c.nW * c.D * SQ; e += blockDim.x) {
             const int row = e / SQ, q = e - row * SQ, m = row / c.D, k = row - m * c.D;
             rn_f4 v = {0.f, 0.f, 0.f, 0.f};
-            if (q < c.EQ) v = ai_ld4(ai_wptr(c, m) + k * c.E + 4 * q, c.E - 4 * q, vw);
+            if (q < c.EQ) v = rn_ld4(ai_wptr(c, m) + k * c.E + 4 * q, c.E - 4 * q, vw);
             *reinterpret_cast<rn_f4*>(lds + row * c.ES + 4 * q) = v;
         }
         if (c.bwd) wfl += c.nW * c.D * c.EP;
@@ -150,11 +123,11 @@ __device__ __forceinline__ void ai_sample_fwd(const AiDesc& c, const float* cons
     for (int e = lane; e < c.F * c.DQ; e += 64) {
         const int f = e / c.DQ, q = e - f * c.DQ;
         const float* xf = fields[f];
-        const rn_f4 v = ai_ld4(xf + b * c.xs + 4 * q, c.D - 4 * q, ai_vec(xf, c.D, c.xs));
+        const rn_f4 v = rn_ld4(xf + b * c.xs + 4 * q, c.D - 4 * q, rn_vec4_ok(xf, c.D, c.xs));
         float* o = t.xt + 4 * q * FS + f;
         o[0] = v.x; o[FS] = v.y; o[2 * FS] = v.z; o[3 * FS] = v.w;
     }
-    AI_WAVE_SYNC();
+    RN_LDS_WAVE_SYNC();
     const int per = c.F * c.EQ;
     for (int e = lane; e < c.nW * per; e += 64) {
         const int m = e / per, r = e - m * per, f = r / c.EQ, q = r - f * c.EQ;
@@ -166,7 +139,7 @@ __device__ __forceinline__ void ai_sample_fwd(const AiDesc& c, const float* cons
         for (int u = 0; u < 4; ++u)
             if (4 * q + u < c.E) o[u * FS] = acc[u];
     }
-    AI_WAVE_SYNC();
+    RN_LDS_WAVE_SYNC();
     const int jj = min(lane, FS - 1);
     const bool valid = lane < c.F;
     for (int h = 0; h < c.H; ++h) {
@@ -177,7 +150,7 @@ __device__ __forceinline__ void ai_sample_fwd(const AiDesc& c, const float* cons
 #pragma unroll
                 for (int u = 0; u < 4; ++u) t.at[u * FS + lane] = a[u];
             }
-            AI_WAVE_SYNC();
+            RN_LDS_WAVE_SYNC();
             for (int e = lane; e < 4 * c.d; e += 64) {
                 const int u = e / c.d, cc = e - u * c.d, i = 4 * ib + u;
                 const float o = ai_rowdot(c, t.at + u * FS, t.vt + (h * c.d + cc) * FS);
@@ -186,7 +159,7 @@ __device__ __forceinline__ void ai_sample_fwd(const AiDesc& c, const float* cons
                     *p = (c.nW == 4 ? *p : 0.f) + o;
                 }
             }
-            AI_WAVE_SYNC();                                 // `at` read before the next block overwrites it
+            RN_LDS_WAVE_SYNC();                                 // `at` read before the next block overwrites it
         }
     }
 }
@@ -198,7 +171,7 @@ k_ai_fwd(const float* const* __restrict__ fields, float* __restrict__ out, AiDes
     ai_prologue(c, ai_lds, nw);
     const float* wl = ai_lds;
     const AiTiles t = ai_tiles(c, ai_lds + (c.wres ? c.nW * c.D * c.ES : 0) + w * c.wavefl);
-    const bool vw = ai_w_vec(c), vo = ai_vec(out, c.E, 0);
+    const bool vw = ai_w_vec(c), vo = rn_vec4_ok(out, c.E, 0);
     const int64_t r0 = (int64_t)blockIdx.x * c.rows, r1 = min(c.B, r0 + c.rows);
     for (int64_t b = r0 + w; b < r1; b += nw) {
         ai_sample_fwd(c, fields, wl, vw, t, b, lane);
@@ -210,9 +183,9 @@ k_ai_fwd(const float* const* __restrict__ fields, float* __restrict__ out, AiDes
 #pragma unroll
                 for (int u = 0; u < 4; ++u) v[u] = (v[u] > 0.f || v[u] != v[u]) ? v[u] : 0.f;       // a NaN stays a NaN
             }
-            ai_st4_stream(out + (b * c.F + f) * c.E + 4 * q, v, c.E - 4 * q, vo);
+            rn_st4_stream(out + (b * c.F + f) * c.E + 4 * q, v, c.E - 4 * q, vo);
         }
-        AI_WAVE_SYNC();                                     // tiles read before the next sample overwrites them
+        RN_LDS_WAVE_SYNC();                                     // tiles read before the next sample overwrites them
     }
 }
 
@@ -231,13 +204,13 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
     float* dqt = t.gt;
     float* dkt = dqt + T;
     float* dvt = dkt + T;
-    const bool vw = ai_w_vec(c), vg = ai_vec(dout, E, 0), vs = (E & 3) == 0;
+    const bool vw = ai_w_vec(c), vg = rn_vec4_ok(dout, E, 0), vs = (E & 3) == 0;
     float* slab = part ? part + (int64_t)blockIdx.x * c.nW * D * E : nullptr;
     const int nitem = c.nW * D * c.EQ;                      // (m, k, e quad) items of the weight gradient, one owner thread each
     if (slab && !c.wres)
         for (int it = threadIdx.x; it < nitem; it += blockDim.x) {
             const int row = it / c.EQ, q = it - row * c.EQ;
-            ai_st4(slab + row * E + 4 * q, rn_f4{0.f, 0.f, 0.f, 0.f}, E - 4 * q, vs);
+            rn_st4(slab + row * E + 4 * q, rn_f4{0.f, 0.f, 0.f, 0.f}, E - 4 * q, vs);
         }
     const int jj = min(lane, FS - 1);
     const bool valid = lane < F;
@@ -249,7 +222,7 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
             // pt: pre -> dpre;  dkt, dvt: cleared (dqt is written whole)
             for (int e = lane; e < F * c.EQ; e += 64) {
                 const int f = e / c.EQ, q = e - f * c.EQ;
-                const rn_f4 g = ai_ld4(dout + (b * F + f) * E + 4 * q, E - 4 * q, vg);
+                const rn_f4 g = rn_ld4(dout + (b * F + f) * E + 4 * q, E - 4 * q, vg);
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
                     if (4 * q + u < E) {
@@ -259,7 +232,7 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
                     }
             }
             for (int e = lane; e < 2 * T; e += 64) dkt[e] = 0.f;
-            AI_WAVE_SYNC();
+            RN_LDS_WAVE_SYNC();
             for (int h = 0; h < c.H; ++h) {
                 const int hd = h * c.d;
                 for (int ib = 0; 4 * ib < F; ++ib) {
@@ -270,7 +243,7 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
                     for (int cc = 0; cc < c.d; ++cc) {
                         const rn_f4 g4 = *reinterpret_cast<const rn_f4*>(t.pt + (hd + cc) * FS + 4 * ib);
                         dA += g4 * t.vt[(hd + cc) * FS + jj];
-                        if (valid) dvt[(hd + cc) * FS + lane] += ai_dot4(a, g4);
+                        if (valid) dvt[(hd + cc) * FS + lane] += rn_dot4(a, g4);
                     }
                     // dS = a (dA - sum a dA) does not change when dA is shifted; shifted by the dA of the row's top key, a near one-hot
                     // row (a_top ~ 1, dA_top - sum a dA cancelling) keeps its small dS_top to full precision
@@ -288,18 +261,18 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
                     for (int u = 0; u < 4; ++u) dS[u] = valid ? a[u] * (dA[u] - rd[u]) : 0.f;
                     // dK_j += sum_i dS[i][j] Q_i (Q carries the scale);  dQ_i = scale * sum_j dS[i][j] K_j
                     for (int cc = 0; cc < c.d; ++cc)
-                        if (valid) dkt[(hd + cc) * FS + lane] += ai_dot4(dS, *reinterpret_cast<const rn_f4*>(t.qt + (hd + cc) * FS + 4 * ib));
+                        if (valid) dkt[(hd + cc) * FS + lane] += rn_dot4(dS, *reinterpret_cast<const rn_f4*>(t.qt + (hd + cc) * FS + 4 * ib));
                     if (lane < FS) {
 #pragma unroll
                         for (int u = 0; u < 4; ++u) t.at[u * FS + lane] = dS[u];
                     }
-                    AI_WAVE_SYNC();
+                    RN_LDS_WAVE_SYNC();
                     for (int e = lane; e < 4 * c.d; e += 64) {
                         const int u = e / c.d, cc = e - u * c.d, i = 4 * ib + u;
                         const float o = ai_rowdot(c, t.at + u * FS, t.kt + (hd + cc) * FS);
                         if (i < F) dqt[(hd + cc) * FS + i] = o * c.scale;
                     }
-                    AI_WAVE_SYNC();
+                    RN_LDS_WAVE_SYNC();
                 }
             }
             // dX_f = dQ_f Wq^T + dK_f Wk^T + dV_f Wv^T (+ dpre_f Wr^T)
@@ -314,13 +287,13 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
                     for (int e2 = 0; e2 < EP; e2 += 4) {
                         const rn_f4 p = {tl[e2 * FS], tl[(e2 + 1) * FS], tl[(e2 + 2) * FS], tl[(e2 + 3) * FS]};
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) acc[u] += ai_dot4(ai_w4(c, wl, m, kk[u], e2, vw), p);
+                        for (int u = 0; u < 4; ++u) acc[u] += rn_dot4(ai_w4(c, wl, m, kk[u], e2, vw), p);
                     }
                 }
                 float* df = dfields[f];
-                ai_st4(df + b * c.dxs + 4 * kq, acc, D - 4 * kq, ai_vec(df, D, c.dxs));
+                rn_st4(df + b * c.dxs + 4 * kq, acc, D - 4 * kq, rn_vec4_ok(df, D, c.dxs));
             }
-            AI_WAVE_SYNC();
+            RN_LDS_WAVE_SYNC();
         }
         if (slab) {
             __syncthreads();                                // every wave's tiles are complete
@@ -334,14 +307,14 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
                     for (int f = 0; f < FS - 4; f += 4) {
                         const rn_f4 x4 = *reinterpret_cast<const rn_f4*>(xr + f);
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) acc[u] += ai_dot4(x4, *reinterpret_cast<const rn_f4*>(tl + u * FS + f));
+                        for (int u = 0; u < 4; ++u) acc[u] += rn_dot4(x4, *reinterpret_cast<const rn_f4*>(tl + u * FS + f));
                     }
                 }
                 if (c.wres) {
                     *reinterpret_cast<rn_f4*>(dwl + row * EP + 4 * q) += acc;
                 } else {
                     float* s = slab + row * E + 4 * q;
-                    ai_st4(s, ai_ld4(s, E - 4 * q, vs) + acc, E - 4 * q, vs);
+                    rn_st4(s, rn_ld4(s, E - 4 * q, vs) + acc, E - 4 * q, vs);
                 }
             }
             __syncthreads();                                // tiles consumed
@@ -350,34 +323,8 @@ k_ai_bwd(const float* const* __restrict__ fields, float* const* __restrict__ dfi
     if (slab && c.wres)
         for (int it = threadIdx.x; it < nitem; it += blockDim.x) {
             const int row = it / c.EQ, q = it - row * c.EQ;
-            ai_st4(slab + row * E + 4 * q, *reinterpret_cast<const rn_f4*>(dwl + row * EP + 4 * q), E - 4 * q, vs);
+            rn_st4(slab + row * E + 4 * q, *reinterpret_cast<const rn_f4*>(dwl + row * EP + 4 * q), E - 4 * q, vs);
         }
-}
-
-// One output element per group of 64 threads (4 per workgroup): thread c adds the partials c, c + 64, .. of the element in fp64, then the 64
-// sums are added in lane order by one thread -- a fixed tree.  Element e belongs to matrix e / (D E).
-__global__ void __launch_bounds__(256)
-k_ai_dw_reduce(const float* __restrict__ part, float* __restrict__ dWq, float* __restrict__ dWk, float* __restrict__ dWv, float* __restrict__ dWr,
-               int DE, int nW, int G) {
-    __shared__ double red[256];
-    const int n = nW * DE;
-    const int c = threadIdx.x & 63, sub = threadIdx.x >> 6;
-    for (int e0 = blockIdx.x * 4; e0 < n; e0 += gridDim.x * 4) {
-        const int e = e0 + sub;
-        double acc = 0.0;
-        if (e < n)
-            for (int g = c; g < G; g += 64) acc += (double)part[(int64_t)g * n + e];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        if (c == 0 && e < n) {
-            double tot = 0.0;
-            for (int g = 0; g < 64; ++g) tot += red[sub * 64 + g];
-            const int m = e / DE;
-            float* o = m == 0 ? dWq : m == 1 ? dWk : m == 2 ? dWv : dWr;
-            o[e - m * DE] = (float)tot;
-        }
-        __syncthreads();
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -402,14 +349,7 @@ static void ai_cfg(int F, int D, int E, int nW, int bwd, int* waves, int* wres, 
         }
     }
 }
-static int ai_groups(int64_t B, int nW, int D, int E) {
-    int64_t g = (B + AI_DW_ROWS - 1) / AI_DW_ROWS;
-    const int64_t cap = (int64_t)AI_PART_BYTES / (4ll * nW * D * E);
-    if (g > cap) g = cap;
-    if (g > AI_MAXG) g = AI_MAXG;
-    if (g < 1) g = 1;
-    return (int)g;
-}
+static int ai_groups(int64_t B, int nW, int D, int E) { return rn_part_groups(B, AI_DW_ROWS, AI_MAXG, (int64_t)nW * D * E); }
 static AiDesc ai_desc(int F, int64_t B, int D, int H, int d, const float* Wq, const float* Wk, const float* Wv, const float* Wr, int scaling,
                       int relu, int bwd, int64_t xs, int64_t dxs, int* waves, size_t* lds, int* grid) {
     AiDesc c;
@@ -429,19 +369,6 @@ static AiDesc ai_desc(int F, int64_t B, int D, int H, int d, const float* Wq, co
     *grid = (int)((B + rows - 1) / rows);                   // <= G, every workgroup has a sample
     return c;
 }
-// more than 64 KiB of dynamic LDS has to be asked for, once per device
-static int ai_big_lds() {
-    static bool done[64];
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        RN_HIP(hipFuncSetAttribute((const void*)k_ai_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, AI_LDS_BYTES));
-        RN_HIP(hipFuncSetAttribute((const void*)k_ai_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, AI_LDS_BYTES));
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return 0;
-}
-
 extern "C" int recnow_autoint_supported(int F, int D, int H, int d) { return ai_shape_ok(F, D, H, d) ? 1 : 0; }
 
 extern "C" int recnow_autoint_route(int F, int D, int H, int d, int use_res, int bwd) {
@@ -467,7 +394,7 @@ extern "C" int recnow_autoint_fwd(const float* const* fields, int64_t xstride, i
     int waves, grid;
     size_t lds;
     const AiDesc c = ai_desc(F, B, D, H, d, Wq, Wk, Wv, Wr, scaling, relu, 0, xstride, 0, &waves, &lds, &grid);
-    if (lds > 64 * 1024) RN_HIP((hipError_t)ai_big_lds());
+    if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_ai_fwd, AI_LDS_BYTES));       // resident weights beside up to four waves' tiles
     hipLaunchKernelGGL(k_ai_fwd, grid, waves * 64, lds, (hipStream_t)stream, fields, out, c);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
@@ -490,14 +417,12 @@ extern "C" int recnow_autoint_bwd(const float* const* fields, int64_t xstride, f
     int waves, grid;
     size_t lds;
     const AiDesc c = ai_desc(F, B, D, H, d, Wq, Wk, Wv, Wr, scaling, relu, 1, xstride, dxstride, &waves, &lds, &grid);
-    if (lds > 64 * 1024) RN_HIP((hipError_t)ai_big_lds());
+    if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_ai_bwd, AI_LDS_BYTES));       // the same, and the weight-gradient accumulators
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_ai_bwd, grid, waves * 64, lds, st, fields, dfields, dout, part, c);
     RN_LAUNCH_CHECK();
-    if (part) {
-        const int n = c.nW * D * c.E;
-        hipLaunchKernelGGL(k_ai_dw_reduce, (n + 3) / 4, 256, 0, st, part, dWq, dWk, dWv, dWr, D * c.E, c.nW, grid);
-        RN_LAUNCH_CHECK();
-    }
-    return RECNOW_OK;
+    if (!part) return RECNOW_OK;
+    const int64_t DE = (int64_t)D * c.E;
+    const RnPartDst dst = {{dWq, dWk, dWv, dWr}, {DE, 2 * DE, 3 * DE, c.nW * DE}};
+    return rn_part_reduce(part, c.nW * DE, 1, grid, c.nW * DE, 0, dst, st);
 }

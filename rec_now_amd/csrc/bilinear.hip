@@ -17,9 +17,10 @@
 // Backward workspace (recnow_bilinear_workspace_bytes; the carve order of recnow_bilinear_bwd):
 //   [dU]    'all' / 'each' only:  B * (F-1) * D floats -- dU_i[b] = sum_j g_ij[b] * x_j[b], read back by the weight-gradient pass
 //   [part]  G * S * D * D floats  -- per row-chunk partial sums of the weight gradient, S = F-1 ('all', 'each') or P ('interaction'),
-//           G = min(ceil(B / BIL_DW_ROWS), BIL_DW_MAXG, max(1, BIL_DW_PART_BYTES / (4 S D^2)))
+//           G = rn_part_groups(B, BIL_DW_ROWS, BIL_DW_MAXG, S D^2) = max(1, min(ceil(B / BIL_DW_ROWS), BIL_DW_MAXG, RN_PART_BYTES / (4 S D^2)))
 //   each carve rounded up to 256 bytes.  Nothing grows as B * P * D^2.
 #include "common.hpp"
+#include "partials.hpp"
 
 #define BIL_ALL 0
 #define BIL_EACH 1
@@ -39,34 +40,7 @@
 #define BIL_TILE_GRID 2048
 #define BIL_DW_ROWS 256                         // rows of one weight-gradient partial at the least
 #define BIL_DW_MAXG 256
-#define BIL_DW_PART_BYTES (32u << 20)
 
-#define BIL_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")       // LDS hand-over inside ONE wave
-
-__device__ __forceinline__ bool bil_vec(const void* p, int D) { return (D & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// up to four floats from p; n = valid floats at p (anything <= 0: none)
-__device__ __forceinline__ rn_f4 bil_ld4(const float* p, int n, bool vec) {
-    if (vec) return *reinterpret_cast<rn_gcf4>((rn_gcf)p);
-    rn_f4 v = {0.f, 0.f, 0.f, 0.f};
-    rn_gcf g = (rn_gcf)p;
-    if (n > 0) v.x = g[0];
-    if (n > 1) v.y = g[1];
-    if (n > 2) v.z = g[2];
-    if (n > 3) v.w = g[3];
-    return v;
-}
-__device__ __forceinline__ void bil_st4(float* p, rn_f4 v, int n, bool vec) {
-    if (vec) { *reinterpret_cast<rn_gf4>((rn_gf)p) = v; return; }
-    rn_gf g = (rn_gf)p;
-    if (n > 0) g[0] = v.x;
-    if (n > 1) g[1] = v.y;
-    if (n > 2) g[2] = v.z;
-    if (n > 3) g[3] = v.w;
-}
-__device__ __forceinline__ void bil_st4_stream(float* p, rn_f4 v, int n, bool vec) {
-    if (vec) { RN_ST_STREAM(reinterpret_cast<rn_gf4>((rn_gf)p), v); return; }
-    bil_st4(p, v, n, false);
-}
 // e / Qp for e * Qp < 2^32 (magic = 2^32 / Qp + 1; Qp == 1 has no 32-bit magic)
 __device__ __forceinline__ int bil_div(int e, int Qp, unsigned magic) { return Qp == 1 ? e : (int)__umulhi((unsigned)e, magic); }
 __device__ __forceinline__ int bil_pair(int i, int j, int F) { return i * F - i * (i + 1) / 2 + (j - i - 1); }
@@ -91,10 +65,10 @@ struct BilRow {
 __device__ __forceinline__ void bil_row_prologue(const BilRow& c, const float* W, float* wl, unsigned short* pt) {
     if (c.wres) {
         const int nW = c.type == BIL_ALL ? 1 : c.F - 1;
-        const bool vw = bil_vec(W, c.D);
+        const bool vw = rn_vec4_ok(W, c.D);
         for (int e = threadIdx.x; e < nW * c.D * c.Qp; e += blockDim.x) {
             const int row = e / c.Qp, q = e - row * c.Qp;
-            *reinterpret_cast<rn_f4*>(wl + row * c.DP + 4 * q) = bil_ld4(W + (int64_t)row * c.D + 4 * q, c.D - 4 * q, vw);
+            *reinterpret_cast<rn_f4*>(wl + row * c.DP + 4 * q) = rn_ld4(W + (int64_t)row * c.D + 4 * q, c.D - 4 * q, vw);
         }
     }
     bil_fill_pairs(pt, c.F, c.P);
@@ -106,10 +80,10 @@ __device__ __forceinline__ void bil_row_xu(const BilRow& c, const float* const* 
     for (int e = lane; e < c.F * c.Qp; e += 64) {
         const int f = bil_div(e, c.Qp, c.magic), q = e - f * c.Qp;
         const float* xf = fields[f];
-        *reinterpret_cast<rn_f4*>(xs + f * c.DP + 4 * q) = bil_ld4(xf + b * c.D + 4 * q, c.D - 4 * q, bil_vec(xf, c.D));
+        *reinterpret_cast<rn_f4*>(xs + f * c.DP + 4 * q) = rn_ld4(xf + b * c.D + 4 * q, c.D - 4 * q, rn_vec4_ok(xf, c.D));
     }
-    BIL_WAVE_SYNC();
-    const bool vw = bil_vec(W, c.D);
+    RN_LDS_WAVE_SYNC();
+    const bool vw = rn_vec4_ok(W, c.D);
     for (int e = lane; e < (c.F - 1) * c.Qp; e += 64) {
         const int i = bil_div(e, c.Qp, c.magic), q = e - i * c.Qp;
         const int wi = c.type == BIL_ALL ? 0 : i;
@@ -119,11 +93,11 @@ __device__ __forceinline__ void bil_row_xu(const BilRow& c, const float* const* 
             for (int k = 0; k < c.D; ++k) acc += xs[i * c.DP + k] * *reinterpret_cast<const rn_f4*>(wr + k * c.DP);
         } else {
             const float* wr = W + (int64_t)wi * c.D * c.D + 4 * q;
-            for (int k = 0; k < c.D; ++k) acc += xs[i * c.DP + k] * bil_ld4(wr + k * c.D, c.D - 4 * q, vw);
+            for (int k = 0; k < c.D; ++k) acc += xs[i * c.DP + k] * rn_ld4(wr + k * c.D, c.D - 4 * q, vw);
         }
         *reinterpret_cast<rn_f4*>(us + i * c.DP + 4 * q) = acc;
     }
-    BIL_WAVE_SYNC();
+    RN_LDS_WAVE_SYNC();
 }
 
 __global__ void __launch_bounds__(256)
@@ -136,7 +110,7 @@ k_bil_row_fwd(const float* const* __restrict__ fields, const float* __restrict__
     float* xs = wl + nWl * c.D * c.DP + c.ptf + w * 2 * c.F * c.DP;
     float* us = xs + c.F * c.DP;
     bil_row_prologue(c, W, wl, pt);
-    const bool vo = bil_vec(out, c.D);
+    const bool vo = rn_vec4_ok(out, c.D);
     const int E = c.P * c.Qp;
     for (int64_t b = (int64_t)blockIdx.x * nw + w; b < c.B; b += (int64_t)gridDim.x * nw) {
         bil_row_xu(c, fields, W, wl, xs, us, b, lane);
@@ -145,9 +119,9 @@ k_bil_row_fwd(const float* const* __restrict__ fields, const float* __restrict__
             const int p = bil_div(e, c.Qp, c.magic), q = e - p * c.Qp;
             const int ij = pt[p], i = ij & 255, j = ij >> 8;
             const rn_f4 o = *reinterpret_cast<const rn_f4*>(us + i * c.DP + 4 * q) * *reinterpret_cast<const rn_f4*>(xs + j * c.DP + 4 * q);
-            bil_st4_stream(ob + p * c.D + 4 * q, o, c.D - 4 * q, vo);
+            rn_st4_stream(ob + p * c.D + 4 * q, o, c.D - 4 * q, vo);
         }
-        BIL_WAVE_SYNC();                                    // tiles read before the next sample overwrites them
+        RN_LDS_WAVE_SYNC();                                    // tiles read before the next sample overwrites them
     }
 }
 
@@ -166,7 +140,7 @@ k_bil_row_bwd(const float* const* __restrict__ fields, float* const* __restrict_
     float* us = xs + c.F * c.DP;
     float* dus = us + c.F * c.DP;
     bil_row_prologue(c, W, wl, pt);
-    const bool vg = bil_vec(dout, c.D), vw = bil_vec(W, c.D), vu = bil_vec(du_ws, c.D);
+    const bool vg = rn_vec4_ok(dout, c.D), vw = rn_vec4_ok(W, c.D), vu = rn_vec4_ok(du_ws, c.D);
     const int F = c.F, D = c.D, DP = c.DP;
     for (int64_t b = (int64_t)blockIdx.x * nw + w; b < c.B; b += (int64_t)gridDim.x * nw) {
         bil_row_xu(c, fields, W, wl, xs, us, b, lane);
@@ -176,17 +150,17 @@ k_bil_row_bwd(const float* const* __restrict__ fields, float* const* __restrict_
             rn_f4 acc = {0.f, 0.f, 0.f, 0.f};
             const float* gr = gb + (int64_t)bil_pair(f, f + 1, F) * D + 4 * q;      // the run of pairs (f, f+1 ..): only read for f < F-1
 #pragma unroll 4
-            for (int j = f + 1; j < F; ++j) acc += bil_ld4(gr + (j - f - 1) * D, D - 4 * q, vg) * *reinterpret_cast<const rn_f4*>(xs + j * DP + 4 * q);
+            for (int j = f + 1; j < F; ++j) acc += rn_ld4(gr + (j - f - 1) * D, D - 4 * q, vg) * *reinterpret_cast<const rn_f4*>(xs + j * DP + 4 * q);
             *reinterpret_cast<rn_f4*>(dus + f * DP + 4 * q) = acc;
-            if (du_ws && f < F - 1) bil_st4(du_ws + (b * (F - 1) + f) * D + 4 * q, acc, D - 4 * q, vu);
+            if (du_ws && f < F - 1) rn_st4(du_ws + (b * (F - 1) + f) * D + 4 * q, acc, D - 4 * q, vu);
         }
-        BIL_WAVE_SYNC();
+        RN_LDS_WAVE_SYNC();
         for (int e = lane; e < F * c.Qp; e += 64) {
             const int f = bil_div(e, c.Qp, c.magic), q = e - f * c.Qp;
             rn_f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
             for (int i = 0; i < f; ++i)
-                acc += bil_ld4(gb + (int64_t)bil_pair(i, f, F) * D + 4 * q, D - 4 * q, vg) * *reinterpret_cast<const rn_f4*>(us + i * DP + 4 * q);
+                acc += rn_ld4(gb + (int64_t)bil_pair(i, f, F) * D + 4 * q, D - 4 * q, vg) * *reinterpret_cast<const rn_f4*>(us + i * DP + 4 * q);
             if (f < F - 1) {
                 const int wi = c.type == BIL_ALL ? 0 : f;
                 float r[4] = {0.f, 0.f, 0.f, 0.f};
@@ -200,7 +174,7 @@ k_bil_row_bwd(const float* const* __restrict__ fields, float* const* __restrict_
                             for (int d = 0; d < DP; d += 4) s += *reinterpret_cast<const rn_f4*>(dus + f * DP + d) * *reinterpret_cast<const rn_f4*>(wr + d);
                         } else {
                             const float* wr = W + ((int64_t)wi * D + k) * D;
-                            for (int d = 0; d < DP; d += 4) s += *reinterpret_cast<const rn_f4*>(dus + f * DP + d) * bil_ld4(wr + d, D - d, vw);
+                            for (int d = 0; d < DP; d += 4) s += *reinterpret_cast<const rn_f4*>(dus + f * DP + d) * rn_ld4(wr + d, D - d, vw);
                         }
                         r[t] = (s.x + s.y) + (s.z + s.w);
                     }
@@ -208,9 +182,9 @@ k_bil_row_bwd(const float* const* __restrict__ fields, float* const* __restrict_
                 acc += rn_f4{r[0], r[1], r[2], r[3]};
             }
             float* df = dfields[f];
-            bil_st4(df + b * D + 4 * q, acc, D - 4 * q, bil_vec(df, D));
+            rn_st4(df + b * D + 4 * q, acc, D - 4 * q, rn_vec4_ok(df, D));
         }
-        BIL_WAVE_SYNC();
+        RN_LDS_WAVE_SYNC();
     }
 }
 
@@ -224,10 +198,10 @@ struct BilTile {
 };
 // the PBc weight matrices from pair p0 on -> wt[pp][k][ws], ws >= DP the row stride
 __device__ __forceinline__ void bil_stage_w(const BilTile& c, const float* W, float* wt, int p0, int PBc, int ws) {
-    const bool vw = bil_vec(W, c.D);
+    const bool vw = rn_vec4_ok(W, c.D);
     for (int e = threadIdx.x; e < PBc * c.D * c.Qp; e += blockDim.x) {
         const int row = e / c.Qp, q = e - row * c.Qp;
-        *reinterpret_cast<rn_f4*>(wt + row * ws + 4 * q) = bil_ld4(W + ((int64_t)p0 * c.D + row) * c.D + 4 * q, c.D - 4 * q, vw);
+        *reinterpret_cast<rn_f4*>(wt + row * ws + 4 * q) = rn_ld4(W + ((int64_t)p0 * c.D + row) * c.D + 4 * q, c.D - 4 * q, vw);
     }
 }
 
@@ -242,7 +216,7 @@ k_bil_tile_fwd(const float* const* __restrict__ fields, const float* __restrict_
     bil_fill_pairs(pt, c.F, c.P);
     const int F = c.F, D = c.D, DP = c.DP, Qp = c.Qp;
     const int LPR = 1 << c.lpr_shift, rr = threadIdx.x >> c.lpr_shift, cc = threadIdx.x & (LPR - 1), rstep = 256 >> c.lpr_shift;
-    const bool vo = bil_vec(out, D);
+    const bool vo = rn_vec4_ok(out, D);
     const int64_t ntiles = (c.B + c.R - 1) / c.R;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t b0 = tile * c.R;
@@ -250,10 +224,10 @@ k_bil_tile_fwd(const float* const* __restrict__ fields, const float* __restrict_
         __syncthreads();                                    // the previous tile is consumed
         for (int f = 0; f < F; ++f) {                       // the field's rows x D block is contiguous in its tensor
             const float* xf = fields[f];
-            const bool vx = bil_vec(xf, D);
+            const bool vx = rn_vec4_ok(xf, D);
             for (int e = threadIdx.x; e < rows * Qp; e += 256) {
                 const int r = bil_div(e, Qp, c.magic), q = e - r * Qp;
-                *reinterpret_cast<rn_f4*>(xt + (r * F + f) * DP + 4 * q) = bil_ld4(xf + (b0 + r) * D + 4 * q, D - 4 * q, vx);
+                *reinterpret_cast<rn_f4*>(xt + (r * F + f) * DP + 4 * q) = rn_ld4(xf + (b0 + r) * D + 4 * q, D - 4 * q, vx);
             }
         }
         for (int p0 = 0; p0 < c.P; p0 += c.PB) {
@@ -288,7 +262,7 @@ k_bil_tile_fwd(const float* const* __restrict__ fields, const float* __restrict_
                     for (int t = 0; t < 4; ++t) {
                         if (r + t * rstep < rows) {
                             const rn_f4 o = acc[t] * *reinterpret_cast<const rn_f4*>(xt + (rk[t] * F + j) * DP + 4 * q);
-                            bil_st4_stream(out + ((b0 + rk[t]) * c.P + (p0 + pp)) * D + 4 * q, o, D - 4 * q, vo);
+                            rn_st4_stream(out + ((b0 + rk[t]) * c.P + (p0 + pp)) * D + 4 * q, o, D - 4 * q, vo);
                         }
                     }
                 }
@@ -314,7 +288,7 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
     float* xi = wt + c.PB * D * XS;
     float* ht = xi + c.R * XS;
     const int LPR = 1 << c.lpr_shift, r = threadIdx.x >> c.lpr_shift, q = threadIdx.x & (LPR - 1);
-    const bool vg = bil_vec(dout, D);
+    const bool vg = rn_vec4_ok(dout, D);
     int kt[4];                                              // the rows of W[p] this thread contracts h with, clamped into the matrix
 #pragma unroll
     for (int t = 0; t < 4; ++t) kt[t] = min(4 * q + t, D - 1);
@@ -345,8 +319,8 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
                         if (++j2 >= F) { ++i2; j2 = i2 + 1; }
                         if (active) {
                             const float* xf = fields[j2];
-                            xq[pp] = bil_ld4(xf + b * D + 4 * q, D - 4 * q, bil_vec(xf, D));
-                            gq[pp] = bil_ld4(gb + (int64_t)(p0 + pp) * D, D - 4 * q, vg);
+                            xq[pp] = rn_ld4(xf + b * D + 4 * q, D - 4 * q, rn_vec4_ok(xf, D));
+                            gq[pp] = rn_ld4(gb + (int64_t)(p0 + pp) * D, D - 4 * q, vg);
                         }
                     }
                 }
@@ -361,12 +335,12 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
                     if (active && icur >= 0) *reinterpret_cast<rn_f4*>(dxr + icur * DP) += dxi;
                     dxi = rn_f4{0.f, 0.f, 0.f, 0.f};
                     icur = i;
-                    BIL_WAVE_SYNC();                        // the row's lanes have read the previous x_i
+                    RN_LDS_WAVE_SYNC();                        // the row's lanes have read the previous x_i
                     if (active) {
                         const float* xf = fields[i];
-                        *reinterpret_cast<rn_f4*>(xi + r * XS + 4 * q) = bil_ld4(xf + b * D + 4 * q, D - 4 * q, bil_vec(xf, D));
+                        *reinterpret_cast<rn_f4*>(xi + r * XS + 4 * q) = rn_ld4(xf + b * D + 4 * q, D - 4 * q, rn_vec4_ok(xf, D));
                     }
-                    BIL_WAVE_SYNC();
+                    RN_LDS_WAVE_SYNC();
                 }
                 const float* wr = wt + pp * D * XS;
                 if (active) {
@@ -380,7 +354,7 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
                     *reinterpret_cast<rn_f4*>(dxr + j * DP) += g * u;
                     *reinterpret_cast<rn_f4*>(ht + r * XS + 4 * q) = g * xj;
                 }
-                BIL_WAVE_SYNC();
+                RN_LDS_WAVE_SYNC();
                 if (active) {
                     rn_f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
                     for (int d = 0; d < DP; d += 4) {       // h is zero past D: the padded columns of wt add nothing
@@ -393,7 +367,7 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
                     // components 4q + t >= D repeat row D-1: never stored
                     dxi += rn_f4{(s0.x + s0.y) + (s0.z + s0.w), (s1.x + s1.y) + (s1.z + s1.w), (s2.x + s2.y) + (s2.z + s2.w), (s3.x + s3.y) + (s3.z + s3.w)};
                 }
-                BIL_WAVE_SYNC();                            // ht read before the next pair overwrites it
+                RN_LDS_WAVE_SYNC();                            // ht read before the next pair overwrites it
             };
 #define BIL_STEP(PP) if (PP < PBc) step(PP, gq[PP], xq[PP])
             BIL_STEP(0); BIL_STEP(1); BIL_STEP(2); BIL_STEP(3); BIL_STEP(4); BIL_STEP(5);
@@ -405,7 +379,7 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
             if (icur >= 0) *reinterpret_cast<rn_f4*>(dxr + icur * DP) += dxi;
             for (int f = 0; f < F; ++f) {
                 float* df = dfields[f];
-                bil_st4(df + b * D + 4 * q, *reinterpret_cast<const rn_f4*>(dxr + f * DP), D - 4 * q, bil_vec(df, D));
+                rn_st4(df + b * D + 4 * q, *reinterpret_cast<const rn_f4*>(dxr + f * DP), D - 4 * q, rn_vec4_ok(df, D));
             }
         }
     }
@@ -414,8 +388,8 @@ k_bil_tile_bwd(const float* const* __restrict__ fields, float* const* __restrict
 // ---------------------------------------------------------------------------------------------------------------------
 // Weight gradient: dW[w(s)][k][d] = sum_b x_{i(s)}[b][k] * h_s[b][d] over the slots s; h_s = dU_s from the workspace ('all', 'each',
 // slot = field i) or g_s * x_{j(s)} formed on the fly ('interaction', slot = pair).  Workgroup (slot chunk, row chunk); a thread owns the
-// 4 x 4 block (k quad, d quad) of one slot and sums its row chunk in row order in fp32; k_bil_dw_reduce adds the row chunks (and for
-// 'all' the slots) in fp64 in a fixed order.
+// 4 x 4 block (k quad, d quad) of one slot and sums its row chunk in row order in fp32; rn_part_reduce (partials.hpp) adds the row chunks (and
+// for 'all' the slots, slot-major) in fp64 in a fixed tree.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_bil_dw_partial(const float* const* __restrict__ fields, const float* __restrict__ dout, const float* __restrict__ du_ws,
@@ -432,15 +406,15 @@ k_bil_dw_partial(const float* const* __restrict__ fields, const float* __restric
     }
     const float* xi = fields[i];
     const float* xj = fields[j];
-    const bool vi = bil_vec(xi, D), vj = bil_vec(xj, D), vg = bil_vec(dout, D), vu = bil_vec(du_ws, D);
+    const bool vi = rn_vec4_ok(xi, D), vj = rn_vec4_ok(xj, D), vg = rn_vec4_ok(dout, D), vu = rn_vec4_ok(du_ws, D);
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_g, r1 = min(B, r0 + rows_per_g);
     rn_f4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
 #pragma unroll 2
     for (int64_t b = r0; b < r1; ++b) {
-        const rn_f4 x = bil_ld4(xi + b * D + 4 * kq, D - 4 * kq, vi);
+        const rn_f4 x = rn_ld4(xi + b * D + 4 * kq, D - 4 * kq, vi);
         rn_f4 h;
-        if (type == BIL_INTER) h = bil_ld4(dout + (b * P + s) * D + 4 * q, D - 4 * q, vg) * bil_ld4(xj + b * D + 4 * q, D - 4 * q, vj);
-        else h = bil_ld4(du_ws + (b * (F - 1) + s) * D + 4 * q, D - 4 * q, vu);
+        if (type == BIL_INTER) h = rn_ld4(dout + (b * P + s) * D + 4 * q, D - 4 * q, vg) * rn_ld4(xj + b * D + 4 * q, D - 4 * q, vj);
+        else h = rn_ld4(du_ws + (b * (F - 1) + s) * D + 4 * q, D - 4 * q, vu);
         a0 += x.x * h; a1 += x.y * h; a2 += x.z * h; a3 += x.w * h;
     }
     float* o = part + ((int64_t)blockIdx.y * S + s) * D * D;
@@ -448,38 +422,9 @@ k_bil_dw_partial(const float* const* __restrict__ fields, const float* __restric
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int k = 4 * kq + t;
-        if (k < D) bil_st4(o + k * D + 4 * q, acc[t], D - 4 * q, bil_vec(part, D));
+        if (k < D) rn_st4(o + k * D + 4 * q, acc[t], D - 4 * q, rn_vec4_ok(part, D));
     }
 }
-// One output element per group of 64 threads (4 per workgroup): thread c adds the terms c, c + 64, .. of the element's fixed term list
-// (row chunks, and for 'all' the slots, slot-major) in fp64, then the 64 sums are added in lane order by one thread -- a fixed tree.
-__global__ void __launch_bounds__(256)
-k_bil_dw_reduce(const float* __restrict__ part, float* __restrict__ dW, int D, int S, int G, int sum_slots) {
-    __shared__ double red[256];
-    const int DD = D * D;
-    const int64_t n = (int64_t)(sum_slots ? 1 : S) * DD;
-    const int c = threadIdx.x & 63, sub = threadIdx.x >> 6;
-    const int nterm = sum_slots ? S * G : G;
-    for (int64_t e0 = (int64_t)blockIdx.x * 4; e0 < n; e0 += (int64_t)gridDim.x * 4) {
-        const int64_t e = e0 + sub;
-        double acc = 0.0;
-        if (e < n)
-            for (int t = c; t < nterm; t += 64) {
-                // term t: 'all' -> (slot t / G, chunk t % G) of element e; else chunk t of element e (its slot is part of e)
-                const int64_t at = sum_slots ? ((int64_t)(t % G) * S + t / G) * DD + e : (int64_t)t * S * DD + e;
-                acc += (double)part[at];
-            }
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        if (c == 0 && e < n) {
-            double tot = 0.0;
-            for (int t = 0; t < 64; ++t) tot += red[sub * 64 + t];
-            dW[e] = (float)tot;
-        }
-        __syncthreads();
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -543,12 +488,7 @@ static BilTile bil_tile_desc(int F, int D, int64_t B, bool bwd, size_t* lds, int
 // slots and row chunks of the weight-gradient partials
 static void bil_dw_cfg(int64_t B, int F, int D, int type, int* S, int* G) {
     *S = type == BIL_INTER ? F * (F - 1) / 2 : F - 1;
-    int64_t g = (B + BIL_DW_ROWS - 1) / BIL_DW_ROWS;
-    const int64_t cap = (int64_t)BIL_DW_PART_BYTES / (4ll * *S * D * D);
-    if (g > cap) g = cap;
-    if (g > BIL_DW_MAXG) g = BIL_DW_MAXG;
-    if (g < 1) g = 1;
-    *G = (int)g;
+    *G = rn_part_groups(B, BIL_DW_ROWS, BIL_DW_MAXG, (int64_t)*S * D * D);
 }
 
 extern "C" int recnow_bilinear_supported(int F, int D, int type) { return bil_shape_ok(F, D, type) ? 1 : 0; }
@@ -640,11 +580,10 @@ extern "C" int recnow_bilinear_bwd(const float* const* fields, float* const* dfi
         hipLaunchKernelGGL(k_bil_dw_partial, dim3((S + SB - 1) / SB, G), 256, 0, st, fields, dout, du, part, F, D, Qp, F * (F - 1) / 2, type, S, SB,
                            B, rows_per_g);
         RN_LAUNCH_CHECK();
-        const int64_t n = (int64_t)(type == BIL_ALL ? 1 : S) * D * D;
-        int64_t g = (n + 3) / 4;
-        if (g > 16384) g = 16384;
-        hipLaunchKernelGGL(k_bil_dw_reduce, (int)g, 256, 0, st, part, dW, D, S, G, type == BIL_ALL ? 1 : 0);
-        RN_LAUNCH_CHECK();
+        // 'all': the S slots of a chunk are terms of one matrix, slot-major; else the slot is part of the element index
+        const int64_t DD = (int64_t)D * D, n = type == BIL_ALL ? DD : S * DD;
+        const RnPartDst dst = {{dW, nullptr, nullptr, nullptr}, {n, n, n, n}};
+        return rn_part_reduce(part, n, type == BIL_ALL ? S : 1, G, S * DD, DD, dst, st);
     }
     return RECNOW_OK;
 }

@@ -256,16 +256,8 @@ int rn_cin_bwd_fused(const float* dXk, const float* W, const float* x0t, const f
     k.dXk = dXk; k.W = W; k.x0t = x0t; k.Xp = Xp; k.dXp = dXp; k.dx0t = dx0t; k.Hk = Hk; k.F = F;
     const size_t lds = cb_lds_bytes(F);
     const int grid = (int)(M / CB_BM);
-    // more than 64 KB of dynamic LDS: raised once per device and kernel (the attribute belongs to the function on that device)
-    static bool raised[2][64];
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    const int which = Hp == 128 ? 0 : 1;
-    if (dev < 0 || dev >= 64 || !raised[which][dev]) {
-        if (Hp == 128) RN_HIP(hipFuncSetAttribute((const void*)k_cin_bwd_fused<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        else RN_HIP(hipFuncSetAttribute((const void*)k_cin_bwd_fused<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (dev >= 0 && dev < 64) raised[which][dev] = true;
-    }
+    // two stages of both operands beside the 2 F row accumulators: more than 64 KB of dynamic LDS
+    RN_HIP(rn_lds_grant(Hp == 128 ? (const void*)k_cin_bwd_fused<128> : (const void*)k_cin_bwd_fused<64>, 160 * 1024));
     if (Hp == 128) hipLaunchKernelGGL((k_cin_bwd_fused<128>), grid, CB_THREADS, lds, st, k);
     else hipLaunchKernelGGL((k_cin_bwd_fused<64>), grid, CB_THREADS, lds, st, k);
     RN_LAUNCH_CHECK();

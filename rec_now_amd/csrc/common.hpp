@@ -73,6 +73,16 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
     return r;
 }
 
+// Hand-over of a wave-PRIVATE LDS tile: orders one wave's LDS writes against its own later LDS reads (and reads against later overwrites).
+// DS instructions of a wave execute in issue order, so only the compiler has to be stopped from moving them; waiting on lgkmcnt alone (not
+// a fence, which also drains vmcnt) keeps global stores asynchronous.
+#define RN_LDS_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+
+// More than 64 KiB of dynamic LDS has to be granted to a kernel on every device it runs on (lds_grant.hip).  hipSuccess when a workgroup of
+// `kernel` may own `bytes` on the current device, else the runtime's error with the sticky error cleared; nothing is asked for bytes <= 64 KiB
+// or for what was granted or refused before.  Not a stream operation: call it ahead of the launch, stream captures do not see it.
+hipError_t rn_lds_grant(const void* kernel, size_t bytes);
+
 // ---- activations (enum recnow_act) -------------------------------------------------------------
 __device__ __forceinline__ float rn_sigmoid(float x) {
     // stable logistic
@@ -139,3 +149,33 @@ typedef rn_f4 __attribute__((address_space(1)))* rn_gf4;
 #define RN_ST_STREAM(p, v) (*(p) = (v))
 #endif
 
+// ---- the guarded 4-float global access of the per-sample layer kernels ------------------------------
+// One 16-byte access when the tensor allows it (rn_vec4_ok: width and row stride multiples of 4 floats, base 16-byte aligned; decided per
+// tensor, in the kernel, because field pointers are device-resident), else up to four guarded 4-byte accesses.
+__device__ __forceinline__ bool rn_vec4_ok(const void* p, int width, int64_t stride = 0) {
+    return (width & 3) == 0 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+// up to four floats from p; n = valid floats at p (anything <= 0: none)
+__device__ __forceinline__ rn_f4 rn_ld4(const float* p, int n, bool vec) {
+    if (vec) return *reinterpret_cast<rn_gcf4>((rn_gcf)p);
+    rn_f4 v = {0.f, 0.f, 0.f, 0.f};
+    rn_gcf g = (rn_gcf)p;
+    if (n > 0) v.x = g[0];
+    if (n > 1) v.y = g[1];
+    if (n > 2) v.z = g[2];
+    if (n > 3) v.w = g[3];
+    return v;
+}
+__device__ __forceinline__ void rn_st4(float* p, rn_f4 v, int n, bool vec) {
+    if (vec) { *reinterpret_cast<rn_gf4>((rn_gf)p) = v; return; }
+    rn_gf g = (rn_gf)p;
+    if (n > 0) g[0] = v.x;
+    if (n > 1) g[1] = v.y;
+    if (n > 2) g[2] = v.z;
+    if (n > 3) g[3] = v.w;
+}
+__device__ __forceinline__ void rn_st4_stream(float* p, rn_f4 v, int n, bool vec) {
+    if (vec) { RN_ST_STREAM(reinterpret_cast<rn_gf4>((rn_gf)p), v); return; }
+    rn_st4(p, v, n, false);
+}
+__device__ __forceinline__ float rn_dot4(rn_f4 a, rn_f4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }

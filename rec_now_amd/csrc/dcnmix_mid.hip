@@ -723,12 +723,6 @@ __global__ void __launch_bounds__(1024) k_mix_dv_reduce(const float* __restrict_
     }
 }
 
-template <typename K>
-static int mid_allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024) RN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return RECNOW_OK;
-}
-
 bool rn_mix_mid_absorbs_slabs(int64_t B, int S, int N, int LDT) {
     return B % MID_ROWS == 0 && ((S == 64 && N == 2) || (S == 32 && N == 4)) && LDT == S * N + 16;
 }
@@ -746,13 +740,13 @@ int rn_mix_mid_fwd(const float* T1, const float* V, float* T2, float* T2g, int64
 #define MID_FWD_FAST(SS, NN)                                                                                                  \
     if (B % MID_ROWS == 0 && S == SS && N == NN && LDT == SS * NN + 16) {                                         \
         if (slabs && sl.n == 4) {                                                                                             \
-            if ((rc = mid_allow_lds(k_mix_mid_fwd_fast<SS, NN, 4>, lds))) return rc;                                          \
+            if ((rc = rn_lds_grant((const void*)k_mix_mid_fwd_fast<SS, NN, 4>, lds))) return rc;                                          \
             hipLaunchKernelGGL((k_mix_mid_fwd_fast<SS, NN, 4>), mid_fwd_grid(B, lds), 256, lds, st, T1, V, T2, T2g, B, LDT, act_outer, sl, act_inner); \
         } else if (slabs) {                                                                                                   \
-            if ((rc = mid_allow_lds(k_mix_mid_fwd_fast<SS, NN, 2>, lds))) return rc;                                          \
+            if ((rc = rn_lds_grant((const void*)k_mix_mid_fwd_fast<SS, NN, 2>, lds))) return rc;                                          \
             hipLaunchKernelGGL((k_mix_mid_fwd_fast<SS, NN, 2>), mid_fwd_grid(B, lds), 256, lds, st, T1, V, T2, T2g, B, LDT, act_outer, sl, act_inner); \
         } else {                                                                                                              \
-            if ((rc = mid_allow_lds(k_mix_mid_fwd_fast<SS, NN, 0>, lds))) return rc;                                          \
+            if ((rc = rn_lds_grant((const void*)k_mix_mid_fwd_fast<SS, NN, 0>, lds))) return rc;                                          \
             hipLaunchKernelGGL((k_mix_mid_fwd_fast<SS, NN, 0>), mid_fwd_grid(B, lds), 256, lds, st, T1, V, T2, T2g, B, LDT, act_outer, sl, act_inner); \
         }                                                                                                                     \
         rn_prof_end(pr, st);                                                                                                  \
@@ -763,10 +757,10 @@ int rn_mix_mid_fwd(const float* T1, const float* V, float* T2, float* T2g, int64
     MID_FWD_FAST(32, 4)
 #undef MID_FWD_FAST
     if (S == 32) {
-        if ((rc = mid_allow_lds(k_mix_mid_fwd<32>, lds))) return rc;
+        if ((rc = rn_lds_grant((const void*)k_mix_mid_fwd<32>, lds))) return rc;
         hipLaunchKernelGGL(k_mix_mid_fwd<32>, mid_fwd_grid(B, lds), 256, lds, st, T1, V, T2, T2g, B, N, LDT, act_outer);
     } else {
-        if ((rc = mid_allow_lds(k_mix_mid_fwd<64>, lds))) return rc;
+        if ((rc = rn_lds_grant((const void*)k_mix_mid_fwd<64>, lds))) return rc;
         hipLaunchKernelGGL(k_mix_mid_fwd<64>, mid_fwd_grid(B, lds), 256, lds, st, T1, V, T2, T2g, B, N, LDT, act_outer);
     }
     rn_prof_end(pr, st);
@@ -792,24 +786,24 @@ int rn_mix_mid_bwd(const float* dT2g, const float* T2, const float* T1, const fl
     RnProfRecord* pr = rn_prof_on() ? rn_prof_begin(RN_TAG_MIX_MID_BWD, 8.0 * B * N * S * S, 16.0 * B * LDT, st) : nullptr;
 #define MID_BWD(SS, VV)                                                                                                       \
     do {                                                                                                                      \
-        if ((rc = mid_allow_lds(k_mix_mid_bwd<SS, VV>, lds))) return rc;                                                      \
+        if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd<SS, VV>, lds))) return rc;                                                      \
         hipLaunchKernelGGL((k_mix_mid_bwd<SS, VV>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, N, LDT, act_inner, act_outer, rscale); \
     } while (0)
     bool done = false;
 #define MID_BWD_FAST(SS, NN)                                                                                                  \
     if (!done && B % MID_ROWS == 0 && S == SS && N == NN && LDT == SS * NN + 16) {                                        \
         const int slv = slabs ? sl.n : 0;                                                                                     \
-        if (rscale && slv == 4) { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, true, 4>, lds))) return rc;               \
+        if (rscale && slv == 4) { if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd_fast<SS, NN, true, 4>, lds))) return rc;               \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, true, 4>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \
-        else if (rscale && slv == 2) { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, true, 2>, lds))) return rc;          \
+        else if (rscale && slv == 2) { if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd_fast<SS, NN, true, 2>, lds))) return rc;          \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, true, 2>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \
-        else if (rscale) { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, true, 0>, lds))) return rc;                      \
+        else if (rscale) { if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd_fast<SS, NN, true, 0>, lds))) return rc;                      \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, true, 0>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \
-        else if (slv == 4) { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, false, 4>, lds))) return rc;                   \
+        else if (slv == 4) { if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd_fast<SS, NN, false, 4>, lds))) return rc;                   \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, false, 4>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \
-        else if (slv == 2) { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, false, 2>, lds))) return rc;                   \
+        else if (slv == 2) { if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd_fast<SS, NN, false, 2>, lds))) return rc;                   \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, false, 2>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \
-        else { if ((rc = mid_allow_lds(k_mix_mid_bwd_fast<SS, NN, false, 0>, lds))) return rc;                                 \
+        else { if ((rc = rn_lds_grant((const void*)k_mix_mid_bwd_fast<SS, NN, false, 0>, lds))) return rc;                                 \
             hipLaunchKernelGGL((k_mix_mid_bwd_fast<SS, NN, false, 0>), grid, 256, lds, st, dT2g, T2, T1, V, dT1, part, B, LDT, act_inner, act_outer, rscale, sl); } \
         done = true;                                                                                                          \
     }

@@ -23,7 +23,6 @@
 // beside these launches.  Rules this file follows because their absence was measured: no load under a run-time condition,
 // no per-lane choice between kernel-argument array elements, tiles leave for memory through LDS as coalesced 16-byte pieces.
 #include <string.h>
-#include <atomic>
 #include "dcnmix_tile.hpp"
 #include "prof.hpp"
 
@@ -339,18 +338,8 @@ template <int NB>
 static int tile_launch(const RnTileFwd& p, int grid, hipStream_t st) {
     const size_t lds = (size_t)TL_LDS_FLOATS(128 * NB) * sizeof(float);
     const bool tanh2 = p.act_inner == RECNOW_ACT_TANH && p.act_outer == RECNOW_ACT_TANH;
-    // more than 64 KB of dynamic LDS: raised once per DEVICE and kernel (the attribute belongs to the function on the current device: a process
-    // that drives a second GPU must raise it there too); std::atomic<bool>: concurrent host threads may race to raise it, never to skip it
-    static std::atomic<bool> raised[2][64];
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    const int which = tanh2 ? 1 : 0;
-    if (dev < 0 || dev >= 64 || !raised[which][dev].load(std::memory_order_acquire)) {
-        hipError_t e = tanh2 ? hipFuncSetAttribute((const void*)k_mix_tile_fwd<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                             : hipFuncSetAttribute((const void*)k_mix_tile_fwd<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0 && dev < 64) raised[which][dev].store(true, std::memory_order_release);
-    }
+    // the resident weight packs and the row tiles of all layers: more than 64 KB of dynamic LDS
+    RN_HIP(rn_lds_grant(tanh2 ? (const void*)k_mix_tile_fwd<NB, true> : (const void*)k_mix_tile_fwd<NB, false>, lds));
     if (tanh2) hipLaunchKernelGGL((k_mix_tile_fwd<NB, true>), grid, 256, lds, st, p);
     else hipLaunchKernelGGL((k_mix_tile_fwd<NB, false>), grid, 256, lds, st, p);
     RN_LAUNCH_CHECK();
@@ -806,16 +795,10 @@ static int tile_bwd_launch(const RnTileBwd& p, int grid, hipStream_t st) {
     const size_t lds = (size_t)TLB_LDS_FLOATS * sizeof(float);
     const bool tanh2 = p.act_inner == RECNOW_ACT_TANH && p.act_outer == RECNOW_ACT_TANH;
     const bool dx = p.dx != nullptr;
-    static std::atomic<bool> raised[4][64];      // per device, as in tile_launch
     const int v = (tanh2 ? 2 : 0) + (dx ? 1 : 0);
     const void* fn = v == 3 ? (const void*)k_mix_tile_bwd<NB, true, true> : v == 2 ? (const void*)k_mix_tile_bwd<NB, true, false>
                    : v == 1 ? (const void*)k_mix_tile_bwd<NB, false, true> : (const void*)k_mix_tile_bwd<NB, false, false>;
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !raised[v][dev].load(std::memory_order_acquire)) {
-        RN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) raised[v][dev].store(true, std::memory_order_release);
-    }
+    RN_HIP(rn_lds_grant(fn, lds));
     if (v == 3) hipLaunchKernelGGL((k_mix_tile_bwd<NB, true, true>), grid, 256, lds, st, p);
     else if (v == 2) hipLaunchKernelGGL((k_mix_tile_bwd<NB, true, false>), grid, 256, lds, st, p);
     else if (v == 1) hipLaunchKernelGGL((k_mix_tile_bwd<NB, false, true>), grid, 256, lds, st, p);

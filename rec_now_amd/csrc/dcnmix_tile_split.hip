@@ -24,7 +24,6 @@
 // launches of the product route in split precision (0.95 ms): the route is therefore OPT-IN (RECNOW_TILE_SPLIT=1, dcnmix.hip), held to the oracle by
 // tests/test_tile_gpu.py.  Where the time goes: DESIGN.md 5l.
 #include <string.h>
-#include <atomic>
 #include "dcnmix_tile.hpp"
 #include "gemm_split.hpp"
 #include "prof.hpp"
@@ -408,16 +407,7 @@ template <int NB>
 static int ts_launch(const RnTileFwd& p, int grid, hipStream_t st) {
     const size_t lds = (size_t)TS_LDS_BYTES(128 * NB);
     const bool tanh2 = p.act_inner == RECNOW_ACT_TANH && p.act_outer == RECNOW_ACT_TANH;
-    static std::atomic<bool> raised[2][64];
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    const int which = tanh2 ? 1 : 0;
-    if (dev < 0 || dev >= 64 || !raised[which][dev].load(std::memory_order_acquire)) {
-        hipError_t e = tanh2 ? hipFuncSetAttribute((const void*)k_mix_tile_fwd_s3<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                             : hipFuncSetAttribute((const void*)k_mix_tile_fwd_s3<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0 && dev < 64) raised[which][dev].store(true, std::memory_order_release);
-    }
+    RN_HIP(rn_lds_grant(tanh2 ? (const void*)k_mix_tile_fwd_s3<NB, true> : (const void*)k_mix_tile_fwd_s3<NB, false>, lds));
     if (tanh2) hipLaunchKernelGGL((k_mix_tile_fwd_s3<NB, true>), grid, 256, lds, st, p);
     else hipLaunchKernelGGL((k_mix_tile_fwd_s3<NB, false>), grid, 256, lds, st, p);
     RN_LAUNCH_CHECK();

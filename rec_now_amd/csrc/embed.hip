@@ -96,7 +96,7 @@ k_embed_pool_fwd(const float* __restrict__ table, int D, int64_t V, const int64_
     float* cnt = acc + T * D;
     for (int64_t b = (int64_t)blockIdx.x * nw + w; b < B; b += (int64_t)gridDim.x * nw) {
         for (int i = lane; i < T * D + T; i += 64) acc[i] = 0.f;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
         // The row's entries, 64 at a time: lane l fetches (target, table row, weight) of entry c0 + l -- coalesced, all in
         // flight at once.  Lane group g then owns the targets t with t % G == g: it takes its entries in ascending order
         // from a ballot mask, four table rows in flight, and adds them into the ONE [T][D] tile -- groups never meet on a
@@ -146,7 +146,7 @@ k_embed_pool_fwd(const float* __restrict__ table, int D, int64_t V, const int64_
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
         if (cnt_out)
             for (int t = lane; t < T; t += 64) cnt_out[b * T + t] = cnt[t];
         for (int i = lane; i < T * D; i += 64) {
@@ -157,7 +157,7 @@ k_embed_pool_fwd(const float* __restrict__ table, int D, int64_t V, const int64_
             }
             out[b * T * D + i] = s;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
     }
 }
 
@@ -180,7 +180,7 @@ k_embed_pool_fwd_v4(const float* __restrict__ table, int D, int64_t V, const int
     float* cnt = acc + T * D;
     for (int64_t b = (int64_t)blockIdx.x * nw + w; b < B; b += (int64_t)gridDim.x * nw) {
         for (int i = lane; i < T * D + T; i += 64) acc[i] = 0.f;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
         for (int c0 = 0; c0 < C; c0 += 64) {
             const int cl = c0 + lane;
             int m_t = -1;
@@ -226,7 +226,7 @@ k_embed_pool_fwd_v4(const float* __restrict__ table, int D, int64_t V, const int
                     }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
         if (cnt_out)
             for (int t = lane; t < T; t += 64) cnt_out[b * T + t] = cnt[t];
         for (int i = lane; i < T * GS; i += 64) {                            // float4 per lane: whole 1 KiB pieces of the output row
@@ -237,7 +237,7 @@ k_embed_pool_fwd_v4(const float* __restrict__ table, int D, int64_t V, const int
             }
             *reinterpret_cast<emb_f4*>(out + b * T * D + 4 * i) = sv;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
     }
 }
 

@@ -66,11 +66,6 @@ struct GemmK {
     int mid_act_outer;
 };
 
-// Order one wave's LDS writes against its own later LDS reads (and reads against later overwrites).  DS instructions of a
-// wave execute in issue order, so only the compiler has to be stopped from moving them; waiting on lgkmcnt alone (not a
-// fence, which also drains vmcnt) keeps the epilogue's global stores asynchronous.
-#define RN_LDS_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-
 __device__ __forceinline__ f32x4 mk4(float a, float b, float c, float d) {
     f32x4 r;
     r.x = a; r.y = b; r.z = c; r.w = d;

@@ -17,7 +17,6 @@
 // reduced across the threads that share a row at the end (there is no fp32 image in LDS to read it from).
 #include "gemm_split.hpp"
 #include "prof.hpp"
-#include <atomic>
 #include <type_traits>
 
 // B (K x N; [K][N] rows of ldb floats, or [N][K] when b_kc) -> planes[s][K/8][N] units of 8 bf16 (16 B): unit (o, n) of piece s
@@ -622,27 +621,21 @@ static bool s3_shape(const GemmK& k, int a2k) {
     return k.batch == 1 && k.N == 128 && k.sp_r >= 1 && k.sp_r <= 2 && k.kchunk % (2 * SPL_BK) == 0 && k.K % k.kchunk == 0 && k.kchunk <= S3_BX_MAXK &&
            (a2k == RECNOW_OPMODE_NONE || a2k == RECNOW_OPMODE_MUL) && !k.as_out;
 }
-static std::atomic<int> g_s3_lds_ready[8];      // dynamic-LDS attribute raised per instantiation (the default limit is 64 KB; a chunk of 2048 k needs 66 KB)
+// a chunk of 2048 k needs 66 KB of dynamic LDS: more than the default limit of 64 KB
 template <bool A_KC, int A2K>
-static int s3_launch(const GemmK& k, const char* planes, int64_t pb, dim3 grid, hipStream_t st, int slot) {
+static int s3_launch(const GemmK& k, const char* planes, int64_t pb, dim3 grid, hipStream_t st) {
     const size_t lds = S3_LDS(k.kchunk);
     // paired A loads (see the kernel): k-contiguous operands, whole groups of four k-tiles, rows that start on a 128-byte line; RECNOW_S3_PAIR=0: A/B switch
     static const bool pair_on = rn_env_int("RECNOW_S3_PAIR", 1) != 0;
     if constexpr (A_KC) {
         if (pair_on && k.kchunk % (4 * SPL_BK) == 0 && k.lda % 32 == 0 && ((uintptr_t)k.A & 127) == 0 && (A2K == RECNOW_OPMODE_NONE || ((uintptr_t)k.A2 & 127) == 0)) {
-            if (lds > 64 * 1024 && !g_s3_lds_ready[4 + slot].load(std::memory_order_acquire)) {
-                RN_HIP(hipFuncSetAttribute((const void*)k_gemm_s3<A_KC, A2K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3_LDS(S3_BX_MAXK)));
-                g_s3_lds_ready[4 + slot].store(1, std::memory_order_release);
-            }
+            if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_gemm_s3<A_KC, A2K, true>, S3_LDS(S3_BX_MAXK)));
             hipLaunchKernelGGL((k_gemm_s3<A_KC, A2K, true>), grid, GEMM_THREADS, lds, st, k, planes, pb);
             RN_LAUNCH_CHECK();
             return RECNOW_OK;
         }
     }
-    if (lds > 64 * 1024 && !g_s3_lds_ready[slot].load(std::memory_order_acquire)) {
-        RN_HIP(hipFuncSetAttribute((const void*)k_gemm_s3<A_KC, A2K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3_LDS(S3_BX_MAXK)));
-        g_s3_lds_ready[slot].store(1, std::memory_order_release);
-    }
+    if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_gemm_s3<A_KC, A2K>, S3_LDS(S3_BX_MAXK)));
     hipLaunchKernelGGL((k_gemm_s3<A_KC, A2K>), grid, GEMM_THREADS, lds, st, k, planes, pb);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
@@ -663,13 +656,13 @@ int rn_gemm_launch_split(const GemmK& k, bool a_kc, bool b_kc, int a2k, void* pl
     static const bool s3_kb = rn_env_int("RECNOW_SPLIT_LEAN", 0) == 2;
     // ready != NULL: the caller holds the planes of this product's B already (the packed weights of a step are split once, dcnmix.hip)
     if (ready && s3_on && s3_shape(k, a2k) && a_kc)
-        return a2k == 0 ? s3_launch<true, 0>(k, (const char*)ready, pb, grid, st, 0) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)ready, pb, grid, st, 1);
+        return a2k == 0 ? s3_launch<true, 0>(k, (const char*)ready, pb, grid, st) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)ready, pb, grid, st);
     if (planes && s3_on && s3_shape(k, a2k) && (a_kc || (!b_kc && s3_kb))) {
         const int64_t units = (int64_t)(k.K / 8) * k.N;
         hipLaunchKernelGGL(k_split_planes, (unsigned)((units + 255) / 256), 256, 0, st, k.B, k.ldb, b_kc ? 1 : 0, k.K, k.N, (char*)planes);
         RN_LAUNCH_CHECK();
-        if (a_kc) return a2k == 0 ? s3_launch<true, 0>(k, (const char*)planes, pb, grid, st, 0) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)planes, pb, grid, st, 1);
-        return a2k == 0 ? s3_launch<false, 0>(k, (const char*)planes, pb, grid, st, 2) : s3_launch<false, RECNOW_OPMODE_MUL>(k, (const char*)planes, pb, grid, st, 3);
+        if (a_kc) return a2k == 0 ? s3_launch<true, 0>(k, (const char*)planes, pb, grid, st) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)planes, pb, grid, st);
+        return a2k == 0 ? s3_launch<false, 0>(k, (const char*)planes, pb, grid, st) : s3_launch<false, RECNOW_OPMODE_MUL>(k, (const char*)planes, pb, grid, st);
     }
     if (planes && k.batch == 1 && a_kc && k.K <= 4096) {
         const int64_t units = (int64_t)(k.K / 8) * k.N;

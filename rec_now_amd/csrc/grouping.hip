@@ -1,6 +1,5 @@
 // The grouping front end: the one-launch kernels (one workgroup: group_small.hpp; cooperative: group_mid.hpp), the workspace layout, and the one
 // driver every consumer calls (grouping.hpp).  Key formation and the multi-launch chain for what fits no single launch are in scan_sort.hip.
-#include <atomic>
 #include "common.hpp"
 #include "scan.hpp"
 #include "grouping.hpp"
@@ -209,18 +208,12 @@ extern "C" size_t recnow_group_segments_workspace_bytes(int64_t B, int n_words) 
     return rn_group_ws(nullptr, B, n_words).total;
 }
 
-// The one-workgroup kernels need gs_lds_bytes() of dynamic LDS: their limit is raised once per device (not a stream operation: a first call outside a
-// stream capture does it, every later call and every capture finds it done).
+// The one-workgroup kernels need gs_lds_bytes() of dynamic LDS: their limit is raised on every device they run on (not a stream operation: a first call
+// outside a stream capture does it, every later call and every capture finds it done).
 static int gs_raise_lds_limit() {
-    static std::atomic<bool> raised[64];
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-        const void* const kernels[5] = {(const void*)k_group_small<0>, (const void*)k_group_small<1>, (const void*)k_group_small<2>,
-                                        (const void*)k_front_small<1>, (const void*)k_front_small<2>};
-        for (const void* k : kernels) RN_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs_lds_bytes()));
-        if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-    }
+    const void* const kernels[5] = {(const void*)k_group_small<0>, (const void*)k_group_small<1>, (const void*)k_group_small<2>,
+                                    (const void*)k_front_small<1>, (const void*)k_front_small<2>};
+    for (const void* k : kernels) RN_HIP(rn_lds_grant(k, gs_lds_bytes()));
     return RECNOW_OK;
 }
 

@@ -34,7 +34,7 @@ k_ipnn_fwd(const float* const* __restrict__ fields, int F, int64_t B, int D, flo
             xb[i] = v;
             if (d < D) xs[f * LD + d] = v;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's own LDS writes, then its reads
+        RN_LDS_WAVE_SYNC();                 // the wave's own LDS writes, then its reads
         float* ob = out + b * P;
         for (int c0 = 0; c0 < F; c0 += 64) {
             const int c = c0 + lane;
@@ -52,7 +52,7 @@ k_ipnn_fwd(const float* const* __restrict__ fields, int F, int64_t B, int D, flo
                 if (c > r && c < F) ob[(int64_t)r * F - (int64_t)r * (r + 1) / 2 + (c - r - 1)] = s;
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the next row overwrites the tile
+        RN_LDS_WAVE_SYNC();                 // reads done before the next row overwrites the tile
     }
 }
 
@@ -72,7 +72,7 @@ k_ipnn_bwd(const float* const* __restrict__ fields, float* const* __restrict__ d
             xb[i] = d < D ? fields[f][b * D + d] : 0.f;
         }
         for (int i = lane; i < P; i += 64) gs[i] = dout[b * P + i];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        RN_LDS_WAVE_SYNC();
         for (int f0 = 0; f0 < F; f0 += 64) {
             const int f = f0 + lane;
             float acc[DMAX];
@@ -100,7 +100,7 @@ k_ipnn_bwd(const float* const* __restrict__ fields, float* const* __restrict__ d
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the next row overwrites the tile
+        RN_LDS_WAVE_SYNC();                 // reads done before the next row overwrites the tile
     }
 }
 
@@ -118,8 +118,6 @@ k_ipnn_bwd(const float* const* __restrict__ fields, float* const* __restrict__ d
 //    dword stores made the L2 fetch the output lines (0.66 ms instead of 0.60 with everything else equal).
 typedef float ipnn_acc16 __attribute__((ext_vector_type(16)));
 typedef float ipnn_acc4 __attribute__((ext_vector_type(4)));
-// LDS hand-over inside ONE wave (the tiles are wave-private): outstanding LDS operations retired, no vmcnt drain
-#define IPNN_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 template <int D>
 __global__ void __launch_bounds__(256)
 k_ipnn_fwd_gram(const float* const* __restrict__ fields, int F, int64_t B, int64_t wstride, float* __restrict__ out) {
@@ -159,7 +157,7 @@ k_ipnn_fwd_gram(const float* const* __restrict__ fields, int F, int64_t B, int64
             for (int t = 0; t < NLD; ++t)
                 if (src[t]) nx[t] = *reinterpret_cast<const RN_GLOBAL ipnn_acc4*>(src[t] + (bb + nw) * D);
         }
-        IPNN_WAVE_SYNC();                                                   // the tile is private to this wave
+        RN_LDS_WAVE_SYNC();                                                 // the tile is private to this wave
         float a0[HD], a1[HD];
 #pragma unroll
         for (int k = 0; k < HD; k += 2) {
@@ -168,7 +166,7 @@ k_ipnn_fwd_gram(const float* const* __restrict__ fields, int F, int64_t B, int64
             const float2 w = *reinterpret_cast<const float2*>(tile + (32 + j) * XS + h * HD + k);      // garbage rows (f >= F) only reach pairs that are never stored
             a1[k] = w.x; a1[k + 1] = w.y;
         }
-        IPNN_WAVE_SYNC();                                                   // operands are in registers: the tile may be overwritten
+        RN_LDS_WAVE_SYNC();                                                 // operands are in registers: the tile may be overwritten
         ipnn_acc16 g00, g01, g11;
 #pragma unroll
         for (int v = 0; v < 16; ++v) { g00[v] = 0.f; g01[v] = 0.f; g11[v] = 0.f; }
@@ -199,14 +197,14 @@ k_ipnn_fwd_gram(const float* const* __restrict__ fields, int F, int64_t B, int64
                 if (32 + j > r && 32 + j < F) tile[base + 32 + jo] = g11[v];
             }
         }
-        IPNN_WAVE_SYNC();
+        RN_LDS_WAVE_SYNC();
         float* og = out + b * P;
         if (((P & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
             for (int64_t i = lane * 4; i < P; i += 256) *reinterpret_cast<float4*>(og + i) = *reinterpret_cast<const float4*>(tile + i);
         } else {
             for (int64_t i = lane; i < P; i += 64) og[i] = tile[i];
         }
-        IPNN_WAVE_SYNC();                                                   // results read back before the next tile lands
+        RN_LDS_WAVE_SYNC();                                                 // results read back before the next tile lands
     }
 }
 
@@ -288,7 +286,7 @@ k_ipnn_bwd_gram(const float* const* __restrict__ fields, float* const* __restric
             for (int64_t i = lane; i < P; i += 64) lin[i] = dout[b * P + i];
         }
         if (bb + nw < B) ipnn_bwd_request<D>(src, nx, nd, dout, bb + nw, P, lane, vec);
-        IPNN_WAVE_SYNC();
+        RN_LDS_WAVE_SYNC();
         float bx[4 * NB];
 #pragma unroll
         for (int kk = 0; kk < 4 * NB; ++kk) bx[kk] = xt[(4 * kk + kq) * 16 + i16];
@@ -327,7 +325,7 @@ k_ipnn_bwd_gram(const float* const* __restrict__ fields, float* const* __restric
                 }
             }
         }
-        IPNN_WAVE_SYNC();                                                   // every lane has its B operands: the X tile is dead
+        RN_LDS_WAVE_SYNC();                                                 // every lane has its B operands: the X tile is dead
 #pragma unroll
         for (int I = 0; I < NB; ++I)
 #pragma unroll
@@ -335,11 +333,11 @@ k_ipnn_bwd_gram(const float* const* __restrict__ fields, float* const* __restric
                 const int f = 16 * I + 4 * kq + v;
                 if (f < F) xt[f * 16 + i16] = acc[I][v];                    // rows >= F stay zero for the next row's k slots
             }
-        IPNN_WAVE_SYNC();
+        RN_LDS_WAVE_SYNC();
 #pragma unroll
         for (int t = 0; t < CPF; ++t)
             if (dsrc[t]) *reinterpret_cast<RN_GLOBAL ipnn_acc4*>(dsrc[t] + b * D) = *reinterpret_cast<const ipnn_acc4*>(xt + dst[t]);
-        IPNN_WAVE_SYNC();                                                   // dX read back before the next X tile lands
+        RN_LDS_WAVE_SYNC();                                                 // dX read back before the next X tile lands
     }
 }
 

@@ -9,7 +9,6 @@
 //             its rows and added up in a fixed order afterwards (deterministic).
 // Limits: equal field widths D % 4 == 0 with D/4 a power of two, F*D/4 <= 256 (a row is one float4 per thread), F <= 64,
 // M <= 64, built-in activations.  Everything else takes the unfused kernels.
-#include <atomic>
 #include "common.hpp"
 #include "gemm.hpp"
 
@@ -391,15 +390,7 @@ extern "C" int recnow_senet_fused_fwd(const float* const* fields, int F, int D, 
     const SfDims dm = {F, D, M, act1, act2, (b1 || b2) ? 1 : 0};
     if (sf8_ok(F, D, M) && ((uintptr_t)out & 15) == 0) {
         const size_t lds = sf8_lds_floats(F, M) * sizeof(float);
-        if (lds > 64 * 1024) {
-            static std::atomic<bool> raised[64];
-            int dev = 0;
-            RN_HIP(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-                RN_HIP(hipFuncSetAttribute((const void*)k_senet_fused_fwd8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sf8_lds_floats(64, 64) * sizeof(float))));
-                if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-            }
-        }
+        if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_senet_fused_fwd8, sf8_lds_floats(64, 64) * sizeof(float)));
         int64_t g = (B + S8_R - 1) / S8_R;
         if (g > 2048) g = 2048;
         hipLaunchKernelGGL(k_senet_fused_fwd8, (int)g, 256, lds, (hipStream_t)stream, fields, dm, B, W1, b1, W2, b2, out, sq_save, h_save, w_save);

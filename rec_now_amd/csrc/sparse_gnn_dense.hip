@@ -269,19 +269,11 @@ int sd_densify(const float* w, const int32_t* src, const int32_t* dst, float* M,
     return RECNOW_OK;
 }
 
-// Dynamic LDS a workgroup of `kernel` may own on this device: raising the kernel's limit IS the query (the device attribute only reports the
-// 64 KB default); asked once per kernel and device.
+// Dynamic LDS a workgroup of the backward may own on this device: raising the kernel's limit IS the query (the device attribute only reports
+// the 64 KB default); rn_lds_grant remembers either answer.
 template <int NB>
 size_t sd_bwd_lds_cap() {
-    static int cached[64];        // 0 = not asked, 1 = 160 KB, 2 = 64 KB
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 64 * 1024;
-    if (!cached[dev]) {
-        const bool ok = hipFuncSetAttribute((const void*)k_sd_bwd<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        cached[dev] = ok ? 1 : 2;
-    }
-    return cached[dev] == 1 ? 160 * 1024 : 64 * 1024;
+    return rn_lds_grant((const void*)k_sd_bwd<NB>, 160 * 1024) == hipSuccess ? 160 * 1024 : 64 * 1024;
 }
 
 // Ring slots of the backward: as many as L needs inside 40 KB (four workgroups per CU); else inside 64 KB; else inside what the device allows.

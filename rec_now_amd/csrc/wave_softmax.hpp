@@ -2,8 +2,6 @@
 // values at once and the compensated exponential.  Included after common.hpp.
 #pragma once
 
-#define AI_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")        // LDS hand-over inside ONE wave
-
 // Wave reductions of four values at once (the four queries of a block: four independent chains hide each other's latency).  Every step
 // exchanges between lane PAIRS (l <-> l ^ 1, l ^ 2, 7 - l and 15 - l inside a row of 16 lanes by DPP, l ^ 16 and l ^ 32 through the LDS
 // crossbar), so both partners form the same sum and all lanes end with the same bits.  n2 is a power of two >= F; lanes >= F hold the

@@ -20,7 +20,7 @@ import torch
 
 from .. import _lib
 from ._keras import Layer, get_initializer
-from .interacting_layer import _field_table
+from ._fields import check_fields, field_table, rows_table
 
 _MAX_F, _MAX_D, _MAX_A = 64, 64, 64                      # AFM_MAX_* of csrc/afm.hip
 
@@ -40,12 +40,11 @@ class _AFMFunction(torch.autograd.Function):
             x = _lib.f32c(inputs[0], 'AFMLayer input')
             B, F, D = x.shape
             xs = [x]
-            table = _lib.const_array([x.data_ptr() + 4 * f * D for f in range(F)], torch.int64, x.device)
-            stride = F * D
+            table, stride = rows_table(x), F * D
         else:
             for t in inputs:
                 _lib.require_gpu(t, 'AFMLayer input')
-            xs, table, stride = _field_table(list(inputs))
+            xs, table, stride = field_table(list(inputs), 'AFMLayer input')
             B, D = xs[0].shape
             F = len(xs)
         ws = [_lib.f32c(t, 'AFMLayer weight') if t is not None else None for t in (w, b, h, p)]
@@ -82,8 +81,7 @@ class _AFMFunction(torch.autograd.Function):
                 dws = [torch.empty_like(t) if t is not None else None for t in ws]
                 ws_bytes = int(_lib.load().recnow_afm_workspace_bytes(B, F, D, A))
                 wsp = _lib.workspace(ws_bytes, dev)
-            dtable = _lib.const_array([dx.data_ptr() + 4 * f * D for f in range(F)], torch.int64, dev)
-            _lib.call('recnow_afm_bwd', _lib.ptr(ctx.table), ctx.stride, _lib.ptr(dtable), F * D, F, B, D, A, _lib.ptr(ws[0]), _lib.ptr(ws[1]),
+            _lib.call('recnow_afm_bwd', _lib.ptr(ctx.table), ctx.stride, _lib.ptr(rows_table(dx)), F * D, F, B, D, A, _lib.ptr(ws[0]), _lib.ptr(ws[1]),
                       _lib.ptr(ws[2]), _lib.ptr(ws[3]), _lib.ptr(dout), _lib.ptr(dws[0]), _lib.ptr(dws[1]), _lib.ptr(dws[2]), _lib.ptr(dws[3]),
                       _lib.ptr(wsp), ws_bytes, _lib.stream())
         grads = (dx,) if ctx.three_d else tuple(dx[:, f] for f in range(F))
@@ -112,24 +110,8 @@ class AFMLayer(Layer):
         self.kernel_regularizer = kernel_regularizer
         self.kernel_constraint = kernel_constraint
 
-    @staticmethod
-    def _check(shapes):
-        """(F, D) of a (B, F, D) shape or of a list of F equal (B, D) shapes."""
-        if isinstance(shapes, (list, tuple)) and len(shapes) > 0 and isinstance(shapes[0], (list, tuple, torch.Size)):
-            first = tuple(shapes[0])
-            if len(first) != 2:
-                raise ValueError('AFMLayer fields must be (B, D) tensors, got shape %s' % (first,))
-            for s in shapes:
-                if tuple(s) != first:
-                    raise ValueError('all AFMLayer fields must have the same (B, D) shape, got %s and %s' % (first, tuple(s)))
-            return len(shapes), int(first[1])
-        shape = tuple(shapes) if isinstance(shapes, (list, tuple, torch.Size)) else ()
-        if len(shape) != 3:
-            raise ValueError('AFMLayer takes a (B, F, D) tensor or a list of (B, D) field tensors, got shape %s' % (shape,))
-        return int(shape[1]), int(shape[2])
-
     def build(self, input_shape):
-        F, D = self._check(input_shape)
+        F, D = check_fields('AFMLayer', input_shape)
         A = self.attention_factor
         kw = dict(initializer=get_initializer(self.kernel_initializer), regularizer=self.kernel_regularizer, constraint=self.kernel_constraint)
         self.attention_W = self.add_weight('attention_W', (D, A), **kw)
@@ -141,12 +123,12 @@ class AFMLayer(Layer):
     def call(self, inputs):
         """inputs: a float32 GPU tensor (B, F, D) or a list of F float32 GPU tensors (B, D) -> (B, 1) with projection, else (B, D)."""
         if isinstance(inputs, torch.Tensor):
-            F, D = self._check(tuple(inputs.shape))
+            F, D = check_fields('AFMLayer', tuple(inputs.shape))
             tensors = [inputs]
         else:
             if not isinstance(inputs, (list, tuple)) or len(inputs) < 1:
                 raise ValueError('AFMLayer takes a (B, F, D) tensor or a list of (B, D) field tensors')
-            F, D = self._check([tuple(x.shape) for x in inputs])
+            F, D = check_fields('AFMLayer', [tuple(x.shape) for x in inputs])
             tensors = list(inputs)
         A = self.attention_factor
         want = [('attention_W', (D, A)), ('attention_b', (A,)), ('projection_h', (A, 1))] + ([('projection_p', (D, 1))] if self.projection else [])

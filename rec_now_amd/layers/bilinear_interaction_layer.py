@@ -14,6 +14,7 @@ Symbols: B batch size, D embedding dim, F number of fields, P = F(F-1)/2.
 import torch
 
 from .. import _lib
+from ._fields import check_fields
 from ._keras import Layer, get_initializer
 
 _TYPES = {'all': 0, 'each': 1, 'interaction': 2}        # RECNOW_BILINEAR_* of include/recnow.h
@@ -95,20 +96,8 @@ class BilinearInteractionLayer(Layer):
         self.kernel_regularizer = kernel_regularizer
         self.kernel_constraint = kernel_constraint
 
-    @staticmethod
-    def _check(shapes):
-        if not isinstance(shapes, (list, tuple)) or len(shapes) < 1:
-            raise ValueError('BilinearInteractionLayer takes a list of (B, D) field tensors')
-        first = tuple(shapes[0])
-        if len(first) != 2:
-            raise ValueError('BilinearInteractionLayer fields must be (B, D) tensors, got shape %s' % (first,))
-        for s in shapes:
-            if tuple(s) != first:
-                raise ValueError('all BilinearInteractionLayer fields must have the same (B, D) shape, got %s and %s' % (first, tuple(s)))
-        return len(shapes), int(first[1])
-
     def build(self, input_shape):
-        F, D = self._check(input_shape)
+        F, D = check_fields('BilinearInteractionLayer', input_shape, allow_3d=False)
         nW = n_weights(self.bilinear_type, F)
         init = self.kernel_initializer
         if not callable(init):
@@ -120,7 +109,7 @@ class BilinearInteractionLayer(Layer):
 
     def call(self, inputs):
         """inputs: list of F float32 GPU tensors of shape (B, D).  Returns (B, P*D), block p at columns [p*D, (p+1)*D)."""
-        F, D = self._check([tuple(x.shape) for x in inputs])
+        F, D = check_fields('BilinearInteractionLayer', [tuple(x.shape) for x in inputs], allow_3d=False)
         w = self.bilinear_weight
         if tuple(w.shape) != (n_weights(self.bilinear_type, F), D, D):
             raise ValueError("bilinear_weight has shape %s; bilinear_type '%s' with %d fields of width %d needs %s"

@@ -17,6 +17,7 @@ Symbols: B batch size, F number of fields, D embedding dim, H head_num, d att_em
 import torch
 
 from .. import _lib
+from ._fields import check_fields, field_table, rows_table
 from ._keras import Layer, get_initializer
 
 _MAX_F, _MAX_D, _MAX_E, _MAX_H = 64, 64, 64, 8           # AI_MAX_* of csrc/autoint.hip
@@ -26,17 +27,6 @@ _ACTIVATIONS = {'relu': 1, None: 0}
 def autoint_supported(F, D, head_num, att_embedding_size):
     """Whether the kernels take this shape (host-only query of the library, no device call)."""
     return bool(_lib.load().recnow_autoint_supported(int(F), int(D), int(head_num), int(att_embedding_size)))
-
-
-def _field_table(xs):
-    """(tensors kept alive, pointer table, row stride) of F (B, D) fields that share one row stride and have unit column stride --
-    views of one (B, F, D) or (B, F*D) tensor pass as they are; anything else is made contiguous."""
-    B, D = xs[0].shape
-    stride = xs[0].stride(0) if B > 1 else D
-    if not all(x.dtype == torch.float32 and (D == 1 or x.stride(1) == 1) and (B <= 1 or x.stride(0) == stride) for x in xs) or stride < D:
-        xs = [_lib.f32c(x, 'InteractingLayer input') for x in xs]
-        stride = D
-    return xs, _lib.ptr_array(xs, xs[0].device), stride
 
 
 class _InteractingFunction(torch.autograd.Function):
@@ -50,12 +40,11 @@ class _InteractingFunction(torch.autograd.Function):
             x = _lib.f32c(inputs[0], 'InteractingLayer input')
             B, F, D = x.shape
             xs = [x]
-            table = _lib.const_array([x.data_ptr() + 4 * f * D for f in range(F)], torch.int64, x.device)
-            stride = F * D
+            table, stride = rows_table(x), F * D
         else:
             for t in inputs:
                 _lib.require_gpu(t, 'InteractingLayer input')
-            xs, table, stride = _field_table(list(inputs))
+            xs, table, stride = field_table(list(inputs), 'InteractingLayer input')
             B, D = xs[0].shape
             F = len(xs)
         ws = [_lib.f32c(w, 'InteractingLayer weight') if w is not None else None for w in (wq, wk, wv, wr)]
@@ -88,8 +77,7 @@ class _InteractingFunction(torch.autograd.Function):
                 dws = [torch.empty_like(w) if w is not None else None for w in ws]
                 ws_bytes = int(_lib.load().recnow_autoint_workspace_bytes(B, F, D, H, d, int(nW == 4)))
                 wsp = _lib.workspace(ws_bytes, dev)
-            dtable = _lib.const_array([dx.data_ptr() + 4 * f * D for f in range(F)], torch.int64, dev)
-            _lib.call('recnow_autoint_bwd', _lib.ptr(ctx.table), ctx.stride, _lib.ptr(dtable), F * D, F, B, D, H, d, _lib.ptr(ws[0]),
+            _lib.call('recnow_autoint_bwd', _lib.ptr(ctx.table), ctx.stride, _lib.ptr(rows_table(dx)), F * D, F, B, D, H, d, _lib.ptr(ws[0]),
                       _lib.ptr(ws[1]), _lib.ptr(ws[2]), _lib.ptr(ws[3]), scaling, relu, _lib.ptr(dout), _lib.ptr(dws[0]), _lib.ptr(dws[1]),
                       _lib.ptr(dws[2]), _lib.ptr(dws[3]), _lib.ptr(wsp), ws_bytes, _lib.stream())
         grads = (dx,) if ctx.three_d else tuple(dx[:, f] for f in range(F))
@@ -127,24 +115,8 @@ class InteractingLayer(Layer):
         self.kernel_regularizer = kernel_regularizer
         self.kernel_constraint = kernel_constraint
 
-    @staticmethod
-    def _check(shapes):
-        """(F, D) of a (B, F, D) shape or of a list of F equal (B, D) shapes."""
-        if isinstance(shapes, (list, tuple)) and len(shapes) > 0 and isinstance(shapes[0], (list, tuple, torch.Size)):
-            first = tuple(shapes[0])
-            if len(first) != 2:
-                raise ValueError('InteractingLayer fields must be (B, D) tensors, got shape %s' % (first,))
-            for s in shapes:
-                if tuple(s) != first:
-                    raise ValueError('all InteractingLayer fields must have the same (B, D) shape, got %s and %s' % (first, tuple(s)))
-            return len(shapes), int(first[1])
-        shape = tuple(shapes) if isinstance(shapes, (list, tuple, torch.Size)) else ()
-        if len(shape) != 3:
-            raise ValueError('InteractingLayer takes a (B, F, D) tensor or a list of (B, D) field tensors, got shape %s' % (shape,))
-        return int(shape[1]), int(shape[2])
-
     def build(self, input_shape):
-        F, D = self._check(input_shape)
+        F, D = check_fields('InteractingLayer', input_shape)
         E = self.head_num * self.att_embedding_size
         for name in ('W_query', 'W_key', 'W_value') + (('W_res',) if self.use_res else ()):
             w = self.add_weight(name, (D, E), initializer=get_initializer(self.kernel_initializer), regularizer=self.kernel_regularizer,
@@ -158,12 +130,12 @@ class InteractingLayer(Layer):
         """inputs: a float32 GPU tensor (B, F, D) -> (B, F, E), or a list of F float32 GPU tensors (B, D) -> (B, F*E), block f at
         columns [f E, (f+1) E)."""
         if isinstance(inputs, torch.Tensor):
-            F, D = self._check(tuple(inputs.shape))
+            F, D = check_fields('InteractingLayer', tuple(inputs.shape))
             tensors = [inputs]
         else:
             if not isinstance(inputs, (list, tuple)) or len(inputs) < 1:
                 raise ValueError('InteractingLayer takes a (B, F, D) tensor or a list of (B, D) field tensors')
-            F, D = self._check([tuple(x.shape) for x in inputs])
+            F, D = check_fields('InteractingLayer', [tuple(x.shape) for x in inputs])
             tensors = list(inputs)
         H, d = self.head_num, self.att_embedding_size
         E = H * d

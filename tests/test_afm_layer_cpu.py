@@ -236,14 +236,14 @@ def test_supported_and_route_queries():
 
 
 def test_workspace_bytes_follow_the_documented_formula():
-    """4 G n rounded up to 256 bytes, n = 4 ceil((D A + 2 A + D) / 4), G = max(1, min(ceil(B / AFM_DW_ROWS), AFM_MAXG, AFM_PART_BYTES / (4 n))) --
+    """4 G n rounded up to 256 bytes, n = 4 ceil((D A + 2 A + D) / 4), G = max(1, min(ceil(B / AFM_DW_ROWS), AFM_MAXG, RN_PART_BYTES / (4 n))) --
     read from the constants of csrc/afm.hip.  Bounded by a constant: it does not grow with B or F."""
     from rec_now_amd import _lib
     lib = _lib.load()
     c = _consts()
     rows, maxg = c['AFM_DW_ROWS'], c['AFM_MAXG']
     cap = 32 << 20
-    assert '#define AFM_PART_BYTES (32u << 20)' in open(os.path.join(ROOT, 'rec_now_amd', 'csrc', 'afm.hip')).read()
+    assert '#define RN_PART_BYTES (32u << 20)' in open(os.path.join(ROOT, 'rec_now_amd', 'csrc', 'partials.hpp')).read()
     for B in (0, 1, 3, 4, 5, 4096, 65536, 1 << 20):
         for F in (1, 2, 24, 64, 65):
             for D in (1, 5, 16, 64):

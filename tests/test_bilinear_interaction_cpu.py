@@ -202,13 +202,13 @@ def test_supported_and_route_queries():
 
 def test_workspace_bytes_follow_the_documented_formula():
     """[dU: 4 B (F-1) D for 'all' / 'each'] + 4 G S D^2, each rounded up to 256 bytes; S = F-1 or P, G = min(ceil(B / BIL_DW_ROWS),
-    BIL_DW_MAXG, max(1, BIL_DW_PART_BYTES / (4 S D^2))) -- read from the constants of csrc/bilinear.hip."""
+    BIL_DW_MAXG, max(1, RN_PART_BYTES / (4 S D^2))) -- read from the constants of csrc/bilinear.hip."""
     from rec_now_amd import _lib
     lib = _lib.load()
     c = _consts()
     rows, maxg = c['BIL_DW_ROWS'], c['BIL_DW_MAXG']
     cap = 32 << 20
-    assert '#define BIL_DW_PART_BYTES (32u << 20)' in open(os.path.join(ROOT, 'rec_now_amd', 'csrc', 'bilinear.hip')).read()
+    assert '#define RN_PART_BYTES (32u << 20)' in open(os.path.join(ROOT, 'rec_now_amd', 'csrc', 'partials.hpp')).read()
     up = lambda n: (n + 255) // 256 * 256                                      # noqa: E731
     for B in (0, 1, 255, 256, 257, 4096, 65536, 1 << 20):
         for F in (1, 2, 3, 24, 64, 65):

@@ -250,14 +250,14 @@ def test_supported_and_route_queries():
 
 
 def test_workspace_bytes_follow_the_documented_formula():
-    """4 G nW D E rounded up to 256 bytes, nW = 3 + use_res, G = max(1, min(ceil(B / AI_DW_ROWS), AI_MAXG, AI_PART_BYTES / (4 nW D E))) --
+    """4 G nW D E rounded up to 256 bytes, nW = 3 + use_res, G = max(1, min(ceil(B / AI_DW_ROWS), AI_MAXG, RN_PART_BYTES / (4 nW D E))) --
     read from the constants of csrc/autoint.hip.  Bounded by a constant: it does not grow as B F."""
     from rec_now_amd import _lib
     lib = _lib.load()
     c = _consts()
     rows, maxg = c['AI_DW_ROWS'], c['AI_MAXG']
     cap = 32 << 20
-    assert '#define AI_PART_BYTES (32u << 20)' in open(os.path.join(ROOT, 'rec_now_amd', 'csrc', 'autoint.hip')).read()
+    assert '#define RN_PART_BYTES (32u << 20)' in open(os.path.join(ROOT, 'rec_now_amd', 'csrc', 'partials.hpp')).read()
     for B in (0, 1, 7, 8, 9, 4096, 65536, 1 << 20):
         for F in (1, 24, 64, 65):
             for D in (1, 5, 16, 64):
