@@ -347,7 +347,11 @@ k_gemm_split(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_b
 // PAIR (round 6, second session; [row][k] operands, whole groups of four k-tiles): the A loads of k-tiles (2 j, 2 j + 1) are issued TOGETHER.  A wave load of a
 // k-contiguous operand covers 32 rows x 64 B -- half of each 128-byte line -- and the other half used to be asked for one k-tile (~1 us) later: with 32 CUs x 2
 // workgroups x 2 streams x 3 k-tiles in flight per XCD (6 MB against 4 MB of L2) the line was often gone by then and came from HBM a second time (PMC:
-// `k_gemm_s3<true, 1>` 738 MB per launch for 570 MB of operands).  Three register sets instead of two: E holds the even k-tiles, O1 / O2 the odd ones in turn.
+// `k_gemm_s3<true, 1>` 738 MB per launch for 570 MB of operands).  Four register sets instead of two: E1 / E2 hold the even k-tiles in turn, O1 / O2 the odd ones.
+// A pair is requested two pairs ahead, in an even k-tile and BEHIND that k-tile's B request: vmcnt retires in order, and the B planes (one register set, requested
+// one k-tile ahead) are waited for in every k-tile, so whatever is requested in front of a B request must land within one k-tile.  Behind it, the pair is first
+// waited for by the B wait of the next even k-tile: two k-tiles of flight for both halves (the three-set form asked for the pair in front of the B
+// request of an odd k-tile, and the next B wait -- vmcnt(0) -- drained it after one k-tile).
 template <bool A_KC, int A2K, bool PAIR = false>
 __global__ void __launch_bounds__(GEMM_THREADS, 2)
 k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_bytes) {
@@ -384,7 +388,7 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
     // bench.py's parity inputs (|logit| up to 39) carried an absolute error of 3.5e-6 rms -- row-wide gate errors up to 5.7e-6, by themselves
     // 1.2e-5 of max|d loss / d x| in the worst row of 65 536 (tools/micro/error_budget_cpu.py); this form leaves 2.5e-7 rms.
     double sp0 = 0.0, sp1 = 0.0;
-    constexpr int NSET = PAIR ? 3 : 2;
+    constexpr int NSET = PAIR ? 4 : 2;
     float va[NSET][8], ya[A2K != RECNOW_OPMODE_NONE ? NSET : 1][8];
     u32x4 bpl[3], wq[3];
 
@@ -477,12 +481,17 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
         *reinterpret_cast<f32x2*>(spl_smem + SPL_BX_OFF + i * 8) = w;
     }
     // prologue: k-tile 0 -> stage 0; A of k-tiles 1 (set 1) and 2 (set 0), B of k-tile 1 requested
-    // (PAIR: k-tiles 0 and 1 requested together into sets E = 0 and O1 = 1, then 2 and 3 into E and O2 = 2)
-    constexpr int Y1 = A2K != RECNOW_OPMODE_NONE ? 1 : 0, Y2 = A2K != RECNOW_OPMODE_NONE ? 2 : 0;
+    // (PAIR: k-tiles 0 and 1 requested together into sets E1 = 0 and O1 = 1, B of k-tile 0, then k-tiles 2 and 3 into E2 = 3 and O2 = 2; nt >= 4)
+    constexpr int Y1 = A2K != RECNOW_OPMODE_NONE ? 1 : 0, Y2 = A2K != RECNOW_OPMODE_NONE ? 2 : 0, Y3 = PAIR && A2K != RECNOW_OPMODE_NONE ? 3 : 0;
     a_issue(va[0], ya[0], 0);
-    if constexpr (PAIR) a_issue(va[1], ya[Y1], clampt(1));
+    if constexpr (PAIR) a_issue(va[1], ya[Y1], 1);
     b_issue(0);
-    if constexpr (!PAIR) a_issue(va[1], ya[Y1], clampt(1));
+    if constexpr (PAIR) {
+        a_issue(va[PAIR ? 3 : 0], ya[Y3], 2);
+        a_issue(va[PAIR ? 2 : 0], ya[Y2], 3);
+    } else {
+        a_issue(va[1], ya[Y1], clampt(1));
+    }
     __syncthreads();
     a_combine(va[0], ya[0]);
     a_side(va[0], 0);
@@ -490,8 +499,7 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
     split_pairs(va[0], 2);
     a_store(spl_smem);
     b_store(spl_smem);
-    a_issue(va[0], ya[0], clampt(2));
-    if constexpr (PAIR) a_issue(va[2], ya[Y2], clampt(3));
+    if constexpr (!PAIR) a_issue(va[0], ya[0], clampt(2));
     b_issue(clampt(1));
     __syncthreads();
 
@@ -506,7 +514,7 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
         _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[SA][i], bf[SB][j], acc[i][j], 0, 0, 0);
     // one k-tile: t = its index; SLOT holds A of k-tile t + 1; STG: stage k-tile t + 1 (false: the last k-tile, compute only)
-    // (PAIR: `issue_c` = the set that takes k-tile t + 4 beside SLOT's t + 3, or -1: this k-tile issues no A loads)
+    // (PAIR: `issue_c` = the even set that takes k-tile t + 4 beside SLOT, the odd set just emptied, which takes t + 5; or -1: this k-tile issues no A loads)
     auto ktile = [&](int t, auto slot_c, auto stage_c, auto issue_c) {
         constexpr int SLOT = decltype(slot_c)::value;
         constexpr int YS = A2K != RECNOW_OPMODE_NONE ? SLOT : 0;
@@ -540,17 +548,20 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
         __builtin_amdgcn_sched_barrier(0);
         S3_TERM(1, 1)
         if (STG) {
-            if constexpr (!PAIR) {
-                a_issue(va[SLOT], ya[YS], clampt(t + 3));
-            } else if constexpr (ISS >= 0) {
-                a_issue(va[SLOT], ya[YS], clampt(t + 3));
-                a_issue(va[ISS], ya[A2K != RECNOW_OPMODE_NONE ? ISS : 0], clampt(t + 4));
-            }
+            if constexpr (!PAIR) a_issue(va[SLOT], ya[YS], clampt(t + 3));
             b_store(Sn);
+            if constexpr (PAIR && ISS >= 0) b_issue(clampt(t + 2));         // in front of the pair: the next B wait leaves the pair in flight
         }
         __builtin_amdgcn_sched_barrier(0);
         S3_TERM(0, 2)
-        if (STG) b_issue(clampt(t + 2));
+        if (STG) {
+            if constexpr (PAIR && ISS >= 0) {
+                a_issue(va[ISS >= 0 ? ISS : 0], ya[A2K != RECNOW_OPMODE_NONE && ISS >= 0 ? ISS : 0], t + 4);
+                a_issue(va[SLOT], ya[YS], t + 5);
+            } else {
+                b_issue(clampt(t + 2));
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         S3_TERM(2, 0)
         __syncthreads();
@@ -558,6 +569,7 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
+    using I3 = std::integral_constant<int, 3>;
     using IN = std::integral_constant<int, -1>;
     using BT = std::integral_constant<bool, true>;
     using BF = std::integral_constant<bool, false>;
@@ -570,16 +582,17 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
         ktile(t, I1(), BT(), IN());
         ktile(t + 1, I0(), BF(), IN());
     } else {
-        // k-tile t stages k-tile t + 1: an odd one from O1 / O2 (t = 0, 2 mod 4), an even one from E (t odd), which then takes k-tile t + 3 while the
-        // odd set that was emptied one k-tile before takes t + 4 -- the two halves of the same 128-byte lines, requested back to back
+        // k-tile t stages k-tile t + 1: an odd one from O1 / O2 (t = 0, 2 mod 4), an even one from E2 / E1 (t = 1, 3 mod 4).  An even k-tile then asks for
+        // the pair two pairs ahead: t + 4 into the even set emptied one k-tile before, t + 5 into the odd set it has just emptied -- the two halves of the
+        // same 128-byte lines, requested back to back.  The last trip asks for k-tiles nt - 4 .. nt - 1: nothing outside the chunk, no clamp.
         for (; t + 4 < nt; t += 4) {
-            ktile(t, I1(), BT(), IN());
-            ktile(t + 1, I0(), BT(), I1());
-            ktile(t + 2, I2(), BT(), IN());
-            ktile(t + 3, I0(), BT(), I2());
+            ktile(t, I1(), BT(), I0());
+            ktile(t + 1, I3(), BT(), IN());
+            ktile(t + 2, I2(), BT(), I3());
+            ktile(t + 3, I0(), BT(), IN());
         }
         ktile(t, I1(), BT(), IN());
-        ktile(t + 1, I0(), BT(), IN());
+        ktile(t + 1, I3(), BT(), IN());
         ktile(t + 2, I2(), BT(), IN());
         ktile(t + 3, I0(), BF(), IN());
     }
