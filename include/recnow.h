@@ -507,6 +507,29 @@ typedef struct recnow_gemm_desc {
 
 size_t recnow_gemm_workspace_bytes(const recnow_gemm_desc* desc_host);
 int recnow_gemm(const recnow_gemm_desc* desc_host, void* ws, size_t ws_bytes, void* stream);
+/* Which kernel recnow_gemm(desc_host, ws, ws_bytes, stream) launches, with a non-NULL ws when ws_bytes > 0: the ONE statement of that choice
+ * (recnow_gemm launches what the function behind it plans); host-only, nothing is launched and no pointer of the descriptor is dereferenced
+ * (addresses are read for their alignment).  It uses the process's precision, staging and environment switches and returns what recnow_gemm
+ * would return before its first launch; the fields are meaningful on RECNOW_OK (ABI 28).
+ *   family   0 nothing to launch (M, N or batch is 0), 1 k_gemm, 2 k_gemm_shortk (fp32), 3 k_gemm_shortk on piece planes (K = 144),
+ *            4 k_gemm_split, 5 k_gemm_s3
+ *   bm, bn, bk, a_kc, b_kc, edge, a2k, b2k, xf   family 1: the template arguments of k_gemm<BM, BN, WM, WN, BK, A_KC, B_KC, EDGE, A2K, B2K, XF>
+ *            (WM x WN waves: 2 x 2 for 128 x 128 and 64 x 128 tiles, else 4 x 1; A_KC: A stored [M][K]; B_KC: B stored [N][K]; the EDGE kernels
+ *            take the operand modes at run time: a2k = b2k = -1).  Families 4 and 5: a_kc, b_kc, a2k of k_gemm_split<A_KC, A2K, BP> /
+ *            k_gemm_s3<A_KC, A2K, PAIR>; bp: 0 B [K][N], 1 B [N][K], both split in the kernel, 2 B from piece planes; pair: paired A loads
+ *   ep, c2_mode   families 2 and 3: ep = (emul ? 1 : 0) | (accumulate ? 2 : 0) and the second-output form
+ *   planes   0 none; 1 B is split into piece planes in the workspace first (family 3: rn_split_planes at its base; 4, 5: k_split_planes behind
+ *            the slabs); 2 planes the caller holds (internal callers only: never from this query)
+ *   splitk, kchunk   K slices and their length (splitk > 1: slabs in the workspace and a reduction); grid_x, grid_y, grid_z: the product's grid
+ *            (family 2 / 3: the tile counts, the persistent kernel sizes its own grid); xcd_remap 0 / 1 / 2; tail_pairs: k pairs of the last
+ *            16-deep k-tile that k_valid leaves (8: all)
+ *   reduce_variant, reduce_blocks   splitk > 1: k_gemm_splitk_reduce<VEC, QUAD> 0 <false, false>, 1 <true, false>, 2 <true, true> and its grid
+ *   tag      the launch's recnow_prof tag (RN_TAG_GEMM_*, csrc/prof_tags.hpp): it names the kernel that runs */
+typedef struct recnow_gemm_route_info {
+    int32_t family, bm, bn, bk, a_kc, b_kc, edge, a2k, b2k, xf, bp, pair, ep, c2_mode, planes;
+    int32_t splitk, kchunk, grid_x, grid_y, grid_z, xcd_remap, tail_pairs, reduce_variant, reduce_blocks, tag;
+} recnow_gemm_route_info;
+int recnow_gemm_route(const recnow_gemm_desc* desc_host, size_t ws_bytes, recnow_gemm_route_info* out);
 /* Process-wide arithmetic of the long-K 128-column products with a side product (the K = 1024 / K = B products of DCNMixLayer):
  *   0 (default) exact fp32 MFMA -- an fp32 fma chain, what TF's fp32 matmul computes up to summation order;
  *   1 "bf16x3": every fp32 operand element split into three bf16 pieces, six bf16 MFMA terms per product, fp32 accumulation:

@@ -73,6 +73,7 @@ SIGNATURES = {
     'recnow_fm_bwd': (_I, [_P, _P, _I, _L, _I, _P, _P, _P]),
     'recnow_gemm_workspace_bytes': (_Z, [_P]),
     'recnow_gemm': (_I, [_P, _P, _Z, _P]),
+    'recnow_gemm_route': (_I, [_P, _Z, _P]),
     'recnow_set_gemm_precision': (_I, [_I]),
     'recnow_get_gemm_precision': (_I, []),
     'recnow_set_gemm_staging': (_I, [_I]),
@@ -212,7 +213,15 @@ class GemmDesc(ctypes.Structure):
         ('E4', _P), ('E5', _P), ('E6', _P),
     ]
 
-ABI_VERSION = 27 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+
+class GemmRouteInfo(ctypes.Structure):
+    """recnow_gemm_route_info of include/recnow.h: the planned route of a recnow_gemm call."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'family', 'bm', 'bn', 'bk', 'a_kc', 'b_kc', 'edge', 'a2k', 'b2k', 'xf', 'bp', 'pair', 'ep', 'c2_mode', 'planes',
+        'splitk', 'kchunk', 'grid_x', 'grid_y', 'grid_z', 'xcd_remap', 'tail_pairs', 'reduce_variant', 'reduce_blocks', 'tag')]
+
+
+ABI_VERSION = 28 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

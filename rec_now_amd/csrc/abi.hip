@@ -22,5 +22,6 @@
 // 24: recnow_approx_ndcg_fwdbwd / _workspace_bytes (in-batch ApproxNDCG on the pair-walk skeletons);
 // 25: recnow_bilinear_fwd / _bwd / _supported / _route / _workspace_bytes (BilinearInteractionLayer);
 // 26: recnow_autoint_fwd / _bwd / _supported / _route / _workspace_bytes (InteractingLayer);
-// 27: recnow_afm_fwd / _bwd / _supported / _route / _workspace_bytes (AFMLayer).
-extern "C" int recnow_abi_version(void) { return 27; }
+// 27: recnow_afm_fwd / _bwd / _supported / _route / _workspace_bytes (AFMLayer);
+// 28: recnow_gemm_route / recnow_gemm_route_info (the planned route of recnow_gemm, queryable).
+extern "C" int recnow_abi_version(void) { return 28; }

@@ -570,9 +570,9 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 d.sp_bx = gate_host[l]; d.sp_bx_ks = N; d.sp_bx_rs = 1; d.sp_cx = T1 + m.NS; d.sp_cx_ms = m.LDT; d.sp_cx_rs = 1; d.sp_r = N;
                 // a shard small enough for this product to be split over K: the sub-space kernel sums the slabs (and applies act_inner)
                 // on its way in -- no reduction launch
-                if (planes_on) rn_gemm_planes_hint(sv.plane(l, 0));
-                if (absorb) rc = rn_gemm_deferred(&d, w.gws, w.gws_bytes, st, &red1);
-                else rc = rn_gemm(&d, w.gws, w.gws_bytes, st);
+                const RnGemmOpts o{0, planes_on ? sv.plane(l, 0) : nullptr};
+                if (absorb) rc = rn_gemm_deferred(&d, w.gws, w.gws_bytes, st, &red1, o);
+                else rc = rn_gemm(&d, w.gws, w.gws_bytes, st, o);
                 if (rc) return rc;
             }
             RnSlabs sl;
@@ -598,8 +598,7 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                 d.M = (int)B; d.N = m.NS; d.K = D;
                 d.prof_flops = 2.0 * (double)B * D * m.KC;
                 d.sp_bx = sv.Wh() + (size_t)m.NS * D; d.sp_bx_ks = 1; d.sp_bx_rs = D; d.sp_cx = Q + m.NS; d.sp_cx_ms = m.LDT; d.sp_cx_rs = 1; d.sp_r = N;
-                rn_gemm_planes_hint(sv.plane(l, 2));
-                if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;      // (not deferred: Q is complete before it is read)
+                if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st, RnGemmOpts{0, sv.plane(l, 2)}))) return rc;      // (not deferred: Q is complete before it is read)
                 RnProfRecord* pr_rd = rn_prof_on() ? rn_prof_begin(RN_TAG_LAYER_END, 2.0 * (double)B * m.KC, 8.0 * (double)B * m.LDT, st) : nullptr;
                 hipLaunchKernelGGL(k_head_rowdot, rn_cdiv(B, 16), 256, 0, st, T2g, Q, head->b, B, m.KC, m.LDT, head->scores);
                 RN_LAUNCH_CHECK();
@@ -626,8 +625,7 @@ static int dcnmix_fwd_impl(const float* x, const float* const* U_host, const flo
                     d.C = sv.O(l);      // not written (c2_mode 3); a valid aligned address for the checks
                     d.hv = head->w; d.hp = hp; d.hp_ld = 2 * (D / 128);
                 }
-                if (planes_on) rn_gemm_planes_hint(sv.plane(l, 1));
-                if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st))) return rc;
+                if ((rc = rn_gemm(&d, w.gws, w.gws_bytes, st, RnGemmOpts{0, planes_on ? sv.plane(l, 1) : nullptr}))) return rc;
                 if (head && l == L - 1) {
                     hipLaunchKernelGGL(k_head_scores, ew_grid(B), 256, 0, st, hp, 2 * (D / 128), head->b, B, head->scores);
                     RN_LAUNCH_CHECK();
@@ -785,10 +783,7 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
     MIX_WAIT(e_chain, st2);
     int pg = rn_cdiv((int64_t)D * m.NS, 256);
     if (pg > 2048) pg = 2048;
-    struct SlotGuard {      // the dW / dU products of a layer run as a concurrent pair: each aims at half the workgroup slots (gemm_dispatch.hpp)
-        explicit SlotGuard(bool on) { if (on) rn_gemm_split_slots(256); }
-        ~SlotGuard() { rn_gemm_split_slots(0); }
-    } slot_guard(two);
+    const RnGemmOpts pair_opts{two ? 256 : 0, nullptr};      // the dW / dU products of a layer run as a concurrent pair: each aims at half the workgroup slots (gemm_dispatch.hpp)
     // Round 5.  The six K = B products behind the chain are independent of each other; what serialised them was the sharing of split-K slab
     // buffers (dW of every layer in one buffer: dW_l waited for the reduction of layer l + 1 on the second stream) and the reductions queued
     // between them.  Kernel trace of the 8192-row step: pairs at 378-427 us, then dU_1 ALONE, dW_1 + dU_0 at 477, dW_0 alone at 551, the last
@@ -837,7 +832,7 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
             d.M = D; d.N = m.NS; d.K = (int)B;
             d.prof_flops = 2.0 * (double)B * D * m.KC;
             d.sp_bx = d.B + m.NS; d.sp_bx_ks = m.LDT; d.sp_bx_rs = 1; d.sp_cx = dbias_host[l]; d.sp_cx_ms = 1; d.sp_cx_rs = D; d.sp_r = N;
-            if ((rc = rn_gemm_deferred(&d, w.slab[2 * l], w.slab_bytes, st2, &red_dw[l]))) return rc;
+            if ((rc = rn_gemm_deferred(&d, w.slab[2 * l], w.slab_bytes, st2, &red_dw[l], pair_opts))) return rc;
             MIX_SIGNAL(e_dw[l], st2);
         }
         {   // dWc1 = x_l^T dT1[:, :NS] -> dU;  dgate[d][n] = x_l^T dlogits as the side product
@@ -851,9 +846,9 @@ static int dcnmix_bwd_tile(const MixDims& m, const float* x, const float* const*
             d.sp_bx = dT1 + m.NS; d.sp_bx_ks = m.LDT; d.sp_bx_rs = 1; d.sp_cx = dgate_host[l]; d.sp_cx_ms = N; d.sp_cx_rs = 1; d.sp_r = N;
             recnow_gemm_desc dq = d;
             dq.C = dU_host[l]; dq.c_perm_s = S;
-            rc = rn_gemm_deferred(&dq, w.slab[2 * l + 1], w.slab_bytes, st, &red_du[l]);
+            rc = rn_gemm_deferred(&dq, w.slab[2 * l + 1], w.slab_bytes, st, &red_du[l], pair_opts);
             if (rc == RECNOW_EUNSUPPORTED) {       // no split: the product stores (D, N S) and is unpacked (dWc1 is reused in stream order)
-                if ((rc = rn_gemm(&d, w.slab[2 * l + 1], w.slab_bytes, st))) return rc;
+                if ((rc = rn_gemm(&d, w.slab[2 * l + 1], w.slab_bytes, st, pair_opts))) return rc;
                 hipLaunchKernelGGL(k_unpack_u, pg, 256, 0, st, w.dWc1, D, S, N, dU_host[l]);
                 RN_LAUNCH_CHECK();
             } else if (rc) {
@@ -1029,9 +1024,9 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
             }
             // split over K at small shards: the sub-space kernel sums the slabs on its way in (no reduction launch)
             // (split precision: the planes of W^T / W * w_head that the forward left; the head's variant only behind a forward that had the head)
-            if (planes_bwd && (l < L - 1 || ((hd != nullptr) == ((have & MIX_PLANES_HEAD) != 0)))) rn_gemm_planes_hint(sv.plane(l, 2));
-            if (absorb_bwd) rc = rn_gemm_deferred(&d, gws, gemm_ws, st, &red_t2g);
-            else rc = rn_gemm(&d, gws, gemm_ws, st);
+            const RnGemmOpts o{0, planes_bwd && (l < L - 1 || ((hd != nullptr) == ((have & MIX_PLANES_HEAD) != 0))) ? sv.plane(l, 2) : nullptr};
+            if (absorb_bwd) rc = rn_gemm_deferred(&d, gws, gemm_ws, st, &red_t2g, o);
+            else rc = rn_gemm(&d, gws, gemm_ws, st, o);
             if (rc) return rc;
         }
         RnSlabs sl_t2g;
@@ -1099,8 +1094,7 @@ static int dcnmix_bwd_exact(const MixDims& m, const float* x, const float* const
             }
             }
             if (!launched) {
-                if (planes_bwd) rn_gemm_planes_hint(sv.plane(l, 3));
-                if ((rc = rn_gemm(&d, gws, gemm_ws, st))) return rc;
+                if ((rc = rn_gemm(&d, gws, gemm_ws, st, RnGemmOpts{0, planes_bwd ? sv.plane(l, 3) : nullptr}))) return rc;
             }
         }
         if (l > 0) MIX_SIGNAL(e_g, st);

@@ -144,16 +144,9 @@ k_layer_end_reduce(const GemmK pa, int va, int na, const GemmK pb, int vb, int n
 }
 
 // ---- host dispatch -------------------------------------------------------------------------------------
-// (tile family, small-M rule and K split: gemm_dispatch.hpp, host-only so that it also builds under the CPU sanitizers)
-#include "gemm_dispatch.hpp"
+// The route of a launch is planned on the host (gemm_dispatch.hpp rn_gemm_plan: host-only, so that it also builds under the CPU sanitizers); what
+// follows reads the process's switches, fills the kernel arguments and launches what the plan names.
 #include "gemm_split.hpp"
-int rn_gemm_precision();
-static inline RnDispatchEnv dispatch_env() {
-    static const int bm64 = rn_env_int("RECNOW_GEMM_BM64", 256);        // A/B: 0 = off, N = tile bound
-    static const int kb = rn_env_int("RECNOW_GEMM_BM64_KB", -1);       // A/B: 0 = only to fill the chip, 1 = always
-    return RnDispatchEnv{bm64, kb, rn_gemm_precision()};
-}
-static inline GemmCfg pick_cfg(const recnow_gemm_desc* d) { return pick_cfg(d, dispatch_env()); }
 
 static std::atomic<int> g_gemm_staging{rn_env_int("RECNOW_GEMM_GLDS", 0) == 1 ? 1 : 0};      // recnow_set_gemm_staging
 static int g_gemm_precision = []() {
@@ -166,71 +159,27 @@ int rn_gemm_set_precision(int mode) {
     g_gemm_precision = mode;
     return RECNOW_OK;
 }
-
-// products whose B operand the split-precision kernel splits once per launch into global planes (weights: small, L2-resident)
-// (round 6: also the (K, 128) activation operand of the K = B weight-gradient products, [k][n] rows of ldb floats -- each of the eight row-tile
-// workgroups that read a k-tile of it split it again before)
-static inline bool split_planes_shape(const recnow_gemm_desc* d) {
-    static const bool kb = rn_env_int("RECNOW_SPLIT_LEAN", 0) == 2;      // A/B switch, see rn_gemm_launch_split
-    return d->sp_r > 0 && d->N == 128 && d->K % 16 == 0 && d->batch == 1 && ((!d->a_trans && d->K <= 4096) || (kb && d->a_trans && !d->b_trans));
+static inline RnDispatchEnv dispatch_env() {
+    static const int bm64 = rn_env_int("RECNOW_GEMM_BM64", 256);        // A/B: 0 = off, N = tile bound
+    static const int kb = rn_env_int("RECNOW_GEMM_BM64_KB", -1);       // A/B: 0 = only to fill the chip, 1 = always
+    static const int longk = rn_env_int("RECNOW_SPLIT_LONGK", 1), shortk = rn_env_int("RECNOW_SPLIT_SHORTK", 1);      // A/B switches (RnDispatchEnv)
+    static const int lean = rn_env_int("RECNOW_SPLIT_LEAN", 1), pair = rn_env_int("RECNOW_S3_PAIR", 1);
+    RnDispatchEnv e{bm64, kb, g_gemm_precision};
+    e.staging = g_gemm_staging.load(std::memory_order_relaxed);
+    e.split_longk = longk; e.split_shortk = shortk; e.split_lean = lean; e.s3_pair = pair;
+    return e;
 }
 
-// short-K products whose packed weights the split-precision short-K kernel splits into planes (K = 144: the ring schedule)
-static inline bool shortk_planes_shape(const recnow_gemm_desc* d) {
-    return d->K == 144 && d->N % 128 == 0 && d->M % 128 == 0 && d->batch == 1 && !d->a_trans && d->sp_r == 0 && d->eu_r == 0;
-}
-
-// workgroup slots the K split of the NEXT launches of this host thread aims at (0 = the default); see pick_split
-static thread_local int g_split_slots = 0;
-void rn_gemm_split_slots(int slots) { g_split_slots = slots; }
-
-size_t rn_gemm_ws_bytes(const recnow_gemm_desc* d) {
-    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return 0;
-    const GemmCfg c = pick_cfg(d);
-    size_t b = rnd_slab_bytes_any(d, c, 256);
-    if (split_planes_shape(d)) b += rn_gemm_split_planes_bytes(d->K, d->N);      // whatever the precision mode is when the product runs
-    if (shortk_planes_shape(d) && b < rn_gemm_shortk_planes_bytes(d->K, d->N)) b = rn_gemm_shortk_planes_bytes(d->K, d->N);
-    return b;
-}
-
-static inline bool host_aligned(const void* p, int64_t ld, int64_t sb) {
-    return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0) && (sb % 4 == 0);
-}
-// the lean (EDGE = false) kernel needs every tile in bounds and every float4 aligned
-static bool gemm_interior(const recnow_gemm_desc* d, const GemmCfg& c, int bk, int kchunk, bool split) {
-    if (d->M % c.BM || d->N % c.BN || d->K % bk || kchunk % bk) return false;
-    if ((int64_t)256 * d->lda >= (1ll << 30) || (int64_t)256 * d->ldb >= (1ll << 30)) return false;      // 32-bit byte offsets inside a tile
-    if (!host_aligned(d->A, d->lda, d->a_batch_stride) || !host_aligned(d->B, d->ldb, d->b_batch_stride)) return false;
-    if (d->a_mode == RECNOW_OPMODE_OUTER) { if (d->a_hq % 4) return false; }
-    else if (d->a_mode != RECNOW_OPMODE_NONE && !host_aligned(d->A2, d->lda, d->a_batch_stride)) return false;
-    if (d->b_mode == RECNOW_OPMODE_OUTER) { if (d->b_hq % 4) return false; }
-    else if (d->b_mode != RECNOW_OPMODE_NONE && !host_aligned(d->B2, d->ldb, d->b_batch_stride)) return false;
-    // the lean epilogue is float4 along the columns of C (the split-K slabs always qualify: N is a tile multiple)
-    if (!split) {
-        if (!d->c_trans && !host_aligned(d->C, d->ldc, d->c_batch_stride)) return false;
-        if (d->emul && !host_aligned(d->emul, d->lde, d->e_batch_stride)) return false;
-        if (d->bias && !host_aligned(d->bias, 4, d->bias_batch_stride)) return false;
-    }
-    return true;
-}
+size_t rn_gemm_ws_bytes(const recnow_gemm_desc* d) { return rnd_ws_bytes(d, dispatch_env()); }
+size_t rn_gemm_split_planes_bytes(int K, int N) { return rnd_planes_bytes(K, N); }
 
 static_assert(sizeof(GemmK) <= sizeof(((RnDeferredReduce*)nullptr)->k), "RnDeferredReduce::k holds a GemmK");
-static thread_local const void* tl_planes_hint = nullptr;
-void rn_gemm_planes_hint(const void* planes) { tl_planes_hint = planes; }
 
-static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* defer) {
-    const void* planes_ready = tl_planes_hint;      // (for THIS call only)
-    tl_planes_hint = nullptr;
-    if (defer) defer->valid = 0;
-    if (!d || d->M < 0 || d->N < 0 || d->K < 0 || d->batch < 0) return RECNOW_EINVAL;
-    if (d->M == 0 || d->N == 0 || d->batch == 0) return RECNOW_OK;
-    if (!d->A || !d->B || !d->C) return RECNOW_EINVAL;
-    if ((d->a_mode != RECNOW_OPMODE_NONE && !d->A2) || (d->b_mode != RECNOW_OPMODE_NONE && !d->B2)) return RECNOW_EINVAL;
-    if (d->K == 0) return RECNOW_EUNSUPPORTED;
-    GemmCfg c = pick_cfg(d);
+// the kernel arguments of a planned launch
+static GemmK gemm_args(const recnow_gemm_desc* d, const RnGemmPlan& p, void* ws) {
     GemmK k;
     k.A = d->A; k.A2 = d->a_mode ? d->A2 : nullptr; k.B = d->B; k.B2 = d->b_mode ? d->B2 : nullptr;
-    k.bias = d->bias; k.emul = d->emul; k.C = d->C; k.partial = nullptr;
+    k.bias = d->bias; k.emul = d->emul; k.C = d->C; k.partial = p.splitk > 1 ? (float*)ws : nullptr;
     k.lda = d->lda; k.ldb = d->ldb; k.ldc = d->ldc; k.lde = d->lde;
     k.sA = d->a_batch_stride; k.sB = d->b_batch_stride; k.sC = d->c_batch_stride;
     k.sBias = d->bias_batch_stride; k.sE = d->e_batch_stride;
@@ -243,86 +192,42 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
     k.sp_r = d->sp_r;
     k.eu_p = d->eu_p; k.eu_q = d->eu_q; k.eu_pms = d->eu_pms; k.eu_qrs = d->eu_qrs; k.eu_qns = d->eu_qns; k.eu_r = d->eu_r;
     k.npart = d->N + (d->sp_r > 0 ? 4 : 0);
-    if (d->sp_r < 0 || d->sp_r > 4 || d->eu_r < 0 || d->eu_r > 4 || (d->sp_r > 0 && d->eu_r > 0)) return RECNOW_EINVAL;
-    if (d->sp_r > 0 && (!d->sp_bx || !d->sp_cx || d->batch != 1)) return RECNOW_EINVAL;
-    if (d->eu_r > 0 && (!d->eu_p || !d->eu_q || d->batch != 1)) return RECNOW_EINVAL;
-    pick_split(d, c, &k.splitk, &k.kchunk, g_split_slots > 0 ? g_split_slots : 512);
-    k.perm_s = 0;
-    if (d->c_perm_s > 0) {
-        if (k.splitk <= 1) return RECNOW_EUNSUPPORTED;       // the permuted store lives in the split-K reduce
-        k.perm_s = d->c_perm_s;
-    }
+    k.splitk = p.splitk; k.kchunk = p.kchunk;
+    k.perm_s = d->c_perm_s > 0 ? d->c_perm_s : 0;       // the permuted store lives in the split-K reduce
     k.trace = nullptr;
-    k.tail_pairs = 8;
+    k.tail_pairs = p.tail_pairs;
     k.prio = 0;
     k.direct_store = 1;
-    if (d->c_perm_s < 0 || (d->c_perm_s > 0 && (d->N % d->c_perm_s || d->batch != 1 || d->c_trans || d->accumulate))) return RECNOW_EINVAL;
-    if (d->k_valid < 0 || d->k_valid > d->K) return RECNOW_EINVAL;
-    if (d->k_valid > 0 && d->K % 16 == 0 && d->k_valid > d->K - 16) k.tail_pairs = (d->k_valid - (d->K - 16) + 1) / 2;      // pairs of the last 16-deep tile
     k.C2 = d->C2; k.E2 = d->E2; k.ldc2 = d->ldc2; k.lde2 = d->lde2;
     k.as_in = d->as_in; k.as_out = d->as_out;
-    if ((d->as_in != nullptr) != (d->as_out != nullptr)) return RECNOW_EINVAL;
-    if (d->c2_mode < 0 || d->c2_mode > 6 || (d->c2_mode && d->c2_mode != 3 && d->c2_mode < 5 && !d->C2) || ((d->c2_mode == 2 || d->c2_mode >= 4) && !d->E2))
-        return RECNOW_EINVAL;
-    if (d->c2_mode >= 5) {      // the input gradient in one go: C = acc + E2 * E3 [+ E4 * E5] + rv (x) cv * E6
-        if (!d->E3 || !d->E6 || !d->rv || !d->cv || ((uintptr_t)d->cv & 15) || d->lde2 != d->lde3 || d->emul || d->accumulate || (d->c2_mode == 5 && (!d->E4 || !d->E5)))
-            return RECNOW_EINVAL;
-        if (!host_aligned(d->E2, d->lde2, 0) || !host_aligned(d->E3, d->lde2, 0) || !host_aligned(d->E6, d->lde2, 0) ||
-            (d->c2_mode == 5 && (!host_aligned(d->E4, d->lde2, 0) || !host_aligned(d->E5, d->lde2, 0))))
-            return RECNOW_EUNSUPPORTED;
-    }
     k.E4 = d->E4; k.E5 = d->E5; k.E6 = d->E6;
     k.A_hi = nullptr; k.planes_hi = nullptr;      // (rn_gemm_dx_once_split only)
-    if (d->c2_mode == 3 && (!d->hv || !d->hp || !d->emul || d->hp_ld < d->N / 64 || ((uintptr_t)d->hv & 15))) return RECNOW_EINVAL;
-    if (d->c2_mode == 4 && (!d->E3 || !d->rv || !d->cv || ((uintptr_t)d->cv & 15) || !host_aligned(d->E3, d->lde3, 0))) return RECNOW_EINVAL;
     k.E3 = d->E3; k.lde3 = d->lde3; k.rv = d->rv; k.cv = d->cv; k.hv = d->hv; k.hp = d->hp; k.hp_ld = d->hp_ld;
     k.mid_V = d->mid_V; k.mid_T1 = d->mid_T1; k.mid_T2 = d->mid_T2; k.mid_T2g = d->mid_T2g; k.mid_ld = d->mid_ld; k.mid_act_outer = d->mid_act_outer;
-    if (d->mid_V) {      // fused sub-space forward: the transposed GEMM1 of DCNMixLayer with two experts of 64 (see recnow_gemm_desc)
-        if (!d->mid_T1 || !d->mid_T2 || !d->mid_T2g || d->M != 128 || d->N % 128 || d->sp_r != 2 || !d->a_trans || !d->b_trans || d->a_mode ||
-            (d->b_mode != RECNOW_OPMODE_NONE && d->b_mode != RECNOW_OPMODE_MUL) ||
-            d->batch != 1 || d->bias || d->emul || d->accumulate || d->c_trans || d->mid_ld % 4 || d->mid_ld < 144 ||
-            (((uintptr_t)d->mid_T1 | (uintptr_t)d->mid_T2 | (uintptr_t)d->mid_T2g) & 15))
-            return RECNOW_EUNSUPPORTED;
-    }
-    if (d->c2_mode && (d->K > 512 || d->K % 16 || d->batch != 1)) return RECNOW_EUNSUPPORTED;      // short-K kernel only
 #ifdef RN_GEMM_TRACE
     if (const char* t = getenv("RECNOW_GEMM_TRACE")) k.trace = (long long*)strtoull(t, nullptr, 10);
 #endif
-    if (k.splitk > 1) {
-        const size_t need = rn_align((size_t)k.splitk * d->batch * d->M * k.npart * sizeof(float));
-        if (!ws || ws_bytes < need) return RECNOW_EWORKSPACE;
-        k.partial = (float*)ws;
-    }
-    const long long gz = (long long)d->batch * k.splitk;
-    if (gz > 65535) return RECNOW_EUNSUPPORTED;
-    dim3 grid(rn_cdiv(d->M, c.BM), rn_cdiv(d->N, c.BN), (unsigned)gz);
-    k.xcd_remap = (k.splitk > 1 && d->batch == 1 && grid.y == 1 && gz % 8 == 0 && grid.x > 1) ? 1 : 0;
-    if (!k.xcd_remap && grid.y > 1 && grid.x % 8 == 0 && d->sp_r == 0 && !d->as_out) k.xcd_remap = 2;
-    const bool a_kc = d->a_trans == 0, b_kc = d->b_trans != 0;
-    int rc;
-    int tag = (c.BM == 256 && c.BN == 32) ? RN_TAG_GEMM_256x32 : (c.BM == 256) ? RN_TAG_GEMM_256x64
-            : (c.BN == 160) ? RN_TAG_GEMM_128x160 : (c.BM == 64) ? RN_TAG_GEMM_64x128 : RN_TAG_GEMM_128x128;
-    // short-K products (K <= 256, e.g. the K = N*S+N = 130 contractions of DCN-v2) are prologue/epilogue dominated:
-    // BK = 16 halves the LDS footprint so 4 workgroups per CU overlap each other's load/store phases.
-    const bool short_k = d->K <= 256 || (d->c2_mode && d->K <= 512);
-    const bool bk16 = short_k && c.BM == 128;
-    const bool edge = !gemm_interior(d, c, bk16 ? 16 : 32, k.kchunk, k.splitk > 1);
-    // lean kernels exist for the two big tile families and the (layout, operand-kind) combos the layers use; anything
-    // else (and every edge shape) runs the general kernel of the same tile family.
-    rc = RECNOW_EUNSUPPORTED;
-    int xf = (d->sp_r > 0 ? 1 : 0) | (d->eu_r > 0 ? 2 : 0);
-    if (d->mid_V && (edge || k.splitk != 1 || c.BM != 128 || c.BN != 128 || short_k)) return RECNOW_EUNSUPPORTED;
-    // the persistent short-K kernel takes the plain products below (same condition as its branch)
-    const bool use_shortk = !xf && !d->as_out && !edge && bk16 && c.BN == 128 && a_kc && k.splitk == 1 && d->batch == 1 && d->a_mode == 0 &&
-                            d->b_mode == 0 && !d->bias && d->act == RECNOW_ACT_LINEAR && !d->c_trans &&
-                            (!d->emul || d->e_mode == RECNOW_OPMODE_MUL);
-    if (use_shortk) tag = RN_TAG_GEMM_SHORTK;
-    static const bool split_longk = rn_env_int("RECNOW_SPLIT_LONGK", 1) != 0;      // A/B switch (diagnostics: which family an error comes from)
-    const bool split_ok = g_gemm_precision == 1 && split_longk && xf == 1 && !d->as_out && !edge && !bk16 && c.BM == 128 && c.BN == 128 && d->b_mode == 0 &&
-                          (d->a_mode == RECNOW_OPMODE_NONE || d->a_mode == RECNOW_OPMODE_MUL) &&
-                          ((a_kc && !b_kc && (d->a_mode == 0 || planes_ready != nullptr)) || (a_kc && b_kc) || (!a_kc && !b_kc));      // (x0 * O_{l-1}) U: the lean kernel on the caller's planes only
-    if (split_ok) tag = RN_TAG_GEMM_SPLIT;
-    if (d->mid_V) tag = RN_TAG_GEMM_MIDF;      // a kernel of its own: the product's flops + the whole sub-space forward in one launch
+    k.xcd_remap = p.xcd_remap;
+    return k;
+}
+
+// the planned k_gemm instantiation: lean kernels for the (layout, operand-kind) combos the layers use, the general (EDGE) kernel of the same tile
+// family for anything else
+static int launch_kgemm(const GemmK& k, const RnGemmPlan& p, dim3 grid, hipStream_t st) {
+    if (p.edge) return rn_gemm_launch_edge(k, p.BM, p.BN, p.a_kc, p.b_kc, grid, st);
+    if (p.BM == 64) return rn_gemm_launch_lean64x(k, p.a_kc, p.b_kc, p.a2k, p.b2k, p.xf, grid, st);
+    if (p.BM == 256) return rn_gemm_launch_lean64(k, p.a_kc, p.b_kc, p.a2k, p.b2k, grid, st);
+    if (p.xf) return rn_gemm_launch_lean128x(k, p.a_kc, p.b_kc, p.BK, p.a2k, p.b2k, p.xf, grid, st);
+    return p.BN == 160 ? rn_gemm_launch_lean160(k, p.a_kc, p.b_kc, p.BK, p.a2k, p.b2k, grid, st)
+                       : rn_gemm_launch_lean128(k, p.a_kc, p.b_kc, p.BK, p.a2k, p.b2k, grid, st);
+}
+
+static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* defer, const RnGemmOpts& o) {
+    if (defer) defer->valid = 0;
+    RnGemmPlan p;
+    int rc = rn_gemm_plan(d, o, ws != nullptr, ws_bytes, dispatch_env(), &p);
+    if (rc || p.family == RN_GF_NONE) return rc;
+    const GemmK k = gemm_args(d, p, ws);
     RnProfRecord* pr = nullptr;
     if (rn_prof_on()) {
         // algorithmic HBM bytes: every operand read once, every output written once (read-modify-write outputs count twice)
@@ -331,92 +236,37 @@ static int rn_gemm_impl(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hi
                              mn * (1 + (d->emul ? 1 : 0) + (d->accumulate ? 1 : 0)) +
                              (d->c2_mode == 1 ? mn : d->c2_mode == 2 ? 3 * mn : d->c2_mode == 3 ? 0.0 : d->c2_mode == 4 ? 3 * mn : d->c2_mode == 5 ? 5 * mn : d->c2_mode == 6 ? 3 * mn : 0.0) +
                              (d->as_out ? 2 * mk : 0.0);
-        pr = rn_prof_begin(tag, d->prof_flops > 0.0 ? d->prof_flops : 2.0 * d->M * d->N * (double)d->K * d->batch, 4.0 * elems * d->batch, st);
+        pr = rn_prof_begin(p.tag, d->prof_flops > 0.0 ? d->prof_flops : 2.0 * d->M * d->N * (double)d->K * d->batch, 4.0 * elems * d->batch, st);
     }
-    if (d->as_out) {      // A-stream side output: instantiated with the side product of dT2g; written by the first column tile
-        if (xf != 1 || d->a_trans || d->a_mode != RECNOW_OPMODE_MUL || d->batch != 1 || k.splitk != 1 ||
-            !host_aligned(d->as_in, d->lda, 0) || !host_aligned(d->as_out, d->lda, 0))
-            return RECNOW_EUNSUPPORTED;
-        xf |= 4;
+    char* const planes = p.planes == 2 ? (char*)o.planes_ready : p.planes == 1 ? (char*)ws + p.planes_off : nullptr;
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    switch (p.family) {
+        case RN_GF_GEMM: rc = launch_kgemm(k, p, grid, st); break;
+        case RN_GF_SHORTK: rc = rn_gemm_launch_shortk(k, p.b_kc, p.ep, p.c2_mode, st); break;
+        case RN_GF_SHORTK_SPLIT: rc = rn_gemm_launch_shortk_split(k, p.b_kc, p.ep, p.c2_mode, planes, p.planes == 1, st); break;
+        default: rc = rn_gemm_launch_split(k, p, planes, grid, st); break;
     }
-    if (xf) {        // side product / rank-R update exist only in the lean 128x128 kernels: the caller guarantees the shape
-        if (edge || (c.BM != 128 && c.BM != 64) || c.BN != 128 || d->c2_mode) return RECNOW_EUNSUPPORTED;
-        rc = RECNOW_EUNSUPPORTED;
-        if (c.BM == 64) {        // small-M dispatch (pick_cfg): 64 x 128 tiles, two-wide side product, fp32 kernels only
-            if (xf != 1 || bk16) return RECNOW_EUNSUPPORTED;
-            rc = rn_gemm_launch_lean64x(k, a_kc, b_kc, d->a_mode, d->b_mode, 9, grid, st);
-            if (rc) return rc;
-        } else {
-        // opt-in split precision: the long-K products with a side product (every k_gemm launch of the DCN-v2 step)
-        if (split_ok) {
-            void* planes = nullptr;
-            if (split_planes_shape(d)) {
-                const size_t used = k.splitk > 1 ? rn_align((size_t)k.splitk * d->batch * d->M * k.npart * sizeof(float)) : 0;
-                if (ws && ws_bytes >= used + rn_gemm_split_planes_bytes(d->K, d->N)) planes = (char*)ws + used;
-            }
-            rc = rn_gemm_launch_split(k, a_kc, b_kc, d->a_mode, planes, grid, st, planes_ready);
-        }
-        if (d->mid_V) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, 32, 0, d->b_mode, 25, grid, st);      // XF 16 | 8 | 1: the fused sub-space forward
-        else if (rc == RECNOW_EUNSUPPORTED && xf == 1 && d->sp_r <= 2 && !bk16) {
-            const bool glds = g_gemm_staging.load(std::memory_order_relaxed) == 1;      // A/B switch: LDS-DMA operand staging (XF | 32)
-            if (glds && !a_kc && !b_kc && d->a_mode == 0 && d->b_mode == 0) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, 32, 0, 0, 41, grid, st);
-            if (rc == RECNOW_EUNSUPPORTED) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, 32, d->a_mode, d->b_mode, 9, grid, st);
-        }
-        if (!d->mid_V && rc == RECNOW_EUNSUPPORTED) rc = rn_gemm_launch_lean128x(k, a_kc, b_kc, bk16 ? 16 : 32, d->a_mode, d->b_mode, xf, grid, st);
-        if (rc) return rc;
-        }
-    } else if (use_shortk) {
-        // C = (A B) [* emul] [+ C] with a short K: persistent kernel, no per-tile prologue, pipelined epilogue (gemm_shortk.hip)
-        if (d->c2_mode && d->c2_mode < 5 && ((d->C2 && !host_aligned(d->C2, d->ldc2, 0)) || ((d->c2_mode == 2 || d->c2_mode == 4) && !host_aligned(d->E2, d->lde2, 0)))) return RECNOW_EUNSUPPORTED;
-        rc = RECNOW_EUNSUPPORTED;
-        static const bool sk_split = rn_env_int("RECNOW_SPLIT_SHORTK", 1) != 0;      // A/B switch
-        if (g_gemm_precision == 1 && sk_split && shortk_planes_shape(d) && (planes_ready || (ws && ws_bytes >= rn_gemm_shortk_planes_bytes(d->K, d->N))))
-            rc = rn_gemm_launch_shortk_split(k, b_kc, (d->emul ? 1 : 0) | (d->accumulate ? 2 : 0), d->c2_mode, ws, st, planes_ready);
-        if (rc == RECNOW_EUNSUPPORTED) rc = rn_gemm_launch_shortk(k, b_kc, (d->emul ? 1 : 0) | (d->accumulate ? 2 : 0), d->c2_mode, st);
-        if (rc) return rc;
-    } else if (d->c2_mode) {
-        return RECNOW_EUNSUPPORTED;          // the second output exists only in the short-K kernel
-    } else if (!edge && c.BM == 128) {
-        const int bk = bk16 ? 16 : 32;
-        rc = (c.BN == 160) ? rn_gemm_launch_lean160(k, a_kc, b_kc, bk, d->a_mode, d->b_mode, grid, st)
-                           : rn_gemm_launch_lean128(k, a_kc, b_kc, bk, d->a_mode, d->b_mode, grid, st);
-    }
-    if (!edge && c.BM == 256 && c.BN == 64) rc = rn_gemm_launch_lean64(k, a_kc, b_kc, d->a_mode, d->b_mode, grid, st);
-    if (rc == RECNOW_EUNSUPPORTED) rc = rn_gemm_launch_edge(k, c.BM, c.BN, a_kc, b_kc, grid, st);
     rn_prof_end(pr, st);
     if (rc) return rc;
-    if (k.splitk > 1) {
-        const int64_t total = (int64_t)d->M * k.npart * d->batch;
-        int g = rn_cdiv(total, 256);
-        if (g > 2048) g = 2048;
-        int variant = 0, blocks = g;
-        // four lanes per output (each a quarter of the slabs) only where one lane per output would leave the chip idle: with eight slabs in
-        // flight per lane the one-lane form reads faster from 96 workgroups on (c3 layer-end reduction: 19.3 vs 24.1 us)
-        if (d->N % 4 == 0 && k.splitk >= 16 && (total / 4) % 64 == 0 && rn_cdiv(total / 4, 256) < 96) {      // whole quads per wave: the shuffles need all four lanes in the loop
-            variant = 2;
-            blocks = rn_cdiv(total, 256) > 4096 ? 4096 : rn_cdiv(total, 256);
-        } else if (d->N % 4 == 0) {
-            variant = 1;
-            blocks = rn_cdiv(total / 4, 256) > 2048 ? 2048 : rn_cdiv(total / 4, 256);
-        }
+    if (p.splitk > 1) {
         if (defer) {             // the caller runs the reduction (rn_layer_end_reduce)
             memcpy(defer->k, &k, sizeof(GemmK));
-            defer->variant = variant;
-            defer->blocks = blocks;
+            defer->variant = p.reduce_variant;
+            defer->blocks = p.reduce_blocks;
             defer->valid = 1;
             return RECNOW_OK;
         }
-        if (variant == 2) hipLaunchKernelGGL((k_gemm_splitk_reduce<true, true>), blocks, 256, 0, st, k);
-        else if (variant == 1) hipLaunchKernelGGL((k_gemm_splitk_reduce<true, false>), blocks, 256, 0, st, k);
-        else hipLaunchKernelGGL((k_gemm_splitk_reduce<false, false>), blocks, 256, 0, st, k);
+        if (p.reduce_variant == 2) hipLaunchKernelGGL((k_gemm_splitk_reduce<true, true>), p.reduce_blocks, 256, 0, st, k);
+        else if (p.reduce_variant == 1) hipLaunchKernelGGL((k_gemm_splitk_reduce<true, false>), p.reduce_blocks, 256, 0, st, k);
+        else hipLaunchKernelGGL((k_gemm_splitk_reduce<false, false>), p.reduce_blocks, 256, 0, st, k);
         RN_LAUNCH_CHECK();
     }
     return RECNOW_OK;
 }
-int rn_gemm(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st) { return rn_gemm_impl(d, ws, ws_bytes, st, nullptr); }
-int rn_gemm_deferred(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* out) {
+int rn_gemm(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, const RnGemmOpts& o) { return rn_gemm_impl(d, ws, ws_bytes, st, nullptr, o); }
+int rn_gemm_deferred(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* out, const RnGemmOpts& o) {
     if (!out) return RECNOW_EINVAL;
-    return rn_gemm_impl(d, ws, ws_bytes, st, out);
+    return rn_gemm_impl(d, ws, ws_bytes, st, out, o);
 }
 // c2_mode 7 / 8 of the short-K kernel (gemm.hpp: RnDxOnce).  The caller owns the shape rules; what a wrong call could turn into an access out of
 // bounds or a misaligned 16-byte access is checked here.
@@ -424,8 +274,8 @@ int rn_gemm_dx_once_split(const RnDxOnce& q, hipStream_t st) {
     if (!q.A_lo || !q.A_hi || !q.planes_lo || !q.planes_hi || !q.E2 || !q.E3 || !q.C || (q.E4 != nullptr) != (q.E5 != nullptr)) return RECNOW_EINVAL;
     if (q.M <= 0 || q.N <= 0 || q.M % 128 || q.N % 128 || q.lda < 144 || q.ld < q.N || (int64_t)128 * q.lda >= (1ll << 29) || (int64_t)128 * q.ld >= (1ll << 29))
         return RECNOW_EUNSUPPORTED;
-    if (!host_aligned(q.A_lo, q.lda, 0) || !host_aligned(q.A_hi, q.lda, 0) || !host_aligned(q.C, q.ld, 0) || !host_aligned(q.E2, q.ld, 0) ||
-        !host_aligned(q.E3, q.ld, 0) || (q.E4 && (!host_aligned(q.E4, q.ld, 0) || !host_aligned(q.E5, q.ld, 0))) || ((uintptr_t)q.planes_lo & 15) ||
+    if (!rnd_aligned(q.A_lo, q.lda, 0) || !rnd_aligned(q.A_hi, q.lda, 0) || !rnd_aligned(q.C, q.ld, 0) || !rnd_aligned(q.E2, q.ld, 0) ||
+        !rnd_aligned(q.E3, q.ld, 0) || (q.E4 && (!rnd_aligned(q.E4, q.ld, 0) || !rnd_aligned(q.E5, q.ld, 0))) || ((uintptr_t)q.planes_lo & 15) ||
         ((uintptr_t)q.planes_hi & 15))
         return RECNOW_EUNSUPPORTED;
     GemmK k;
@@ -638,4 +488,12 @@ extern "C" size_t recnow_gemm_workspace_bytes(const recnow_gemm_desc* desc_host)
 }
 extern "C" int recnow_gemm(const recnow_gemm_desc* desc_host, void* ws, size_t ws_bytes, void* stream) {
     return rn_gemm(desc_host, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int recnow_gemm_route(const recnow_gemm_desc* desc_host, size_t ws_bytes, recnow_gemm_route_info* out) {
+    if (!out) return RECNOW_EINVAL;
+    RnGemmPlan p;
+    const int rc = rn_gemm_plan(desc_host, RnGemmOpts(), ws_bytes > 0, ws_bytes, dispatch_env(), &p);
+    *out = recnow_gemm_route_info{p.family, p.BM, p.BN, p.BK, p.a_kc, p.b_kc, p.edge, p.a2k, p.b2k, p.xf, p.bp, p.pair, p.ep, p.c2_mode, p.planes,
+                                  p.splitk, p.kchunk, p.grid_x, p.grid_y, p.grid_z, p.xcd_remap, p.tail_pairs, p.reduce_variant, p.reduce_blocks, p.tag};
+    return rc;
 }

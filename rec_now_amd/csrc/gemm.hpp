@@ -1,10 +1,12 @@
 // Internal interface of the exact-fp32 MFMA GEMM (gemm.hip).  The public C struct lives in include/recnow.h.
 #pragma once
 #include "common.hpp"
+#include "gemm_dispatch.hpp"
 #include <string.h>
 
 // C[b] = epilogue( opA(A[b]) * opB(B[b]) ), b = 0..batch-1, see recnow_gemm_desc in include/recnow.h
-int rn_gemm(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st);
+// `o` (gemm_dispatch.hpp): what the caller states about this one launch -- the K split's slot target, ready piece planes of B
+int rn_gemm(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, const RnGemmOpts& o = RnGemmOpts());
 size_t rn_gemm_ws_bytes(const recnow_gemm_desc* d);
 // A split-K product whose slab reduction is left to the caller: rn_gemm_deferred launches the product only and describes the
 // reduction; rn_layer_end_reduce then runs up to two such reductions and the dV partial sum of the sub-space backward kernel as ONE
@@ -16,9 +18,7 @@ struct RnDeferredReduce {
     int blocks;
     int valid;
 };
-int rn_gemm_deferred(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* out);
-// K-split target of the following launches of this host thread: workgroup slots to fill (0 = default 512); products launched as concurrent pairs ask for 256
-void rn_gemm_split_slots(int slots);
+int rn_gemm_deferred(const recnow_gemm_desc* d, void* ws, size_t ws_bytes, hipStream_t st, RnDeferredReduce* out, const RnGemmOpts& o = RnGemmOpts());
 // the slabs of a deferred (valid) product: slab s, row m, column c at partial[s * stride + m * ld + c]; side columns behind the N main ones
 void rn_deferred_slabs(const RnDeferredReduce* r, const float** partial, int* nsplit, int* ld, int64_t* stride);
 int rn_layer_end_reduce(const RnDeferredReduce* a, const RnDeferredReduce* b, const float* dv_part, int dv_nparts, int dv_total, float* dV,
@@ -34,9 +34,6 @@ struct RnSplitJob { const float* B; int64_t ldb; int b_kc, K, N; char* planes; }
 struct RnSplitJobs { RnSplitJob job[RN_SPLIT_MAX_JOBS]; int n; };
 int rn_split_planes_multi(const RnSplitJobs& jobs, hipStream_t st);
 size_t rn_gemm_split_planes_bytes(int K, int N);
-// The next rn_gemm / rn_gemm_deferred call of THIS host thread finds the piece planes of its B operand at `planes` (the layout and size its own
-// split would write) and skips that split; consumed (or dropped) by that one call.
-void rn_gemm_planes_hint(const void* planes);
 
 // The input gradient of a fused-head DCN-v2 step in one go, split precision only (c2_mode 7 / 8 of the short-K kernel, gemm_shortk.hip):
 //   C = [A_lo | A_hi] @ [B_lo ; B_hi] + E2 * E3 [+ E4 * E5]        (M x N; E4 == NULL: without the bracket)

@@ -12,12 +12,7 @@ int rn_gemm_launch_lean64x(const GemmK& k, bool a_kc, bool b_kc, int a2k, int b2
         RN_LAUNCH_CHECK();                                                                                           \
         return RECNOW_OK;                                                                                            \
     }
-    X(true, false, 0, 0, 9)     // GEMM1:  x_l [U | K]
-    X(true, false, 1, 0, 9)     //         (x0 * O_{l-1}) [U | K]: x_l formed in the operand load (dcnmix.hip mix_xless)
-    X(true, true, 1, 0, 9)      // dT2g:   (x * g) Wc2^T
-    X(true, true, 0, 0, 9)      // dT2g of the top layer under the fused head
-    X(false, false, 0, 0, 9)    // dU:     x_l^T dT1
-    X(false, false, 1, 0, 9)    // dW^T:   (x * g)^T T2g
+    RN_GEMM_LEAN64X_LIST(X)
 #undef X
-    return RECNOW_EUNSUPPORTED;
+    return RN_EINTERNAL;
 }

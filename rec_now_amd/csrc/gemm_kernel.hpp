@@ -1046,7 +1046,10 @@ k_gemm(const GemmK p) {
 }
 
 
-// launchers defined in gemm_inst_*.hip; each returns RECNOW_EUNSUPPORTED when it has no instantiation for the combo
+// Launchers of the planned kernel (gemm_dispatch.hpp rn_gemm_plan), defined in gemm_inst_*.hip, gemm_split.hip and gemm_shortk.hip.  The plan names only
+// combinations that the lists of gemm_inst_lists.hpp hold, so a launcher that is handed one it does not have returns RN_EINTERNAL: an error, never
+// a signal to try another kernel.
+#define RN_EINTERNAL (-99)
 int rn_gemm_launch_lean128(const GemmK& k, bool a_kc, bool b_kc, int bk, int a2k, int b2k, dim3 grid, hipStream_t st);
 int rn_gemm_launch_lean160(const GemmK& k, bool a_kc, bool b_kc, int bk, int a2k, int b2k, dim3 grid, hipStream_t st);
 int rn_gemm_launch_lean64(const GemmK& k, bool a_kc, bool b_kc, int a2k, int b2k, dim3 grid, hipStream_t st);
@@ -1059,11 +1062,11 @@ static inline void rn_gemm_launch_one(const GemmK& k, dim3 grid, hipStream_t st)
 }
 int rn_gemm_launch_lean128x(const GemmK& k, bool a_kc, bool b_kc, int bk, int a2k, int b2k, int xf, dim3 grid, hipStream_t st);
 int rn_gemm_launch_lean64x(const GemmK& k, bool a_kc, bool b_kc, int a2k, int b2k, int xf, dim3 grid, hipStream_t st);
-// split-precision (bf16x3) 128x128 kernel, k-tiles of 16 (gemm_split.hip)
-int rn_gemm_launch_split(const GemmK& k, bool a_kc, bool b_kc, int a2k, void* planes, dim3 grid, hipStream_t st, const void* ready = nullptr);
-size_t rn_gemm_split_planes_bytes(int K, int N);
-int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, void* planes, hipStream_t st, const void* ready = nullptr);
-size_t rn_gemm_shortk_planes_bytes(int K, int N);
+// split-precision (bf16x3) 128x128 kernels, k-tiles of 16 (gemm_split.hip): k_gemm_split or k_gemm_s3 as planned; `planes`: the piece planes of B
+// (plan.planes == 1: B is split into them first)
+int rn_gemm_launch_split(const GemmK& k, const RnGemmPlan& p, char* planes, dim3 grid, hipStream_t st);
+// ... of the short-K kernel (K = 144); split_first: the packed weights are split into `planes` first
+int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, char* planes, bool split_first, hipStream_t st);
 // K = 288 as two K = 144 halves (k.A / planes_lo, k.A_hi / k.planes_hi); c2_mode 7 / 8
 int rn_gemm_launch_shortk_split2(const GemmK& k, int c2_mode, const void* planes_lo, hipStream_t st);
 // persistent short-K kernel (gemm_shortk.hip): ep = (emul ? 1 : 0) | (accumulate ? 2 : 0)

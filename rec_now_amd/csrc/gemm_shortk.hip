@@ -508,33 +508,27 @@ static int launch_sk(const GemmK& k, hipStream_t st, const char* planes = nullpt
     return RECNOW_OK;
 }
 
-size_t rn_gemm_shortk_planes_bytes(int K, int N) { return rn_align((size_t)(K / 8) * N * 16 * 3); }
-
-// Split-precision forms of the six products of the DCN-v2 step (K = 144, ring schedule).  `planes`: rn_gemm_shortk_planes_bytes(K, N) bytes of
-// workspace; the packed weights are split into them first.  RECNOW_EUNSUPPORTED: the caller runs the fp32 kernel.
-int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, void* planes, hipStream_t st, const void* ready) {
-    if (k.K != 9 * SK_BK || (!planes && !ready) || (int64_t)128 * k.lda >= (1ll << 29)) return RECNOW_EUNSUPPORTED;
-    const bool fwd = !b_kc && ep == 1 && (c2_mode == 0 || c2_mode == 1 || c2_mode == 3);
-    const bool fwd0 = !b_kc && ep == 0 && c2_mode == 0;
-    const bool bwd = b_kc && ((ep == 2 && c2_mode == 0) || (ep == 0 && (c2_mode == 0 || c2_mode == 2 || c2_mode == 4 || c2_mode == 5 || c2_mode == 6)));
-    if (!fwd && !fwd0 && !bwd) return RECNOW_EUNSUPPORTED;
-    if (!ready) {       // (ready: the caller split the packed weights already, once per step)
+// Split-precision forms of the six products of the DCN-v2 step (K = 144, ring schedule), as planned (gemm_dispatch.hpp rnd_has_shortk_split).
+// `planes`: the piece planes of the packed weights; split_first: they are split into it here (rnd_planes_bytes(K, N) bytes of workspace).
+int rn_gemm_launch_shortk_split(const GemmK& k, bool b_kc, int ep, int c2_mode, char* planes, bool split_first, hipStream_t st) {
+    if (k.K != 9 * SK_BK || !planes || (int64_t)128 * k.lda >= (1ll << 29) || !rnd_has_shortk_split(b_kc, ep, c2_mode)) return RN_EINTERNAL;
+    const bool fwd = !b_kc && ep == 1, fwd0 = !b_kc && ep == 0;
+    if (split_first) {       // (else the caller split the packed weights already, once per step)
         int rc = rn_split_planes(k.B, k.ldb, b_kc ? 1 : 0, k.K, k.N, planes, st);
         if (rc) return rc;
     }
-    const char* pl = ready ? (const char*)ready : (const char*)planes;
     if (fwd) {      // (no whole-tile prefetch of emul: its 64 registers are the fragments' here)
-        if (c2_mode == 1) return launch_sk<false, 1, 1, false, 9, true>(k, st, pl);
-        if (c2_mode == 3) return launch_sk<false, 1, 3, false, 9, true>(k, st, pl);
-        return launch_sk<false, 1, 0, false, 9, true>(k, st, pl);
+        if (c2_mode == 1) return launch_sk<false, 1, 1, false, 9, true>(k, st, planes);
+        if (c2_mode == 3) return launch_sk<false, 1, 3, false, 9, true>(k, st, planes);
+        return launch_sk<false, 1, 0, false, 9, true>(k, st, planes);
     }
-    if (fwd0) return launch_sk<false, 0, 0, false, 9, true>(k, st, pl);
-    if (ep == 2) return launch_sk<true, 2, 0, false, 9, true>(k, st, pl);
-    if (c2_mode == 2) return launch_sk<true, 0, 2, false, 9, true>(k, st, pl);
-    if (c2_mode == 4) return launch_sk<true, 0, 4, false, 9, true>(k, st, pl);
-    if (c2_mode == 5) return launch_sk<true, 0, 5, false, 9, true>(k, st, pl);
-    if (c2_mode == 6) return launch_sk<true, 0, 6, false, 9, true>(k, st, pl);
-    return launch_sk<true, 0, 0, false, 9, true>(k, st, pl);
+    if (fwd0) return launch_sk<false, 0, 0, false, 9, true>(k, st, planes);
+    if (ep == 2) return launch_sk<true, 2, 0, false, 9, true>(k, st, planes);
+    if (c2_mode == 2) return launch_sk<true, 0, 2, false, 9, true>(k, st, planes);
+    if (c2_mode == 4) return launch_sk<true, 0, 4, false, 9, true>(k, st, planes);
+    if (c2_mode == 5) return launch_sk<true, 0, 5, false, 9, true>(k, st, planes);
+    if (c2_mode == 6) return launch_sk<true, 0, 6, false, 9, true>(k, st, planes);
+    return launch_sk<true, 0, 0, false, 9, true>(k, st, planes);
 }
 
 int rn_gemm_launch_shortk_split2(const GemmK& k, int c2_mode, const void* planes_lo, hipStream_t st) {
@@ -546,7 +540,8 @@ int rn_gemm_launch_shortk_split2(const GemmK& k, int c2_mode, const void* planes
 
 // ep: bit 0 = multiply by emul, bit 1 = accumulate into C.  c2_mode: second output (recnow_gemm_desc).  The caller
 // guarantees: M, N multiples of 128, K a multiple of 16, A k-contiguous, every operand 16-byte aligned, batch == 1, no
-// bias / activation / transposed store.  Second outputs are instantiated for the two products DCN-v2 uses them in.
+// bias / activation / transposed store.  Second outputs are instantiated for the two products DCN-v2 uses them in (gemm_dispatch.hpp
+// rnd_has_shortk states which forms exist; the plan asks for no other).
 int rn_gemm_launch_shortk(const GemmK& k, bool b_kc, int ep, int c2_mode, hipStream_t st) {
     // nine k-tiles (DCN-v2: K = N*S + N = 130 stored as 144): the ring schedule
     if (k.K == 9 * SK_BK && !b_kc && ep == 1) {
@@ -563,15 +558,15 @@ int rn_gemm_launch_shortk(const GemmK& k, bool b_kc, int ep, int c2_mode, hipStr
         if (c2_mode == 6) return launch_sk<true, 0, 6, false, 9>(k, st);
         if (c2_mode == 0) return launch_sk<true, 0, 0, false, 9>(k, st);      // g_l alone (the input gradient is accumulated once, c2_mode 5 / 6)
     }
-    if (c2_mode >= 5) return RECNOW_EUNSUPPORTED;
+    if (c2_mode >= 5) return RN_EINTERNAL;
     if (!b_kc && ep == 1) {
         if (c2_mode == 1) return launch_sk<false, 1, 1, true>(k, st);
         if (c2_mode == 3) return launch_sk<false, 1, 3, true>(k, st);
         if (c2_mode == 0) return launch_sk<false, 1, 0, true>(k, st);
     }
-    if (c2_mode == 2) return (b_kc && ep == 0) ? launch_sk<true, 0, 2>(k, st) : RECNOW_EUNSUPPORTED;
-    if (c2_mode == 4) return (b_kc && ep == 0) ? launch_sk<true, 0, 4>(k, st) : RECNOW_EUNSUPPORTED;
-    if (c2_mode) return RECNOW_EUNSUPPORTED;      // c2_mode 1 / 3: the EP == 1 forward above only
+    if (c2_mode == 2) return (b_kc && ep == 0) ? launch_sk<true, 0, 2>(k, st) : RN_EINTERNAL;
+    if (c2_mode == 4) return (b_kc && ep == 0) ? launch_sk<true, 0, 4>(k, st) : RN_EINTERNAL;
+    if (c2_mode) return RN_EINTERNAL;      // c2_mode 1 / 3: the EP == 1 forward above only
     if (b_kc) {
         switch (ep) {
             case 0: return launch_sk<true, 0, 0>(k, st);
@@ -584,6 +579,6 @@ int rn_gemm_launch_shortk(const GemmK& k, bool b_kc, int ep, int c2_mode, hipStr
         case 0: return launch_sk<false, 0, 0>(k, st);
         case 2: return launch_sk<false, 2, 0>(k, st);
         case 3: return launch_sk<false, 3, 0>(k, st);
-        default: return RECNOW_EUNSUPPORTED;      // (EP == 1: the prefetching kernel above)
+        default: return RN_EINTERNAL;      // (EP == 1: the prefetching kernel above)
     }
 }

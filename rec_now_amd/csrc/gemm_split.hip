@@ -624,80 +624,43 @@ k_gemm_s3(const GemmK p, const char* __restrict__ b_planes, int64_t b_plane_byte
     gemm_lean_epilogue<2, 2, 0>(p, acc, smem, m0, 0, wm, wn, lane, wave, z, 0);
 }
 
-size_t rn_gemm_split_planes_bytes(int K, int N) { return rn_align((size_t)(K / 8) * N * 16 * 3); }
-
-// Launcher: the (layout, operand kind) combinations of the DCN-v2 step, N = 128 (one column tile: the side product belongs to
-// it).  `planes` != NULL: B is split once into planes there (rn_gemm_split_planes_bytes(K, N) bytes) before the product.
-// RECNOW_EUNSUPPORTED -> the caller runs the fp32 kernel.
-// Lean form (round 6): N = 128, at most two side columns, whole k-chunks of an even number of k-tiles, the chunk's side weights in LDS.
-static bool s3_shape(const GemmK& k, int a2k) {
-    return k.batch == 1 && k.N == 128 && k.sp_r >= 1 && k.sp_r <= 2 && k.kchunk % (2 * SPL_BK) == 0 && k.K % k.kchunk == 0 && k.kchunk <= S3_BX_MAXK &&
-           (a2k == RECNOW_OPMODE_NONE || a2k == RECNOW_OPMODE_MUL) && !k.as_out;
-}
 // a chunk of 2048 k needs 66 KB of dynamic LDS: more than the default limit of 64 KB
-template <bool A_KC, int A2K>
+static_assert(S3_BX_MAXK == RND_S3_MAXK && SPL_BK == RND_SPL_BK, "gemm_dispatch.hpp plans with these");
+template <bool A_KC, int A2K, bool PAIR>
 static int s3_launch(const GemmK& k, const char* planes, int64_t pb, dim3 grid, hipStream_t st) {
     const size_t lds = S3_LDS(k.kchunk);
-    // paired A loads (see the kernel): k-contiguous operands, whole groups of four k-tiles, rows that start on a 128-byte line; RECNOW_S3_PAIR=0: A/B switch
-    static const bool pair_on = rn_env_int("RECNOW_S3_PAIR", 1) != 0;
-    if constexpr (A_KC) {
-        if (pair_on && k.kchunk % (4 * SPL_BK) == 0 && k.lda % 32 == 0 && ((uintptr_t)k.A & 127) == 0 && (A2K == RECNOW_OPMODE_NONE || ((uintptr_t)k.A2 & 127) == 0)) {
-            if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_gemm_s3<A_KC, A2K, true>, S3_LDS(S3_BX_MAXK)));
-            hipLaunchKernelGGL((k_gemm_s3<A_KC, A2K, true>), grid, GEMM_THREADS, lds, st, k, planes, pb);
-            RN_LAUNCH_CHECK();
-            return RECNOW_OK;
-        }
-    }
-    if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_gemm_s3<A_KC, A2K>, S3_LDS(S3_BX_MAXK)));
-    hipLaunchKernelGGL((k_gemm_s3<A_KC, A2K>), grid, GEMM_THREADS, lds, st, k, planes, pb);
+    if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_gemm_s3<A_KC, A2K, PAIR>, S3_LDS(S3_BX_MAXK)));
+    hipLaunchKernelGGL((k_gemm_s3<A_KC, A2K, PAIR>), grid, GEMM_THREADS, lds, st, k, planes, pb);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
 }
+template <int A2K>
+static int s3_pick(const GemmK& k, const RnGemmPlan& p, const char* planes, int64_t pb, dim3 grid, hipStream_t st) {
+    if (!p.a_kc) return p.pair ? RN_EINTERNAL : s3_launch<false, A2K, false>(k, planes, pb, grid, st);      // (paired A loads: k-contiguous A only)
+    return p.pair ? s3_launch<true, A2K, true>(k, planes, pb, grid, st) : s3_launch<true, A2K, false>(k, planes, pb, grid, st);
+}
 
-// Launcher: the (layout, operand kind) combinations of the DCN-v2 step, N = 128 (one column tile: the side product belongs to
-// it).  `planes` != NULL: B is split once into planes there (rn_gemm_split_planes_bytes(K, N) bytes) before the product.
-// RECNOW_EUNSUPPORTED -> the caller runs the fp32 kernel.
-int rn_gemm_launch_split(const GemmK& k, bool a_kc, bool b_kc, int a2k, void* planes, dim3 grid, hipStream_t st, const void* ready) {
-    if (grid.y != 1 || k.K % SPL_BK || k.kchunk % SPL_BK || k.sp_r <= 0) return RECNOW_EUNSUPPORTED;
-    // element offsets inside a tile are 32-bit
-    if ((int64_t)128 * k.lda >= (1ll << 31) || (int64_t)128 * k.ldb >= (1ll << 31)) return RECNOW_EUNSUPPORTED;
+// Launcher of the planned split-precision kernel (gemm_dispatch.hpp rnd_plan_split): the (layout, operand kind) combinations of the DCN-v2 step,
+// N = 128.  p.planes == 1: B is split once into `planes` (rn_gemm_split_planes_bytes(K, N) bytes) before the product.
+int rn_gemm_launch_split(const GemmK& k, const RnGemmPlan& p, char* planes, dim3 grid, hipStream_t st) {
     const int64_t pb = (int64_t)(k.K / 8) * k.N * 16;
-    static const bool s3_on = rn_env_int("RECNOW_SPLIT_LEAN", 1) != 0;      // A/B switch: 0 = k_gemm_split of rounds 2-5
-    // [k][row] operands (the K = B weight-gradient products) with a pre-split activation operand: built and measured in the step -- 103 / 130 us
-    // (A / A * A2) + 18 us for the split of the (B, 128) operand against 111 / 126 us for k_gemm_split, which splits B in every workgroup: the
-    // pre-pass costs what the leaner loop gains, so these products stay on k_gemm_split (RECNOW_SPLIT_LEAN=2 routes them here: A/B switch)
-    static const bool s3_kb = rn_env_int("RECNOW_SPLIT_LEAN", 0) == 2;
-    // ready != NULL: the caller holds the planes of this product's B already (the packed weights of a step are split once, dcnmix.hip)
-    if (ready && s3_on && s3_shape(k, a2k) && a_kc)
-        return a2k == 0 ? s3_launch<true, 0>(k, (const char*)ready, pb, grid, st) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)ready, pb, grid, st);
-    if (planes && s3_on && s3_shape(k, a2k) && (a_kc || (!b_kc && s3_kb))) {
+    if (p.planes == 1) {
         const int64_t units = (int64_t)(k.K / 8) * k.N;
-        hipLaunchKernelGGL(k_split_planes, (unsigned)((units + 255) / 256), 256, 0, st, k.B, k.ldb, b_kc ? 1 : 0, k.K, k.N, (char*)planes);
+        hipLaunchKernelGGL(k_split_planes, (unsigned)((units + 255) / 256), 256, 0, st, k.B, k.ldb, p.b_kc ? 1 : 0, k.K, k.N, planes);
         RN_LAUNCH_CHECK();
-        if (a_kc) return a2k == 0 ? s3_launch<true, 0>(k, (const char*)planes, pb, grid, st) : s3_launch<true, RECNOW_OPMODE_MUL>(k, (const char*)planes, pb, grid, st);
-        return a2k == 0 ? s3_launch<false, 0>(k, (const char*)planes, pb, grid, st) : s3_launch<false, RECNOW_OPMODE_MUL>(k, (const char*)planes, pb, grid, st);
     }
-    if (planes && k.batch == 1 && a_kc && k.K <= 4096) {
-        const int64_t units = (int64_t)(k.K / 8) * k.N;
-        hipLaunchKernelGGL(k_split_planes, (unsigned)((units + 255) / 256), 256, 0, st, k.B, k.ldb, b_kc ? 1 : 0, k.K, k.N, (char*)planes);
-        RN_LAUNCH_CHECK();
-        if (a2k == 0) hipLaunchKernelGGL((k_gemm_split<true, 0, 2>), grid, GEMM_THREADS, SPL_LDS, st, k, (const char*)planes, pb);
-        else if (a2k == 1) hipLaunchKernelGGL((k_gemm_split<true, 1, 2>), grid, GEMM_THREADS, SPL_LDS, st, k, (const char*)planes, pb);
-        else return RECNOW_EUNSUPPORTED;
-        RN_LAUNCH_CHECK();
-        return RECNOW_OK;
+    if (p.family == RN_GF_S3) {
+        if (!planes || (p.a2k != 0 && p.a2k != RECNOW_OPMODE_MUL)) return RN_EINTERNAL;
+        return p.a2k == 0 ? s3_pick<0>(k, p, planes, pb, grid, st) : s3_pick<RECNOW_OPMODE_MUL>(k, p, planes, pb, grid, st);
     }
-#define X(AKC, BKC, A2)                                                                                               \
-    if (a_kc == AKC && b_kc == BKC && a2k == A2) {                                                                    \
-        hipLaunchKernelGGL((k_gemm_split<AKC, A2, BKC ? 1 : 0>), grid, GEMM_THREADS, SPL_LDS, st, k, (const char*)nullptr, (int64_t)0);  \
+    if ((p.bp == 2) != (planes != nullptr)) return RN_EINTERNAL;
+#define X(AKC, A2, BP)                                                                                                \
+    if ((p.a_kc != 0) == AKC && p.a2k == A2 && p.bp == BP) {                                                          \
+        hipLaunchKernelGGL((k_gemm_split<AKC, A2, BP>), grid, GEMM_THREADS, SPL_LDS, st, k, (const char*)planes, BP == 2 ? pb : (int64_t)0);  \
         RN_LAUNCH_CHECK();                                                                                            \
         return RECNOW_OK;                                                                                             \
     }
-    X(true, false, 0)      // GEMM1:  x_l U
-    X(true, true, 1)       // dT2g:   (x*g) W^T
-    X(true, true, 0)       // dT2g of the top layer under a fused scoring head
-    X(false, false, 0)     // dU:     x_l^T dA
-    X(false, false, 1)     // dW^T:   (x*g)^T T2g
+    RN_GEMM_SPLIT_LIST(X)
 #undef X
-    return RECNOW_EUNSUPPORTED;
+    return RN_EINTERNAL;
 }

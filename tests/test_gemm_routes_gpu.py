@@ -9,7 +9,8 @@ One row per k_gemm instantiation of csrc/gemm_inst_*.hip and per split-K reduce 
      output is bit-identical to the clean census run;
   4. random data: |C - R|_ij <= C_ELEM (|A'||B'|)_ij plus the ulps of the epilogue terms, side product included, and the norm bound of
      test_gemm_fuzz;
-  5. tile family: the launch's recnow_prof tag is the row's family (never the short-K kernel's);
+  5. route and tile family: recnow_gemm_route names the row's kernel (tests/_gemm_routes.py check_route) for the very descriptor and workspace size
+     being launched, and the launch's recnow_prof tag is the row's family (never the short-K kernel's);
   6. TANH / SIGMOID epilogues on the census pre-activations stay within rn_act's documented error, and every route maps the same pre-activation to
      the same bits (test_act_routes_agree).
 Left out: XF 25, the fused sub-space forward (tests/test_midf_gpu.py reaches it through the layer oracle); the split-precision and the short-K
@@ -23,6 +24,7 @@ import pytest
 import torch
 
 import _exact_census as E
+import _gemm_routes as R
 from _gemm_routes import ROUTES, TAG_SHORTK
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +35,6 @@ pytestmark = pytest.mark.gpu
 # 1e-6 is 2.4x their sum
 C_ELEM = 1e-6
 U = 2.0 ** -23                    # one rounding of an epilogue term, with a factor 2 of margin
-PAD_ROWS = 256                    # a full tile of rows of guard band before and after every buffer
 SENT = 0x7FC0DEAD                 # sentinel word of the output buffers (a NaN no kernel computes)
 TANH_ABS = 1.5e-7                 # rn_tanh for |x| >= 0.25 (csrc/common.hpp: "about 2e-7 absolute"; test_act_sweep measured 1.27e-7)
 ACT_REL = 2.0 ** -21              # rn_tanh's odd series below 0.25 and rn_act's SIGMOID 1 / (1 + expf(-x)): 4 ulp relative
@@ -42,27 +43,22 @@ TINY = 2.0 ** -126                # sigmoid below -87.3 (subnormal results, expf
 ACT_SEEN = {}                     # (act, z bits) -> (output bits, route): the activated census outputs of every route
 
 
-def _ceil4(n):
-    return (n + 3) // 4 * 4
-
-
 class Buf:
-    """A (batch, rows, cols) matrix inside a guard-banded flat device buffer: leading dimension ld, batch stride (rows + 1) * ld, PAD_ROWS rows of
-    `fill` before and after, the first element `off` floats into the buffer's lines."""
+    """The matrix of a Geo (tests/_gemm_routes.py) inside its guard-banded flat device buffer, filled with `fill` around the stored `data`."""
 
-    def __init__(self, dev, nb, rows, cols, ld, off=0, fill=float('nan'), data=None, rep=(1, 1)):
-        self.ld, self.sb, self.pre = ld, (rows + 1) * ld, PAD_ROWS * ld + off
-        self.buf = torch.full((self.pre + nb * self.sb + PAD_ROWS * ld + 64,), fill, dtype=torch.float32, device=dev)
-        self.view = self.buf[self.pre:self.pre + nb * self.sb].view(nb, rows + 1, ld)[:, :rows, :cols]
+    def __init__(self, dev, geo, fill=float('nan'), data=None):
+        g = self.geo = geo
+        self.buf = torch.full((g.words,), fill, dtype=torch.float32, device=dev)
+        self.view = self.buf[g.pre:g.pre + g.nb * g.sb].view(g.nb, g.rows + 1, g.ld)[:, :g.rows, :g.cols]
         if data is not None:
-            self.view.copy_(torch.from_numpy(np.ascontiguousarray(data)).to(dev).repeat(1, rep[0], rep[1]))
-        self.ptr = self.buf.data_ptr() + 4 * self.pre
+            self.view.copy_(torch.from_numpy(np.ascontiguousarray(data)).to(dev).repeat(1, g.rep[0], g.rep[1]))
 
     def intact(self):
         """every word outside the logical matrix still holds the sentinel"""
+        g = self.geo
         bits = self.buf.view(torch.int32)
         outside = torch.ones_like(bits, dtype=torch.bool)
-        outside[self.pre:self.pre + self.view.shape[0] * self.sb].view(self.view.shape[0], -1, self.ld)[:, :self.view.shape[1], :self.view.shape[2]] = False
+        outside[g.pre:g.pre + g.nb * g.sb].view(g.nb, -1, g.ld)[:, :g.rows, :g.cols] = False
         return int(((bits != SENT) & outside).sum())
 
     def get(self):
@@ -73,94 +69,38 @@ def _sent_float():
     return float(np.array([SENT], np.uint32).view(np.float32)[0])
 
 
-def run(dev, spec, extra, st, act=E.LINEAR, prof=False):
+def run(dev, spec, extra, st, act=E.LINEAR, prof=False, route=None):
     """One recnow_gemm of `spec` on the stored operands `st` (census or random; arrays of the census's shapes).  Returns (C (batch, M, N),
-    Cx, as_out, tags) and checks every sentinel."""
+    Cx, as_out, tags) and checks every sentinel.  route = (name, kernel): recnow_gemm_route names the row's kernel for the very descriptor and
+    workspace size of the launch."""
     from rec_now_amd import _lib
     lib = _lib.load()
     s = spec
-    M, N, K, nb = s['M'], s['N'], s['K'], s['batch']
-    mt, nt = extra.get('tile', (1, 1))
-    off = extra.get('off', 0)
-    d = _lib.GemmDesc()
-    keep = []
-
-    def operand(side, key_ld):
-        first, second = st[side], st.get(side + '2')
-        rows, cols = first.shape[1], first.shape[2]
-        rep = ((mt, 1) if side == 'A' else (1, nt)) if (mt, nt) != (1, 1) else (1, 1)
-        ld = _ceil4(cols * rep[1]) + 4 + (1 if (off and side == 'A') else 0)
-        b = Buf(dev, first.shape[0], rows * rep[0], cols * rep[1], ld, off=off if side == 'A' else 0, data=first, rep=rep)
-        keep.append(b)
-        mode = s['a_mode'] if side == 'A' else s['b_mode']
-        p2, ld2 = 0, 0
-        if mode:
-            if mode == E.OUTER:
-                ld2 = _ceil4(second.shape[2]) + 4
-                b2 = Buf(dev, 1, second.shape[1], second.shape[2], ld2, data=second)
-            else:
-                b2 = Buf(dev, second.shape[0], rows * rep[0], cols * rep[1], ld, off=off if side == 'A' else 0, data=second, rep=rep)
-            keep.append(b2)
-            p2 = b2.ptr
-        return b, p2, ld2
-    a, a2p, ald2 = operand('A', 'lda')
-    bb, b2p, bld2 = operand('B', 'ldb')
-    d.A, d.lda, d.a_batch_stride, d.a_trans, d.a_mode, d.a_act = a.ptr, a.ld, a.sb, s['ta'], s['a_mode'], s['a_act']
-    d.B, d.ldb, d.b_batch_stride, d.b_trans, d.b_mode, d.b_act = bb.ptr, bb.ld, bb.sb, s['tb'], s['b_mode'], s['b_act']
-    if s['a_mode']:
-        d.A2 = a2p
-    if s['b_mode']:
-        d.B2 = b2p
-    if s['a_mode'] == E.OUTER:
-        d.a_hq, d.a_ld2 = s['a_hq'], ald2
-    if s['b_mode'] == E.OUTER:
-        d.b_hq, d.b_ld2 = s['b_hq'], bld2
-    d.M, d.N, d.K, d.batch = M, N, K, nb
-    sent = _sent_float()
+    M, N = s['M'], s['N']
     perm = extra.get('perm', 0)
-    if perm:
-        c = Buf(dev, 1, M * N // 128, 128, 128, fill=sent)
-    elif s['c_trans']:
-        c = Buf(dev, nb, N, M, _ceil4(M) + 4, fill=sent, data=st['C0'].transpose(0, 2, 1) if s['accumulate'] else None)
-    else:
-        c = Buf(dev, nb, M, N, _ceil4(N) + 4, fill=sent, data=st['C0'] if s['accumulate'] else None, rep=(mt, nt))
-    outs = [c]
-    d.C, d.ldc, d.c_batch_stride, d.c_trans, d.accumulate, d.c_perm_s = c.ptr, c.ld, c.sb, s['c_trans'], s['accumulate'], perm
-    if s['bias']:
-        bi = Buf(dev, nb, 1, N, _ceil4(N) + 4, data=st['bias'])
-        keep.append(bi)
-        d.bias, d.bias_batch_stride = bi.ptr, bi.sb
-    if s['e_mode']:
-        e = Buf(dev, nb, M, N, _ceil4(N) + 4, data=st['E'], rep=(mt, nt))
-        keep.append(e)
-        d.emul, d.lde, d.e_batch_stride, d.e_mode, d.e_act = e.ptr, e.ld, e.sb, s['e_mode'], s['e_act']
-    d.act, d.act_cols, d.k_valid = act, s['act_cols'], s['k_valid']
-    cx = aso = None
-    if s['sp_r']:
-        R = s['sp_r']
-        bx = Buf(dev, 1, K, R, R + 4, data=st['Bx'])
-        cx = Buf(dev, 1, M, R, R + 4, fill=sent)
-        keep.append(bx)
-        outs.append(cx)
-        d.sp_bx, d.sp_cx, d.sp_bx_ks, d.sp_bx_rs, d.sp_cx_ms, d.sp_cx_rs, d.sp_r = bx.ptr, cx.ptr, bx.ld, 1, cx.ld, 1, R
-    if s['eu_r']:
-        R = s['eu_r']
-        P = Buf(dev, 1, M, R, R + 4, data=st['P'])
-        Q = Buf(dev, 1, R, N, _ceil4(N) + 4, data=st['Q'])
-        keep += [P, Q]
-        d.eu_p, d.eu_q, d.eu_pms, d.eu_qrs, d.eu_qns, d.eu_r = P.ptr, Q.ptr, P.ld, Q.ld, 1, R
-    if s['as_out']:
-        ai = Buf(dev, 1, a.view.shape[1], a.view.shape[2], a.ld, data=st['as_in'])
-        aso = Buf(dev, 1, a.view.shape[1], a.view.shape[2], a.ld, fill=sent)
-        keep.append(ai)
-        outs.append(aso)
-        d.as_in, d.as_out = ai.ptr, aso.ptr
+    shapes = {k: st[k].shape for k in ('A', 'A2', 'B', 'B2') if k in st}
+    assert shapes == R.stored_shapes(R.census_spec(spec, extra)[1])
+    geo = R.geometry(s, extra, shapes)
+    sent = _sent_float()
+    data = {'A': st['A'], 'A2': st.get('A2'), 'B': st['B'], 'B2': st.get('B2'), 'bias': st.get('bias'), 'E': st.get('E'), 'Bx': st.get('Bx'),
+            'P': st.get('P'), 'Q': st.get('Q'), 'as_in': st.get('as_in')}
+    if s['accumulate']:
+        data['C'] = st['C0'].transpose(0, 2, 1) if s['c_trans'] else st['C0']
+    outputs = ('C', 'Cx', 'as_out')
+    bufs = {k: Buf(dev, g, fill=sent if k in outputs else float('nan'), data=data.get(k)) for k, g in geo.items()}
+    d = R.fill_desc(_lib.GemmDesc(), s, extra, act, geo, {k: b.buf.data_ptr() for k, b in bufs.items()})
+    c, cx, aso = bufs['C'], bufs.get('Cx'), bufs.get('as_out')
+    outs = [bufs[k] for k in outputs if k in bufs]
     wsb = int(lib.recnow_gemm_workspace_bytes(ctypes.byref(d)))
     ws = torch.full((wsb // 4 + 4096,), sent, dtype=torch.float32, device=dev)
     tags = None
     if prof:
         _lib.check(lib.recnow_prof_enable(16), 'recnow_prof_enable')
         _lib.check(lib.recnow_prof_sample_every(1), 'recnow_prof_sample_every')
+    if route is not None:
+        info = _lib.GemmRouteInfo()
+        assert lib.recnow_gemm_route(ctypes.byref(d), wsb, ctypes.byref(info)) == 0, '%s: recnow_gemm_route refuses the descriptor' % route[0]
+        R.check_route(route[0], route[1], extra, info)
     try:
         _lib.call('recnow_gemm', ctypes.byref(d), ctypes.c_void_p(ws.data_ptr()), wsb, _lib.stream())
         torch.cuda.synchronize()
@@ -172,7 +112,7 @@ def run(dev, spec, extra, st, act=E.LINEAR, prof=False):
     finally:
         if prof:
             lib.recnow_prof_enable(0)
-    for o, what in zip(outs, ('C', 'Cx', 'as_out')):
+    for o, what in zip(outs, [k for k in outputs if k in bufs]):
         bad = o.intact()
         assert bad == 0, '%d sentinel words of %s changed (leading-dimension padding, rows before / after, batch gaps)' % (bad, what)
     tail = ws[wsb // 4:].view(torch.int32)
@@ -188,13 +128,6 @@ def run(dev, spec, extra, st, act=E.LINEAR, prof=False):
 def _tiled(x, extra):
     mt, nt = extra.get('tile', (1, 1))
     return np.tile(x, (1, mt, nt)) if (mt, nt) != (1, 1) else x
-
-
-def _census_spec(spec, extra):
-    s = dict(E.SPEC_DEFAULTS)
-    s.update(spec)
-    mt, nt = extra.get('tile', (1, 1))
-    return s, dict(s, M=s['M'] // mt, N=s['N'] // nt)
 
 
 def _same(tag, got, want):
@@ -253,7 +186,7 @@ def _with(c, st):
 
 def check_row(dev, name, kern, spec, extra):
     from rec_now_amd import _lib
-    full, cs = _census_spec(spec, extra)
+    full, cs = R.census_spec(spec, extra)
     c = E.make(cs)
     staging = extra.get('staging')
     if staging is not None:
@@ -261,7 +194,7 @@ def check_row(dev, name, kern, spec, extra):
     try:
         clean = None
         for act in (E.LINEAR, E.RELU):
-            C, Cx, aso, tags = run(dev, full, extra, c.stored, act, prof=(act == E.LINEAR))
+            C, Cx, aso, tags = run(dev, full, extra, c.stored, act, prof=(act == E.LINEAR), route=(name, kern))
             if tags is not None:
                 assert tags and TAG_SHORTK not in tags and set(tags) == {extra['tag']}, '%s: launch tags %r, expected %d' % (name, tags, extra['tag'])
             want, wx, wa = E.expected(c, act)
@@ -342,6 +275,30 @@ def test_gemm_route(dev, route):
     from rec_now_amd import _lib
     _lib.call('recnow_set_gemm_precision', 0)
     check_row(dev, name, kern, spec, extra)
+
+
+def test_split_precision_refusal_is_tagged_fp32(dev):
+    """Precision 1 with a side product over TWO column tiles (M 128, N 256, K 512, interior, aligned): the split kernels take one column tile only,
+    so the plan names the fp32 k_gemm of the 128 x 128 family (two-wide side product, XF 9), the launch is tagged with that family and not with
+    RN_TAG_GEMM_SPLIT, and the output is the precision-0 run's bit for bit."""
+    from rec_now_amd import _lib
+    spec, extra = dict(M=128, N=256, K=512, sp_r=2), {'tag': R.T128, 'reduce': 1}
+    kern = R.kname(128, 128, 32, True, False, False, 0, 0, 9)
+    full, cs = R.census_spec(spec, extra)
+    c = E.make(cs)
+    got = {}
+    try:
+        for prec in (1, 0):
+            _lib.call('recnow_set_gemm_precision', prec)
+            C, Cx, _, tags = run(dev, full, extra, c.stored, prof=True, route=('two column tiles, precision %d' % prec, kern))
+            assert tags == [R.T128], 'precision %d: launch tags %r' % (prec, tags)
+            got[prec] = (C, Cx)
+    finally:
+        _lib.call('recnow_set_gemm_precision', 0)
+    assert np.array_equal(got[1][0].view(np.int32), got[0][0].view(np.int32)) and np.array_equal(got[1][1].view(np.int32), got[0][1].view(np.int32))
+    want, wx, _ = E.expected(c, E.LINEAR)
+    _same('two column tiles C', got[1][0], want)
+    _same('two column tiles Cx', got[1][1], wx)
 
 
 def test_act_routes_agree(dev):

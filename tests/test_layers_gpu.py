@@ -551,7 +551,25 @@ def test_gemm_second_output_outside_short_k_is_unsupported(dev):
     d.M, d.N, d.K, d.batch = 128, 128, 1024, 1
     d.C2, d.ldc2, d.c2_mode = C.data_ptr(), 128, 1
     ws = _lib.workspace(256, dev)
-    assert lib.recnow_gemm(ctypes.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream()) == -3
+    info = _lib.GemmRouteInfo()
+    assert lib.recnow_gemm_route(ctypes.byref(d), ws.numel(), ctypes.byref(info)) == -3      # the plan refuses it, host-only ...
+    # ... and recnow_gemm before it opens a profiling record: with ONE slot armed the refused call leaves it to the valid call behind it
+    ntag = lib.recnow_prof_tag_count()
+    count, ms, flops = (ctypes.c_int * ntag)(), (ctypes.c_double * ntag)(), (ctypes.c_double * ntag)()
+    _lib.check(lib.recnow_prof_enable(1), 'recnow_prof_enable')
+    _lib.check(lib.recnow_prof_sample_every(1), 'recnow_prof_sample_every')
+    try:
+        assert lib.recnow_gemm(ctypes.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream()) == -3
+        _lib.check(lib.recnow_prof_collect(count, ms, flops, None), 'recnow_prof_collect')
+        assert sum(count) == 0, list(count)
+        assert lib.recnow_gemm(ctypes.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream()) == -3
+        d.c2_mode = 0
+        ws = _lib.workspace(lib.recnow_gemm_workspace_bytes(ctypes.byref(d)), dev)
+        _lib.call('recnow_gemm', ctypes.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream())
+        _lib.check(lib.recnow_prof_collect(count, ms, flops, None), 'recnow_prof_collect')
+        assert sum(count) == 1 and lib.recnow_prof_dropped() == 0, (list(count), 'the refused call used up the slot')
+    finally:
+        lib.recnow_prof_enable(0)
 
 
 def test_gemm_a_stream_side_output(dev):
