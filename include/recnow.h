@@ -1252,6 +1252,42 @@ int recnow_afm_bwd(const float* const* fields, int64_t xstride, float* const* df
                    float* dh, float* dp, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * In-batch sampled softmax (ABI 29): the retrieval loss of a two-tower model over in-batch negatives, csrc/in_batch_softmax.hip.
+ * An addition; the reference has no such loss.  q, v: (B, D) fp32 with row strides ldq, ldv in floats (>= D).  ids (B) int64 or NULL,
+ * log_q (B) fp32 or NULL, mask (B) uint8 or NULL (NULL: every row takes part).  With inv_tau = 1 / temperature:
+ *   s_ij = <q_i, v_j> inv_tau - log_q[j];  row i takes part iff mask[i] != 0;  column j is a candidate of row i iff j == i, or
+ *   mask[j] != 0 and not (remove_hits and ids and ids[j] == ids[i]);  l_i = lse_{j in C(i)} s_ij - s_ii.
+ * recnow_ibs_fwd writes per row the statistic (row_max[i], row_logsum[i]) with lse_i = row_max[i] + row_logsum[i] (row_logsum the log
+ * of the sum rescaled by the maximum: exactly 0 for a row whose only candidate is itself), row_pos[i] = s_ii and row_loss[i] = l_i
+ * (rows that do not take part: NaN, NaN, NaN, 0), then loss[0] = the mean of l_i over the n taking-part rows (0 when n = 0) and
+ * n_rows[0] = n, by a fixed-order fp64 reduction of one partial per workgroup.  No (B, B) memory: a workgroup keeps
+ * recnow_ibs_tile(0) rows on chip and walks the other side in tiles of recnow_ibs_tile(1) rows, the logit tiles on
+ * v_mfma_f32_32x32x2_f32 (exact fp32).  recnow_ibs_bwd recomputes the tiles and writes, each row once,
+ *   dq_i = c sum_j (p_ij - [j == i]) v_j,   dv_j = c sum_{i takes part} (p_ij - [j == i]) q_i,   c = gout[0] inv_tau / n,
+ * p_ij = exp(s_ij - lse_i) on candidates, 0 elsewhere; rows that do not take part get 0.  gout and n_rows are DEVICE scalars (nothing
+ * synchronises); dq or dv may be NULL: that orientation is not launched.  Rows that do not take part may hold anything, NaN included.
+ * No atomics: the same input gives the same bits on every run.  B == 0: RECNOW_OK without a launch (loss and n_rows are not written).
+ * recnow_ibs_workspace_bytes = 16 ceil(B / recnow_ibs_tile(0)) for the forward (bwd = 0), 0 for the backward.
+ * recnow_ibs_supported: host-only, 1 for B >= 0 and 1 <= D <= 128, else 0 (RECNOW_EUNSUPPORTED from _fwd / _bwd).
+ * recnow_ibs_tile(which): 0 the rows a workgroup owns, 1 the rows of a streamed tile, 2 the D granule rows are padded to on chip.
+ * 16-byte global accesses need D and the row stride multiples of 4 floats and a 16-byte aligned base (decided per tensor); anything
+ * else takes guarded 4-byte accesses in the same kernels, with the same bits.  recnow_ibs_launches(orientation, vec): host-only count
+ * of the launches so far of orientation 0 (forward), 1 (dq), 2 (dv) whose OWNER-side tensor took 16-byte (vec 1) or 4-byte (vec 0)
+ * accesses; orientation + 4: the same for the streamed-side tensor.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_ibs_supported(int64_t B, int D);
+size_t recnow_ibs_workspace_bytes(int64_t B, int D, int bwd);
+int recnow_ibs_tile(int which);
+int64_t recnow_ibs_launches(int orientation, int vec);
+int recnow_ibs_fwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                   const uint8_t* mask, int64_t B, int D, float inv_tau, int remove_hits, float* row_max, float* row_logsum,
+                   float* row_pos, float* row_loss, float* loss, float* n_rows, void* ws, size_t ws_bytes, void* stream);
+int recnow_ibs_bwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                   const uint8_t* mask, int64_t B, int D, float inv_tau, int remove_hits, const float* row_max,
+                   const float* row_logsum, const float* n_rows, const float* gout, float* dq, int64_t lddq, float* dv,
+                   int64_t lddv, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

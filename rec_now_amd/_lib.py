@@ -181,6 +181,12 @@ SIGNATURES = {
     'recnow_afm_workspace_bytes': (_Z, [_L, _I, _I, _I]),
     'recnow_afm_fwd': (_I, [_P, _L, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
     'recnow_afm_bwd': (_I, [_P, _L, _P, _L, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_ibs_supported': (_I, [_L, _I]),
+    'recnow_ibs_workspace_bytes': (_Z, [_L, _I, _I]),
+    'recnow_ibs_tile': (_I, [_I]),
+    'recnow_ibs_launches': (_L, [_I, _I]),
+    'recnow_ibs_fwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_ibs_bwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _Z, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -221,7 +227,7 @@ class GemmRouteInfo(ctypes.Structure):
         'splitk', 'kchunk', 'grid_x', 'grid_y', 'grid_z', 'xcd_remap', 'tail_pairs', 'reduce_variant', 'reduce_blocks', 'tag')]
 
 
-ABI_VERSION = 28 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 29 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax]"""
 import os
 import sys
 
@@ -1052,6 +1052,92 @@ def afm():
                                                                            'faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread'))
 
 
+def ibs_ref_eager(q, v, ids, lq, tau):
+    """The in-batch sampled softmax as a user writes it from torch operators: the (B, B) logits, a mask of the accidental hits, cross_entropy."""
+    B = q.shape[0]
+    logits = q @ v.T / tau
+    if lq is not None:
+        logits = logits - lq[None, :]
+    if ids is not None:
+        hit = ids[None, :] == ids[:, None]
+        hit.fill_diagonal_(False)
+        logits = logits.masked_fill(hit, float('-inf'))
+    return torch.nn.functional.cross_entropy(logits, torch.arange(B, device=q.device))
+
+
+def in_batch_softmax():
+    """in_batch_softmax_loss forward and forward + backward (dq and dv) at (B 16 384, D 64), (B 65 536, D 64) and (B 65 536, D 128), plain and
+    with item ids + log_q: graph-replay GPU time, the routes in turn, twice, with the spread between the two passes; TFLOP/s of the flop model
+    (2 B^2 D forward, 8 B^2 D backward) beside the 157.3 TFLOP/s exact-fp32 MFMA peak.  The yardstick is the torch composition in the same run
+    (forward, and backward through autograd); at B = 65 536 it holds about 50 GB of (B, B) tensors -- reported as such where it does not fit."""
+    from rec_now_amd.rec_block.in_batch_softmax import in_batch_softmax_loss
+    tau = 0.5
+    cases = [(16384, 64), (65536, 64), (65536, 128)]
+    seen = {}
+
+    def graph_ms(fn):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fn()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        ms = timeit(g.replay, reps, warm=2)
+        del g
+        torch.cuda.empty_cache()
+        return ms
+
+    for rnd in (1, 2):
+        for B, D in cases:
+            for with_ids in (False, True):
+                gen = torch.Generator(device=dev).manual_seed(B + D)
+                q = (torch.randn(B, D, device=dev, generator=gen) * D ** -0.25).requires_grad_(True)
+                v = (torch.randn(B, D, device=dev, generator=gen) * D ** -0.25).requires_grad_(True)
+                ids = torch.randint(0, B // 4, (B,), device=dev, generator=gen) if with_ids else None
+                lq = torch.rand(B, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids else None
+                run, ref = (lambda: in_batch_softmax_loss(q, v, ids, lq, tau)), (lambda: ibs_ref_eager(q, v, ids, lq, tau))
+
+                def fb_of(fn):
+                    def step():
+                        return torch.autograd.grad(fn(), [q, v])
+                    return step
+
+                def fwd_of(fn):
+                    def step():
+                        with torch.no_grad():
+                            return fn()
+                    return step
+                ff, fb = 2.0 * B * B * D, 8.0 * B * B * D
+                gf, gfb = graph_ms(fwd_of(run)), graph_ms(fb_of(run))
+                tag = 'ids+log_q' if with_ids else 'plain'
+                try:
+                    with torch.no_grad():
+                        err = abs(run().item() - ref().item())
+                    rgf, rgfb = graph_ms(fwd_of(ref)), graph_ms(fb_of(ref))
+                    fits = 'torch composition (forms (B, B)): fwd %.3f ms, bwd %.3f ms, fwd+bwd %.3f ms -> fused is %.2fx (fwd) %.2fx (bwd) %.2fx (fwd+bwd) | |loss - torch| %.2g' % (
+                        rgf, rgfb - rgf, rgfb, rgf / gf, (rgfb - rgf) / (gfb - gf), rgfb / gfb, err)
+                except torch.cuda.OutOfMemoryError:
+                    rgf = rgfb = float('nan')
+                    fits = 'torch composition: DOES NOT FIT (out of memory on its (B, B) tensors)'
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                print('pass %d in_batch_softmax B=%d D=%d %s : fused (graph) fwd %.3f ms %.1f TFLOP/s (%.2f of 157.3), bwd %.3f ms %.1f TFLOP/s (%.2f), fwd+bwd %.3f ms | %s'
+                      % (rnd, B, D, tag, gf, ff / gf / 1e9, ff / gf / 1e9 / 157.3, gfb - gf, fb / (gfb - gf) / 1e9, fb / (gfb - gf) / 1e9 / 157.3, gfb, fits), flush=True)
+                seen.setdefault((B, D, tag), []).append((gfb, rgfb, gf, rgf))
+                del q, v, ids, lq
+                torch.cuda.empty_cache()
+    for (B, D, tag), ((a, ra, af, raf), (b, rb, bf, rbf)) in seen.items():
+        for what, (p, s, rp, rs) in (('fwd', (af, bf, raf, rbf)), ('bwd', (a - af, b - bf, ra - raf, rb - rbf)), ('fwd+bwd', (a, b, ra, rb))):
+            spread = abs(p - s) / min(p, s)
+            worst = min(rp, rs) / max(p, s)
+            verdict = 'no yardstick' if worst != worst else ('faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread')
+            print('in_batch_softmax B=%d D=%d %s : fused %s (graph) %.3f / %.3f ms, spread between the passes %.1f %%; torch %.3f / %.3f ms; fused against torch '
+                  'in the worse pairing %.2fx -> %s' % (B, D, tag, what, p, s, 100 * spread, rp, rs, worst, verdict))
+
+
 def gnn_ref_eager(x, indices, ws, L, F):
     """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
     from the weight vector, matmul, add, tanh; transpose back and flatten."""
@@ -1429,6 +1515,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax)):
         if name in which:
             fn()
