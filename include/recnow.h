@@ -419,6 +419,12 @@ int recnow_fm_fwd(const float* const* fields, int F, int64_t B, int D, float* y,
 /* dfields[f][b][d] = gy[b] * (S[b][d] - x_f[b][d]);  dfields: DEVICE array of F device pointers to (B,D) buffers. */
 int recnow_fm_bwd(const float* const* fields, float* const* dfields, int F, int64_t B, int D, const float* S,
                   const float* gy, void* stream);
+/* Which kernel recnow_fm_fwd (which = 0) / recnow_fm_bwd (which = 1) launch for a call of this shape: the ONE statement of that choice (both
+ * launchers call the function behind it); nothing is launched and no device is needed.  has_S: S != NULL (1 is required for the backward).
+ * Returns family * 100000 + save_s * 1000 + lanes_per_row.  family: 1 k_fm_*_generic (lanes_per_row 0), 2 k_fm_*_vec4, 3 k_fm_*_wide;
+ * save_s: the forward instantiation that writes S (0 for the backward); lanes_per_row = D / 4.  B = 0: 0 (no launch).  RECNOW_EINVAL: which
+ * outside {0, 1}, F < 1, B < 0, D < 1, has_S outside {0, 1}, or the backward without S. */
+int recnow_fm_route(int which, int64_t B, int F, int D, int has_S);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exact-fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32: every product/accumulate is an fp32 fma, no reduced precision),
@@ -791,6 +797,14 @@ int recnow_cin_bwd(const float* const* weights_host, const float* dout, const vo
 int recnow_inner_pnn_fwd(const float* const* fields, int F, int64_t B, int D, float* out, void* stream);
 int recnow_inner_pnn_bwd(const float* const* fields, float* const* dfields, int F, int64_t B, int D, const float* dout,
                          void* stream);
+/* Which kernel recnow_inner_pnn_fwd (which = 0) / _bwd (which = 1) launch (the launchers call the function behind it; no launch, no device).
+ * align_mask: 1 when `out` (forward) / `dout` (backward) starts OFF a 16-byte boundary.  Returns
+ *   100000 + DMAX * 10 + waves                               k_ipnn_fwd / k_ipnn_bwd<DMAX> with `waves` waves per workgroup
+ *   200000 + D * 100 + two * 10 + vec                        k_ipnn_fwd_gram<D>; two: F > 32; vec: float4 stores of the results
+ *   300000 + D * 1000 + NB * 100 + FULL * 10 + vec           k_ipnn_bwd_gram<D, NB, FULL>; vec: float4 loads of dout
+ * 0 for an empty call (B = 0; the forward with F = 1); RECNOW_EUNSUPPORTED where the launcher answers that (D > 64, or one row's tile does not
+ * fit in LDS); RECNOW_EINVAL: which outside {0, 1}, F < 1, B < 0, D < 1, align_mask outside {0, 1}. */
+int recnow_inner_pnn_route(int which, int64_t B, int F, int D, int align_mask);
 
 /* SENETLayer: rec_now/layers/senet_layer.py:93-119.  Fields may have different widths: dims[f], offs[f] (first column of
  * field f in the concatenation, total = sum dims) are DEVICE int32 arrays.
@@ -834,6 +848,12 @@ int recnow_attention_dot_fwd(const float* user, const float* doc, int64_t B, int
                              float* score_sum, void* stream);
 int recnow_attention_dot_bwd(const float* user, const float* doc, const float* dmat, const float* dsum, int64_t B, int L,
                              int D, int filter_neg, float* duser, float* ddoc, void* stream);
+/* Which kernel recnow_attention_dot_fwd (which = 0) / _bwd (which = 1) launch (the launchers call the function behind it; no launch, no
+ * device).  align_mask: one bit per tensor that starts OFF a 16-byte boundary (NULL is aligned) -- 1 user, 2 doc, 4 mat (forward) / dmat
+ * (backward), 8 duser, 16 ddoc (backward only).  Returns 200000 + CPL for k_attn_dot_v4<CPL, ..> (CPL = D / 4), 100000 + GS for
+ * k_attn_dot_fwd / _bwd<GS>; 0 for B = 0; RECNOW_EUNSUPPORTED for D > 256; RECNOW_EINVAL: which outside {0, 1}, B < 0, L < 0, D < 1,
+ * align_mask outside 0 .. 7 (forward) / 0 .. 31 (backward). */
+int recnow_attention_dot_route(int which, int64_t B, int L, int D, int align_mask);
 
 /* attention_by_dnn (DIN attention unit, ABI 8): rec_now/rec_block/attention.py:41-82.  user (B,L,D), doc (B,D), nl Dense
  * layers of widths dims_host[0..nl) (a HOST array; dims_host[nl-1] must be 1), kernels_host / biases_host: HOST arrays of nl

@@ -71,6 +71,7 @@ SIGNATURES = {
     'recnow_approx_ndcg_fwdbwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_fm_fwd': (_I, [_P, _I, _L, _I, _P, _P, _P]),
     'recnow_fm_bwd': (_I, [_P, _P, _I, _L, _I, _P, _P, _P]),
+    'recnow_fm_route': (_I, [_I, _L, _I, _I, _I]),
     'recnow_gemm_workspace_bytes': (_Z, [_P]),
     'recnow_gemm': (_I, [_P, _P, _Z, _P]),
     'recnow_gemm_route': (_I, [_P, _Z, _P]),
@@ -108,6 +109,7 @@ SIGNATURES = {
     'recnow_cin_bwd': (_I, [_P, _P, _P, _Z, _L, _I, _I, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     'recnow_inner_pnn_fwd': (_I, [_P, _I, _L, _I, _P, _P]),
     'recnow_inner_pnn_bwd': (_I, [_P, _P, _I, _L, _I, _P, _P]),
+    'recnow_inner_pnn_route': (_I, [_I, _L, _I, _I, _I]),
     'recnow_senet_squeeze': (_I, [_P, _P, _P, _I, _I, _L, _P, _I, _P]),
     'recnow_senet_scale_fwd': (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _P]),
     'recnow_senet_scale_bwd_w': (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _P]),
@@ -118,6 +120,7 @@ SIGNATURES = {
     'recnow_senet_fused_bwd': (_I, [_P, _P, _I, _I, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'recnow_attention_dot_fwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P]),
     'recnow_attention_dot_bwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
+    'recnow_attention_dot_route': (_I, [_I, _L, _I, _I, _I]),
     'recnow_attention_dnn_workspace_bytes': (_Z, [_L, _I, _I, _I, _P, _I]),
     'recnow_attention_dnn_fwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     'recnow_attention_dnn_bwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
@@ -227,7 +230,7 @@ class GemmRouteInfo(ctypes.Structure):
         'splitk', 'kchunk', 'grid_x', 'grid_y', 'grid_z', 'xcd_remap', 'tail_pairs', 'reduce_variant', 'reduce_blocks', 'tag')]
 
 
-ABI_VERSION = 29 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 30 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""
@@ -293,6 +296,16 @@ def f32c(t, what='tensor'):
     if t.dtype != torch.float32:
         t = t.to(torch.float32)
     return t.contiguous()
+
+
+def aligned_fields(tensors, vector_route):
+    """The field tensors of a list-of-tensor call, each on a 16-byte boundary when the call takes a float4 route.  recnow_fm_fwd / _bwd (D % 4 == 0)
+    and the Gram kernels of InnerPNN read float4 pieces of every field and do not test its base pointer; a contiguous view that starts a few floats into
+    a larger buffer passes f32c and is not aligned.  Such a field is replaced by a copy (clone(): a fresh allocation); every other tensor is returned as
+    it is, and nothing is touched when the route is scalar."""
+    if not vector_route:
+        return list(tensors)
+    return [t if t.data_ptr() % 16 == 0 else t.clone() for t in tensors]
 
 
 def ptr(t):

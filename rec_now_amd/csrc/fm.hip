@@ -262,6 +262,29 @@ static inline int fm_grid(int64_t n) {
     return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }
 
+// The route choice of recnow_fm_fwd / recnow_fm_bwd, stated once: the launchers launch what fm_route returns and recnow_fm_route answers the same
+// question without a launch (tests/_rowop_routes.py mirrors it).  save_s: the forward writes S (always 0 for the backward).
+enum { FM_GENERIC = 1, FM_VEC4 = 2, FM_WIDE = 3 };
+struct FmRoute {
+    int family, save_s, lanes;          // lanes: lanes_per_row = D / 4 of the float4 kernels, 0 on the generic path
+};
+static FmRoute fm_route(int which, int64_t B, int D, bool has_S) {
+    FmRoute r = {FM_GENERIC, which == 0 && has_S, 0};
+    if (!fm_vec_ok(D)) return r;
+    const int64_t nchunk = B * D / 4;
+    r.lanes = D / 4;
+    // enough chunks for 512 workgroups of 4 per thread; k_fm_bwd_wide has no tail code: whole workgroups only
+    const bool wide = nchunk >= 256 * 4 * 512 && (which == 0 || nchunk % (256 * 4) == 0);
+    r.family = wide ? FM_WIDE : FM_VEC4;
+    return r;
+}
+extern "C" int recnow_fm_route(int which, int64_t B, int F, int D, int has_S) {
+    if ((which != 0 && which != 1) || F < 1 || B < 0 || D < 1 || (has_S != 0 && has_S != 1) || (which == 1 && !has_S)) return RECNOW_EINVAL;
+    if (B == 0) return 0;
+    const FmRoute r = fm_route(which, B, D, has_S != 0);
+    return r.family * 100000 + r.save_s * 1000 + r.lanes;
+}
+
 // fields: device array of F pointers, each to a contiguous (B,D) fp32 tensor (16-byte aligned when D % 4 == 0).
 // y: [B];  S: [B*D] saved for backward (may be NULL: forward only).
 extern "C" int recnow_fm_fwd(const float* const* fields, int F, int64_t B, int D, float* y, float* S, void* stream) {
@@ -269,16 +292,17 @@ extern "C" int recnow_fm_fwd(const float* const* fields, int F, int64_t B, int D
     if (B == 0) return RECNOW_OK;
     if (!fields || !y) return RECNOW_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (fm_vec_ok(D)) {
-        const int64_t nchunk = B * D / 4;
-        if (nchunk >= 256 * 4 * 512) {          // enough chunks for 512 workgroups of 4 per thread
-            const int g = fm_grid((nchunk + 3) / 4);
-            if (S) hipLaunchKernelGGL((k_fm_fwd_wide<true, 4, 4>), g, 256, 0, st, fields, F, nchunk, D / 4, y, S);
-            else hipLaunchKernelGGL((k_fm_fwd_wide<false, 4, 4>), g, 256, 0, st, fields, F, nchunk, D / 4, y, S);
-        } else if (S) hipLaunchKernelGGL(k_fm_fwd_vec4<true>, fm_grid(nchunk), 256, 0, st, fields, F, nchunk, D / 4, y, S);
-        else hipLaunchKernelGGL(k_fm_fwd_vec4<false>, fm_grid(nchunk), 256, 0, st, fields, F, nchunk, D / 4, y, S);
+    const FmRoute r = fm_route(0, B, D, S != nullptr);
+    const int64_t nchunk = B * D / 4;
+    if (r.family == FM_WIDE) {
+        const int g = fm_grid((nchunk + 3) / 4);
+        if (r.save_s) hipLaunchKernelGGL((k_fm_fwd_wide<true, 4, 4>), g, 256, 0, st, fields, F, nchunk, r.lanes, y, S);
+        else hipLaunchKernelGGL((k_fm_fwd_wide<false, 4, 4>), g, 256, 0, st, fields, F, nchunk, r.lanes, y, S);
+    } else if (r.family == FM_VEC4) {
+        if (r.save_s) hipLaunchKernelGGL(k_fm_fwd_vec4<true>, fm_grid(nchunk), 256, 0, st, fields, F, nchunk, r.lanes, y, S);
+        else hipLaunchKernelGGL(k_fm_fwd_vec4<false>, fm_grid(nchunk), 256, 0, st, fields, F, nchunk, r.lanes, y, S);
     } else {
-        if (S) hipLaunchKernelGGL(k_fm_fwd_generic<true>, rn_cdiv(B, 256), 256, 0, st, fields, F, B, D, y, S);
+        if (r.save_s) hipLaunchKernelGGL(k_fm_fwd_generic<true>, rn_cdiv(B, 256), 256, 0, st, fields, F, B, D, y, S);
         else hipLaunchKernelGGL(k_fm_fwd_generic<false>, rn_cdiv(B, 256), 256, 0, st, fields, F, B, D, y, S);
     }
     RN_LAUNCH_CHECK();
@@ -292,14 +316,11 @@ extern "C" int recnow_fm_bwd(const float* const* fields, float* const* dfields, 
     if (B == 0) return RECNOW_OK;
     if (!fields || !dfields || !S || !gy) return RECNOW_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (fm_vec_ok(D)) {
-        const int64_t nchunk = B * D / 4;
-        if (nchunk >= 256 * 4 * 512 && nchunk % (256 * 4) == 0)
-            hipLaunchKernelGGL((k_fm_bwd_wide<4, 4>), fm_grid(nchunk / 4), 256, 0, st, fields, dfields, F, nchunk, D / 4, S, gy);
-        else hipLaunchKernelGGL(k_fm_bwd_vec4, fm_grid(nchunk), 256, 0, st, fields, dfields, F, nchunk, D / 4, S, gy);
-    } else {
-        hipLaunchKernelGGL(k_fm_bwd_generic, fm_grid(B * D), 256, 0, st, fields, dfields, F, B, D, S, gy);
-    }
+    const FmRoute r = fm_route(1, B, D, true);
+    const int64_t nchunk = B * D / 4;
+    if (r.family == FM_WIDE) hipLaunchKernelGGL((k_fm_bwd_wide<4, 4>), fm_grid(nchunk / 4), 256, 0, st, fields, dfields, F, nchunk, r.lanes, S, gy);
+    else if (r.family == FM_VEC4) hipLaunchKernelGGL(k_fm_bwd_vec4, fm_grid(nchunk), 256, 0, st, fields, dfields, F, nchunk, r.lanes, S, gy);
+    else hipLaunchKernelGGL(k_fm_bwd_generic, fm_grid(B * D), 256, 0, st, fields, dfields, F, B, D, S, gy);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
 }

@@ -352,15 +352,65 @@ static int ipnn_cfg(int F, int D, bool bwd, int* waves, size_t* lds) {
     return RECNOW_OK;
 }
 
+// The route choice of recnow_inner_pnn_fwd / recnow_inner_pnn_bwd, stated once: the launchers launch what ipnn_route returns and
+// recnow_inner_pnn_route answers the same question without a launch (tests/_rowop_routes.py mirrors it).  out_mis: `out` (forward) / `dout`
+// (backward) starts off a 16-byte boundary.  `two` and the forward's `vec` are not launch arguments: k_ipnn_fwd_gram takes both branches from F, P and
+// the address of `out` by the expressions repeated here.
+enum { IPNN_NONE = 0, IPNN_GENERAL = 1, IPNN_GRAM_FWD = 2, IPNN_GRAM_BWD = 3 };
+struct IpnnRoute {
+    int rc;                 // RECNOW_OK, or why nothing can be launched
+    int family;             // IPNN_NONE: an empty call
+    int d;                  // general: DMAX of k_ipnn_fwd / k_ipnn_bwd; Gram: D
+    int waves;              // general: waves per workgroup
+    size_t lds;             // general: dynamic LDS bytes
+    int two, vec;           // Gram forward: F > 32 (the g01 / g11 blocks), float4 stores of the results; Gram backward: vec = float4 loads of dout
+    int nb, full;           // Gram backward: NB = ceil(F / 16), F == 16 NB
+};
+static IpnnRoute ipnn_route(int which, int64_t B, int F, int D, bool out_mis) {
+    IpnnRoute r = {RECNOW_OK, IPNN_NONE, 0, 0, 0, 0, 0, 0, 0};
+    if (B == 0 || (which == 0 && F == 1)) return r;
+    if (D > 64) {
+        r.rc = RECNOW_EUNSUPPORTED;
+        return r;
+    }
+    const int64_t P = (int64_t)F * (F - 1) / 2;
+    if (F >= 2 && F <= 64 && (D == 4 || D == 8 || D == 12 || D == 16) && B <= 0x7fffffffll) {
+        r.family = which == 0 ? IPNN_GRAM_FWD : IPNN_GRAM_BWD;
+        r.d = D;
+        r.vec = (P & 3) == 0 && !out_mis;                   // rows of out / dout are float4-addressable
+        r.two = which == 0 && F > 32;
+        if (which == 1) {
+            r.nb = (F + 15) / 16;
+            r.full = F == 16 * r.nb;
+        }
+        return r;
+    }
+    r.rc = ipnn_cfg(F, D, which == 1, &r.waves, &r.lds);
+    if (r.rc) return r;
+    r.family = IPNN_GENERAL;
+    r.d = D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : 64;
+    return r;
+}
+extern "C" int recnow_inner_pnn_route(int which, int64_t B, int F, int D, int align_mask) {
+    if ((which != 0 && which != 1) || F < 1 || B < 0 || D < 1 || align_mask < 0 || align_mask > 1) return RECNOW_EINVAL;
+    const IpnnRoute r = ipnn_route(which, B, F, D, align_mask != 0);
+    if (r.rc) return r.rc;
+    if (r.family == IPNN_GENERAL) return 100000 + r.d * 10 + r.waves;
+    if (r.family == IPNN_GRAM_FWD) return 200000 + r.d * 100 + r.two * 10 + r.vec;
+    if (r.family == IPNN_GRAM_BWD) return 300000 + r.d * 1000 + r.nb * 100 + r.full * 10 + r.vec;
+    return 0;
+}
+
 extern "C" int recnow_inner_pnn_fwd(const float* const* fields, int F, int64_t B, int D, float* out, void* stream) {
     if (F < 1 || B < 0 || D < 1) return RECNOW_EINVAL;
     if (B == 0 || F == 1) return RECNOW_OK;
     if (!fields || !out) return RECNOW_EINVAL;
-    if (D > 64) return RECNOW_EUNSUPPORTED;
-    int waves;
-    size_t lds;
+    const IpnnRoute route = ipnn_route(0, B, F, D, (reinterpret_cast<uintptr_t>(out) & 15) != 0);
+    if (route.rc) return route.rc;
+    const int waves = route.waves;
+    const size_t lds = route.lds;
     hipStream_t st = (hipStream_t)stream;
-    if (F <= 64 && (D == 4 || D == 8 || D == 12 || D == 16) && B <= 0x7fffffffll) {
+    if (route.family == IPNN_GRAM_FWD) {
         int64_t gs = (B + 3) / 4;
         if (gs > 16384) gs = 16384;
         // per wave: the input tile (64 rows, padded stride <= 20 floats), later overwritten by the row's P results
@@ -368,20 +418,18 @@ extern "C" int recnow_inner_pnn_fwd(const float* const* fields, int F, int64_t B
         int64_t wstride = 64 * 20;
         if (((P + 3) & ~3ll) > wstride) wstride = (P + 3) & ~3ll;
         const size_t slds = 4 * (size_t)wstride * sizeof(float);
-        if (D == 16) hipLaunchKernelGGL(k_ipnn_fwd_gram<16>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
-        else if (D == 12) hipLaunchKernelGGL(k_ipnn_fwd_gram<12>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
-        else if (D == 8) hipLaunchKernelGGL(k_ipnn_fwd_gram<8>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
+        if (route.d == 16) hipLaunchKernelGGL(k_ipnn_fwd_gram<16>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
+        else if (route.d == 12) hipLaunchKernelGGL(k_ipnn_fwd_gram<12>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
+        else if (route.d == 8) hipLaunchKernelGGL(k_ipnn_fwd_gram<8>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
         else hipLaunchKernelGGL(k_ipnn_fwd_gram<4>, (int)gs, 256, slds, st, fields, F, B, wstride, out);
         RN_LAUNCH_CHECK();
         return RECNOW_OK;
     }
-    int rc = ipnn_cfg(F, D, false, &waves, &lds);
-    if (rc) return rc;
     int64_t g = (B + waves - 1) / waves;
     if (g > 4096) g = 4096;
-    if (D <= 8) hipLaunchKernelGGL(k_ipnn_fwd<8>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
-    else if (D <= 16) hipLaunchKernelGGL(k_ipnn_fwd<16>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
-    else if (D <= 32) hipLaunchKernelGGL(k_ipnn_fwd<32>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
+    if (route.d == 8) hipLaunchKernelGGL(k_ipnn_fwd<8>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
+    else if (route.d == 16) hipLaunchKernelGGL(k_ipnn_fwd<16>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
+    else if (route.d == 32) hipLaunchKernelGGL(k_ipnn_fwd<32>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
     else hipLaunchKernelGGL(k_ipnn_fwd<64>, (int)g, waves * 64, lds, st, fields, F, B, D, out);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
@@ -392,46 +440,45 @@ extern "C" int recnow_inner_pnn_bwd(const float* const* fields, float* const* df
     if (F < 1 || B < 0 || D < 1) return RECNOW_EINVAL;
     if (B == 0) return RECNOW_OK;
     if (!fields || !dfields || (F > 1 && !dout)) return RECNOW_EINVAL;
-    if (D > 64) return RECNOW_EUNSUPPORTED;
-    int waves;
-    size_t lds;
+    const IpnnRoute route = ipnn_route(1, B, F, D, (reinterpret_cast<uintptr_t>(dout) & 15) != 0);
+    if (route.rc) return route.rc;
+    const int waves = route.waves;
+    const size_t lds = route.lds;
     hipStream_t st = (hipStream_t)stream;
-    if (F >= 2 && F <= 64 && (D == 4 || D == 8 || D == 12 || D == 16) && B <= 0x7fffffffll) {
+    if (route.family == IPNN_GRAM_BWD) {
         int64_t gs = (B + 3) / 4;
         if (gs > 16384) gs = 16384;
         const int64_t P = (int64_t)F * (F - 1) / 2;
         // per wave: the [64][16] X tile, then the packed gradients (+64: masked-out reads of the last rows stay inside)
         const int64_t wstride = 64 * 16 + ((P + 64 + 3) & ~3ll);
         const size_t slds = 4 * (size_t)wstride * sizeof(float);
-        const int vec = (P & 3) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0;       // rows of dout are float4-addressable
+        const int vec = route.vec;
 #define IPNN_BWD_LAUNCH(DD, NBB)                                                                                         \
     do {                                                                                                                 \
-        if (F == 16 * NBB) hipLaunchKernelGGL((k_ipnn_bwd_gram<DD, NBB, true>), (int)gs, 256, slds, st, fields, dfields, F, B, wstride, dout, vec); \
-        else hipLaunchKernelGGL((k_ipnn_bwd_gram<DD, NBB, false>), (int)gs, 256, slds, st, fields, dfields, F, B, wstride, dout, vec);             \
+        if (route.full) hipLaunchKernelGGL((k_ipnn_bwd_gram<DD, NBB, true>), (int)gs, 256, slds, st, fields, dfields, F, B, wstride, dout, vec); \
+        else hipLaunchKernelGGL((k_ipnn_bwd_gram<DD, NBB, false>), (int)gs, 256, slds, st, fields, dfields, F, B, wstride, dout, vec);          \
     } while (0)
 #define IPNN_BWD_LAUNCH_D(DD)                                                                                            \
     do {                                                                                                                 \
-        if (F <= 16) IPNN_BWD_LAUNCH(DD, 1);                                                                             \
-        else if (F <= 32) IPNN_BWD_LAUNCH(DD, 2);                                                                        \
-        else if (F <= 48) IPNN_BWD_LAUNCH(DD, 3);                                                                        \
+        if (route.nb == 1) IPNN_BWD_LAUNCH(DD, 1);                                                                       \
+        else if (route.nb == 2) IPNN_BWD_LAUNCH(DD, 2);                                                                  \
+        else if (route.nb == 3) IPNN_BWD_LAUNCH(DD, 3);                                                                  \
         else IPNN_BWD_LAUNCH(DD, 4);                                                                                     \
     } while (0)
-        if (D == 16) IPNN_BWD_LAUNCH_D(16);
-        else if (D == 12) IPNN_BWD_LAUNCH_D(12);
-        else if (D == 8) IPNN_BWD_LAUNCH_D(8);
+        if (route.d == 16) IPNN_BWD_LAUNCH_D(16);
+        else if (route.d == 12) IPNN_BWD_LAUNCH_D(12);
+        else if (route.d == 8) IPNN_BWD_LAUNCH_D(8);
         else IPNN_BWD_LAUNCH_D(4);
 #undef IPNN_BWD_LAUNCH_D
 #undef IPNN_BWD_LAUNCH
         RN_LAUNCH_CHECK();
         return RECNOW_OK;
     }
-    int rc = ipnn_cfg(F, D, true, &waves, &lds);
-    if (rc) return rc;
     int64_t g = (B + waves - 1) / waves;
     if (g > 4096) g = 4096;
-    if (D <= 8) hipLaunchKernelGGL(k_ipnn_bwd<8>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
-    else if (D <= 16) hipLaunchKernelGGL(k_ipnn_bwd<16>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
-    else if (D <= 32) hipLaunchKernelGGL(k_ipnn_bwd<32>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
+    if (route.d == 8) hipLaunchKernelGGL(k_ipnn_bwd<8>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
+    else if (route.d == 16) hipLaunchKernelGGL(k_ipnn_bwd<16>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
+    else if (route.d == 32) hipLaunchKernelGGL(k_ipnn_bwd<32>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
     else hipLaunchKernelGGL(k_ipnn_bwd<64>, (int)g, waves * 64, lds, st, fields, dfields, F, B, D, dout);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
@@ -813,13 +860,38 @@ k_attn_dot_v4(const float* __restrict__ user, const float* __restrict__ doc, con
         if (!BWD && ok && gl == 0) ssum[b] = tot;
     }
 }
-static inline int attn_cpl(int D, const void* a, const void* b2, const void* c2, const void* d2) {
-    if (D % 4 || ((((uintptr_t)a | (uintptr_t)b2 | (uintptr_t)c2 | (uintptr_t)d2) & 15) != 0)) return 0;
+// The route choice of recnow_attention_dot_fwd / _bwd, stated once: the launchers launch what attn_route returns and recnow_attention_dot_route
+// answers the same question without a launch (tests/_rowop_routes.py mirrors it).  mis: one bit per tensor that starts OFF a 16-byte boundary
+// (NULL is aligned) -- the float4 kernels need every one of them aligned.
+#define ATTN_MIS_USER 1
+#define ATTN_MIS_DOC 2
+#define ATTN_MIS_MAT 4        /* forward: mat; backward: dmat */
+#define ATTN_MIS_DUSER 8      /* backward */
+#define ATTN_MIS_DDOC 16      /* backward */
+struct AttnRoute {
+    int cpl;                // > 0: k_attn_dot_v4<cpl, ..>
+    int gs;                 // cpl == 0: k_attn_dot_fwd / _bwd<gs>
+};
+static AttnRoute attn_route(int D, int mis) {
+    AttnRoute r = {0, D <= 16 ? 16 : D <= 32 ? 32 : 64};
     const int cpl = D / 4;
-    return (cpl == 1 || cpl == 2 || cpl == 4 || cpl == 8 || cpl == 16) ? cpl : 0;
+    if (D % 4 == 0 && !mis && (cpl == 1 || cpl == 2 || cpl == 4 || cpl == 8 || cpl == 16)) r.cpl = cpl;
+    return r;
+}
+static inline int attn_mis(const void* user, const void* doc, const void* mat, const void* duser, const void* ddoc) {
+    auto off = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    return (off(user) ? ATTN_MIS_USER : 0) | (off(doc) ? ATTN_MIS_DOC : 0) | (off(mat) ? ATTN_MIS_MAT : 0) | (off(duser) ? ATTN_MIS_DUSER : 0) |
+           (off(ddoc) ? ATTN_MIS_DDOC : 0);
+}
+extern "C" int recnow_attention_dot_route(int which, int64_t B, int L, int D, int align_mask) {
+    if ((which != 0 && which != 1) || B < 0 || L < 0 || D < 1 || align_mask < 0 || align_mask > (which ? 31 : 7)) return RECNOW_EINVAL;
+    if (D > 64 * ATTN_NCH) return RECNOW_EUNSUPPORTED;
+    if (B == 0) return 0;
+    const AttnRoute r = attn_route(D, align_mask);
+    return r.cpl ? 200000 + r.cpl : 100000 + r.gs;
 }
 #define ATTN_V4_LAUNCH(BWD, ...)                                                                                          \
-    switch (cpl) {                                                                                                       \
+    switch (route.cpl) {                                                                                                 \
         case 1: hipLaunchKernelGGL((k_attn_dot_v4<1, BWD>), attn_grid(B, 16), 256, 0, st, __VA_ARGS__); break;           \
         case 2: hipLaunchKernelGGL((k_attn_dot_v4<2, BWD>), attn_grid(B, 16), 256, 0, st, __VA_ARGS__); break;           \
         case 4: hipLaunchKernelGGL((k_attn_dot_v4<4, BWD>), attn_grid(B, 16), 256, 0, st, __VA_ARGS__); break;           \
@@ -833,13 +905,14 @@ extern "C" int recnow_attention_dot_fwd(const float* user, const float* doc, int
     if (B == 0) return RECNOW_OK;
     if ((L > 0 && !user) || !doc || !mat || !score_sum) return RECNOW_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (const int cpl = attn_cpl(D, user, doc, mat, nullptr)) {
+    const AttnRoute route = attn_route(D, attn_mis(user, doc, mat, nullptr, nullptr));
+    if (route.cpl) {
         ATTN_V4_LAUNCH(false, user, doc, (const float*)nullptr, (const float*)nullptr, B, L, filter_neg, mat, score_sum, (float*)nullptr);
         RN_LAUNCH_CHECK();
         return RECNOW_OK;
     }
-    if (D <= 16) hipLaunchKernelGGL(k_attn_dot_fwd<16>, attn_grid(B, 16), 256, 0, st, user, doc, B, L, D, filter_neg, mat, score_sum);
-    else if (D <= 32) hipLaunchKernelGGL(k_attn_dot_fwd<32>, attn_grid(B, 32), 256, 0, st, user, doc, B, L, D, filter_neg, mat, score_sum);
+    if (route.gs == 16) hipLaunchKernelGGL(k_attn_dot_fwd<16>, attn_grid(B, 16), 256, 0, st, user, doc, B, L, D, filter_neg, mat, score_sum);
+    else if (route.gs == 32) hipLaunchKernelGGL(k_attn_dot_fwd<32>, attn_grid(B, 32), 256, 0, st, user, doc, B, L, D, filter_neg, mat, score_sum);
     else hipLaunchKernelGGL(k_attn_dot_fwd<64>, attn_grid(B, 64), 256, 0, st, user, doc, B, L, D, filter_neg, mat, score_sum);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
@@ -851,13 +924,14 @@ extern "C" int recnow_attention_dot_bwd(const float* user, const float* doc, con
     if (B == 0) return RECNOW_OK;
     if ((L > 0 && (!user || !duser)) || !doc || !ddoc) return RECNOW_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (const int cpl = attn_cpl(D, user, doc, dmat, (const void*)((uintptr_t)duser | (uintptr_t)ddoc))) {
+    const AttnRoute route = attn_route(D, attn_mis(user, doc, dmat, duser, ddoc));
+    if (route.cpl) {
         ATTN_V4_LAUNCH(true, user, doc, dmat, dsum, B, L, filter_neg, ddoc, (float*)nullptr, duser);
         RN_LAUNCH_CHECK();
         return RECNOW_OK;
     }
-    if (D <= 16) hipLaunchKernelGGL(k_attn_dot_bwd<16>, attn_grid(B, 16), 256, 0, st, user, doc, dmat, dsum, B, L, D, filter_neg, duser, ddoc);
-    else if (D <= 32) hipLaunchKernelGGL(k_attn_dot_bwd<32>, attn_grid(B, 32), 256, 0, st, user, doc, dmat, dsum, B, L, D, filter_neg, duser, ddoc);
+    if (route.gs == 16) hipLaunchKernelGGL(k_attn_dot_bwd<16>, attn_grid(B, 16), 256, 0, st, user, doc, dmat, dsum, B, L, D, filter_neg, duser, ddoc);
+    else if (route.gs == 32) hipLaunchKernelGGL(k_attn_dot_bwd<32>, attn_grid(B, 32), 256, 0, st, user, doc, dmat, dsum, B, L, D, filter_neg, duser, ddoc);
     else hipLaunchKernelGGL(k_attn_dot_bwd<64>, attn_grid(B, 64), 256, 0, st, user, doc, dmat, dsum, B, L, D, filter_neg, duser, ddoc);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;

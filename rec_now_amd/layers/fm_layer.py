@@ -13,6 +13,7 @@ class _FMFunction(torch.autograd.Function):
         for x in xs:
             if x.shape != (B, D):
                 raise ValueError('all FM inputs must have the same (B, D) shape')
+        xs = _lib.aligned_fields(xs, D % 4 == 0)
         dev = xs[0].device
         y = torch.empty((B, 1), dtype=torch.float32, device=dev)
         S = torch.empty((B, D), dtype=torch.float32, device=dev)
@@ -26,6 +27,7 @@ class _FMFunction(torch.autograd.Function):
         S, *xs = ctx.saved_tensors
         B, D = S.shape
         F = len(xs)
+        xs = _lib.aligned_fields(xs, D % 4 == 0)
         gy = _lib.f32c(gy, 'grad').reshape(-1)
         dx = torch.empty((F, B, D), dtype=torch.float32, device=S.device)
         ptrs = _lib.ptr_array(xs, S.device)

@@ -5,6 +5,11 @@ from .. import _lib
 from ._keras import Layer
 
 
+def _gram_route(which, B, F, D):
+    """the call takes the matrix-core kernels, which read float4 pieces of every field (recnow_inner_pnn_route: families 2 and 3)"""
+    return _lib.load().recnow_inner_pnn_route(which, B, F, D, 0) // 100000 in (2, 3)
+
+
 class _InnerPNNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *fields):
@@ -16,6 +21,7 @@ class _InnerPNNFunction(torch.autograd.Function):
         F = len(xs)
         if D > 64:
             raise NotImplementedError('InnerPNNLayer kernels cover embedding_dim <= 64 (the reference has no limit); got %d' % D)
+        xs = _lib.aligned_fields(xs, _gram_route(0, B, F, D))
         dev = xs[0].device
         out = torch.empty((B, F * (F - 1) // 2), dtype=torch.float32, device=dev)
         ptrs = _lib.ptr_array(xs, dev)
@@ -28,6 +34,7 @@ class _InnerPNNFunction(torch.autograd.Function):
         xs = ctx.saved_tensors
         F = len(xs)
         B, D = xs[0].shape
+        xs = _lib.aligned_fields(xs, _gram_route(1, B, F, D))
         dev = xs[0].device
         dout = _lib.f32c(dout, 'grad')
         dx = torch.empty((F, B, D), dtype=torch.float32, device=dev)

@@ -25,6 +25,18 @@ def test_header_symbols_exported_and_bound():
     assert lib.recnow_abi_version() == _lib.ABI_VERSION
 
 
+def test_route_queries_need_no_device():
+    """ABI 30: the kernel choice of FM, InnerPNN and attention_by_dot_product is a host function each (tests/test_rowop_census_cpu.py sweeps them)"""
+    from rec_now_amd import _lib
+    lib = _lib.load()
+    assert _lib.ABI_VERSION >= 30 and lib.recnow_abi_version() >= 30
+    assert lib.recnow_fm_route(0, 0, 3, 16, 1) == 0 and lib.recnow_inner_pnn_route(0, 0, 3, 16, 0) == 0 and lib.recnow_attention_dot_route(0, 0, 3, 16, 0) == 0
+    assert lib.recnow_fm_route(0, 64, 8, 16, 1) == 201004 and lib.recnow_fm_route(1, 64, 8, 16, 1) == 200004
+    assert lib.recnow_inner_pnn_route(0, 64, 8, 16, 0) == 201601 and lib.recnow_inner_pnn_route(1, 64, 8, 16, 0) == 316101
+    assert lib.recnow_attention_dot_route(0, 64, 50, 16, 0) == 200004 and lib.recnow_attention_dot_route(1, 64, 50, 16, 1) == 100016
+    assert lib.recnow_fm_route(2, 64, 8, 16, 1) == -1 and lib.recnow_inner_pnn_route(0, 64, 8, 65, 0) == -3 and lib.recnow_attention_dot_route(0, 64, 50, 257, 0) == -3
+
+
 def test_cpu_tensor_is_refused_loudly():
     import pytest
     import torch
