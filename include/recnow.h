@@ -1307,6 +1307,38 @@ int recnow_ibs_bwd(const float* q, int64_t ldq, const float* v, int64_t ldv, con
                    const float* row_logsum, const float* n_rows, const float* gout, float* dq, int64_t lddq, float* dv,
                    int64_t lddv, void* ws, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Extra negatives for the in-batch sampled softmax (C ABI 31): N rows on the item side that have no query row of their own -- uniformly
+ * sampled items (mixed negative sampling), a memory bank of earlier steps' items, or the other ranks' items after an all-gather.
+ * extra: (N, D) fp32 with row stride ld_extra (>= D); extra_ids (N) int64 or NULL -- given iff ids is; extra_log_q (N) fp32 or NULL;
+ * extra_mask (N) uint8 or NULL (NULL: every extra is on).  Extra k is a candidate of row i iff row i takes part, extra_mask[k] != 0 and not
+ * (remove_hits and ids and extra_ids[k] == ids[i]); it is never a positive.  s_{i,B+k} = <q_i, e_k> inv_tau - extra_log_q[k].  Everything
+ * else is as recnow_ibs_fwd / _bwd state it, with C(i) the larger set; with N = 0 the two entries ARE those (same kernels, same bits).
+ * The forward and dq stream the items and then, from a fresh tile, the extras through the same recnow_ibs_tile(1)-row LDS tile; the owners
+ * are the B queries, so the workspace is recnow_ibs_workspace_bytes(B, D, 0) as before (16 bytes per forward workgroup) and no memory of
+ * the library's is sized by N.  recnow_ibs_extra_bwd writes
+ *   dq_i = c (sum_j (p_ij - [j == i]) v_j + sum_k p_{i,B+k} e_k),   dv as recnow_ibs_bwd,   de_k = c sum_{i takes part} p_{i,B+k} q_i
+ * de: (N, D) with row stride ldde, written by a launch of its own that owns recnow_ibs_tile(0) extras per workgroup and streams the queries
+ * with their saved statistic; extras with extra_mask 0 may hold anything (NaN included) and get 0.  Each of dq, dv, de may be NULL: that
+ * orientation is not launched.  Backward workspace: 0.  B == 0: RECNOW_OK without a launch (de is not written).
+ * RECNOW_EINVAL: N < 0, ld_extra < D, a missing pointer with N > 0, ids without extra_ids or the reverse; RECNOW_EUNSUPPORTED: N > 2^30.
+ * recnow_ibs_extra_launches(which, vec): host-only count of the launches so far of which 0 (a forward with an extra segment), 1 (a dq with
+ * one), 2 (de, counted by its owner side) and 3 (de, by its streamed side); vec 1: 16-byte accesses were used for the extras (which 0 to 2)
+ * or the queries (which 3), vec 0: guarded 4-byte accesses.  Negative outside those ranges.  These launches are not in recnow_ibs_launches;
+ * the dv launch of recnow_ibs_extra_bwd is.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t recnow_ibs_extra_launches(int which, int vec);
+int recnow_ibs_extra_fwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                         const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                         const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                         float* row_max, float* row_logsum, float* row_pos, float* row_loss, float* loss, float* n_rows, void* ws,
+                         size_t ws_bytes, void* stream);
+int recnow_ibs_extra_bwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                         const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                         const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                         const float* row_max, const float* row_logsum, const float* n_rows, const float* gout, float* dq,
+                         int64_t lddq, float* dv, int64_t lddv, float* de, int64_t ldde, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and

@@ -25,5 +25,6 @@
 // 27: recnow_afm_fwd / _bwd / _supported / _route / _workspace_bytes (AFMLayer);
 // 28: recnow_gemm_route / recnow_gemm_route_info (the planned route of recnow_gemm, queryable);
 // 29: recnow_ibs_fwd / _bwd / _supported / _workspace_bytes / _tile / _launches (the in-batch sampled-softmax retrieval loss);
-// 30: recnow_fm_route, recnow_inner_pnn_route, recnow_attention_dot_route (the kernel choice of FM, InnerPNN and attention_by_dot_product, queryable).
-extern "C" int recnow_abi_version(void) { return 30; }
+// 30: recnow_fm_route, recnow_inner_pnn_route, recnow_attention_dot_route (the kernel choice of FM, InnerPNN and attention_by_dot_product, queryable);
+// 31: recnow_ibs_extra_fwd / _extra_bwd / _extra_launches (extra negatives for the in-batch sampled softmax: sampled items, a bank, other ranks).
+extern "C" int recnow_abi_version(void) { return 31; }

@@ -10,6 +10,9 @@
 //   MODE 0, forward:  owner = queries, streamed = items.  Running (maximum, rescaled sum) per lane, merged across the half-waves at the end.
 //   MODE 1, dq:       owner = queries, streamed = items.  p from the owner's saved statistic.
 //   MODE 2, dv:       owner = items,   streamed = queries.  p from the streamed rows' saved statistic (staged in LDS with the tile).
+// Extra negatives (recnow_ibs_extra_*): N item-side rows with no query row of their own.  The streamed side is a
+// list of segments; the forward and dq stream the items (a segment with a diagonal), then the extras (one without), each segment from a
+// fresh tile.  dv is the square launch unchanged.  de is MODE 2 with the extras as owners and the queries streamed without a diagonal.
 // In the backward modes the 16 weights  w_e = p - [diagonal]  of a lane are fed STRAIGHT BACK as the B operand of the second product
 // out^T (d, n) += Y^T (d, m) w (m, n):  step e of it contracts over the two streamed rows m_e(h = 0), m_e(h = 1), and the A operand is read
 // from the LDS tile at exactly those rows (a permuted k index; no shuffle, no LDS round trip of the weights).
@@ -25,16 +28,28 @@
 #define IB_THREADS 128
 typedef float ib_f16v __attribute__((ext_vector_type(16)));
 
-struct IbArgs {
-    const float* own; int64_t ldo;              // owner-side rows
-    const float* str; int64_t lds;              // streamed-side rows
+// One side of the product: rows with their per-row id, logQ correction, on-flag and (backward) saved statistic.  The owner side is one of
+// these; the streamed side is a short list of them, walked segment by segment, each from a fresh tile to its own ragged tile.  has_diag: the
+// segment's row k is the positive of owner row k (the batch against itself); a segment without one (the extra negatives, or the queries
+// streamed past extras that own) holds candidates only.
+struct IbSide {
+    const float* rows; int64_t ld; int64_t count;
     const int64_t* ids; const float* log_q; const uint8_t* mask;
-    int64_t B; int D; float inv_tau; int remove_hits;
-    float* row_max; float* row_logsum; float* row_pos; float* row_loss; double* part;                    // MODE 0
-    const float* st_max; const float* st_logsum; const float* n_rows; const float* gout; float* dout; int64_t ldd;   // MODE 1, 2
+    const float* st_max; const float* st_logsum;
+    int has_diag;
 };
 
-template <int NC, int MODE>
+struct IbArgs {
+    IbSide own;                                 // owner-side rows
+    IbSide seg[2]; int nseg;                    // streamed-side rows
+    int D; float inv_tau; int remove_hits;
+    float* row_max; float* row_logsum; float* row_pos; float* row_loss; double* part;                    // MODE 0
+    const float* n_rows; const float* gout; float* dout; int64_t ldd;                                    // MODE 1, 2
+};
+
+// XT 0: the square loss -- one streamed segment, the batch, with its diagonal (both known at compile time).  XT 1: the segment list is read
+// from the arguments: items then extras (MODE 0, 1), or the queries past owning extras (MODE 2, "de").
+template <int NC, int MODE, int XT>
 __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
     constexpr int DP = NC * 32, LD = DP + 4;    // + 4: the 16 lanes of a ds_read_b128 phase fall on 64 distinct banks, rows stay 16-byte aligned
     __shared__ __attribute__((aligned(16))) float sY[IB_TN * LD];
@@ -46,29 +61,28 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
     __shared__ float sRedL[IB_ROWS];
     __shared__ int sRedN[IB_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, h = lane >> 5;
-    const int64_t B = a.B;
     const int D = a.D;
     const int64_t og = (int64_t)blockIdx.x * IB_ROWS + wave * 32 + n;
-    const bool o_in = og < B;
-    const bool o_on = o_in && (a.mask == nullptr || a.mask[o_in ? og : 0] != 0);
-    const bool use_ids = a.ids != nullptr && a.remove_hits != 0;
-    const int64_t o_id = (use_ids && o_in) ? a.ids[og] : 0;
+    const bool o_in = og < a.own.count;
+    const bool o_on = o_in && (a.own.mask == nullptr || a.own.mask[o_in ? og : 0] != 0);
+    const bool use_ids = a.own.ids != nullptr && a.remove_hits != 0;
+    const int64_t o_id = (use_ids && o_in) ? a.own.ids[og] : 0;
     const float inv_tau = a.inv_tau;
 
     // the owner rows as B-operand fragments: MFMA step 4 j + u contracts over the columns 8 j + u (h = 0) and 8 j + 4 + u (h = 1)
     rn_f4 x[NC * 4];
     {
-        const bool ovec = rn_vec4_ok(a.own, D, a.ldo);
+        const bool ovec = rn_vec4_ok(a.own.rows, D, a.own.ld);
 #pragma unroll
         for (int j = 0; j < NC * 4; ++j) {
             const int col = 8 * j + 4 * h;
             rn_f4 z = {0.f, 0.f, 0.f, 0.f};
-            x[j] = (o_on && col < D) ? rn_ld4(a.own + og * a.ldo + col, D - col, ovec) : z;
+            x[j] = (o_on && col < D) ? rn_ld4(a.own.rows + og * a.own.ld + col, D - col, ovec) : z;
         }
     }
     float o_lq = 0.f, o_max = 0.f, o_ls = 0.f;
-    if (MODE == 2 && a.log_q != nullptr && o_in) o_lq = a.log_q[og];
-    if (MODE == 1 && o_on) { o_max = a.st_max[og]; o_ls = a.st_logsum[og]; }
+    if (MODE == 2 && a.own.log_q != nullptr && o_in) o_lq = a.own.log_q[og];
+    if (MODE == 1 && o_on) { o_max = a.own.st_max[og]; o_ls = a.own.st_logsum[og]; }
 
     const float NEG_INF = -__builtin_inff();
     float run_m = NEG_INF, run_s = 0.f, pos = 0.f;             // MODE 0
@@ -78,25 +92,34 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[c][e] = 0.f;
 
-    const bool svec = rn_vec4_ok(a.str, D, a.lds);
-    for (int64_t s0 = 0; s0 < B; s0 += IB_TN) {
+    // One loop over the tiles of all segments (a nest of two would keep a second copy of the accumulators): the batch segment's tiles first,
+    // in the order of the square loss, then -- from a fresh tile -- the second segment's.  de streams the queries alone.
+    // The walk is over streamed rows: the first segment's span is rounded up to whole tiles where a second one follows it.
+    const int64_t span0 = XT ? (a.seg[0].count + IB_TN - 1) / IB_TN * IB_TN : a.seg[0].count;
+    const int64_t span = span0 + ((XT && MODE != 2 && a.nseg > 1) ? a.seg[1].count : 0);
+    for (int64_t sw = 0; sw < span; sw += IB_TN) {
+        const int si = (XT && sw >= span0) ? 1 : 0;
+        const IbSide& g = a.seg[si];
+        const int64_t s0 = si ? sw - span0 : sw;
+        const int64_t og_d = (XT && g.has_diag == 0) ? -1 : og;  // the streamed row that is this owner's positive; none in a segment without a diagonal
+        const bool svec = rn_vec4_ok(g.rows, D, g.ld);           // the access width is a segment's own
         __syncthreads();                                       // the tile before this one has been read
         if (tid < IB_TN) {
             const int64_t sg = s0 + tid;
-            const bool in = sg < B;
-            const bool on = in && (a.mask == nullptr || a.mask[in ? sg : 0] != 0);
+            const bool in = sg < g.count;
+            const bool on = in && (g.mask == nullptr || g.mask[in ? sg : 0] != 0);
             sOn[tid] = on ? 1 : 0;
-            sId[tid] = (use_ids && in) ? a.ids[sg] : 0;
-            if (MODE != 2) sLq[tid] = (a.log_q != nullptr && in) ? a.log_q[sg] : 0.f;
-            if (MODE == 2) { sMax[tid] = on ? a.st_max[sg] : 0.f; sLs[tid] = on ? a.st_logsum[sg] : 0.f; }
+            sId[tid] = (use_ids && in) ? g.ids[sg] : 0;
+            if (MODE != 2) sLq[tid] = (g.log_q != nullptr && in) ? g.log_q[sg] : 0.f;
+            if (MODE == 2) { sMax[tid] = on ? g.st_max[sg] : 0.f; sLs[tid] = on ? g.st_logsum[sg] : 0.f; }
         }
         for (int idx = tid; idx < IB_TN * (DP / 4); idx += IB_THREADS) {
             const int r = idx / (DP / 4), c = (idx % (DP / 4)) * 4;
             const int64_t sg = s0 + r;
-            const bool in = sg < B;
-            const bool on = in && (a.mask == nullptr || a.mask[in ? sg : 0] != 0);
+            const bool in = sg < g.count;
+            const bool on = in && (g.mask == nullptr || g.mask[in ? sg : 0] != 0);
             rn_f4 z = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<rn_f4*>(&sY[r * LD + c]) = (on && c < D) ? rn_ld4(a.str + sg * a.lds + c, D - c, svec) : z;
+            *reinterpret_cast<rn_f4*>(&sY[r * LD + c]) = (on && c < D) ? rn_ld4(g.rows + sg * g.ld + c, D - c, svec) : z;
         }
         __syncthreads();
 
@@ -116,14 +139,15 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
             }
         }
 
-        // logits, candidates: s_ij = <q_i, v_j> / tau - log_q[j]; the candidate test is symmetric in (owner, streamed)
+        // logits, candidates: s_ij = <q_i, v_j> / tau - log_q[j]; the candidate test is symmetric in (owner, streamed).  A segment without
+        // a diagonal has diag[e] false throughout: no positive is picked up there and no "- 1" can be selected into a weight
         float sv[16];
         bool valid[16], diag[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int m = 8 * (e >> 2) + 4 * h + (e & 3);
             const int64_t sg = s0 + m;
-            diag[e] = sg == og;
+            diag[e] = sg == og_d;
             const bool same = use_ids && sId[m] == o_id;
             valid[e] = o_on && sOn[m] != 0 && (diag[e] || !same);
             sv[e] = t[e] * inv_tau - (MODE == 2 ? o_lq : sLq[m]);
@@ -225,21 +249,35 @@ __global__ void __launch_bounds__(256) k_ibs_mean(const double* __restrict__ par
 }
 
 static int64_t g_ibs_launches[8][2];
+static int64_t g_ibsx_launches[4][2];
 
-template <int MODE>
+static IbSide ibs_side(const float* rows, int64_t ld, int64_t count, const int64_t* ids, const float* log_q, const uint8_t* mask,
+                       const float* st_max, const float* st_logsum, int has_diag) {
+    IbSide s = {rows, ld, count, ids, log_q, mask, st_max, st_logsum, has_diag};
+    return s;
+}
+
+template <int MODE, int XT>
 static int ibs_launch(const IbArgs& a, hipStream_t st) {
     const int nc = (a.D + IB_DG - 1) / IB_DG;
-    const int grid = rn_cdiv(a.B, IB_ROWS);
+    const int grid = rn_cdiv(a.own.count, IB_ROWS);
     switch (nc) {
-        case 1: hipLaunchKernelGGL((k_ibs<1, MODE>), grid, IB_THREADS, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_ibs<2, MODE>), grid, IB_THREADS, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((k_ibs<3, MODE>), grid, IB_THREADS, 0, st, a); break;
-        default: hipLaunchKernelGGL((k_ibs<4, MODE>), grid, IB_THREADS, 0, st, a); break;
+        case 1: hipLaunchKernelGGL((k_ibs<1, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((k_ibs<2, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
+        case 3: hipLaunchKernelGGL((k_ibs<3, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
+        default: hipLaunchKernelGGL((k_ibs<4, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
     }
     RN_LAUNCH_CHECK();
-    const auto vec = [&](const void* p, int64_t ld) { return ((a.D & 3) == 0 && (ld & 3) == 0 && ((uintptr_t)p & 15) == 0) ? 1 : 0; };
-    ++g_ibs_launches[MODE][vec(a.own, a.ldo)];
-    ++g_ibs_launches[MODE + 4][vec(a.str, a.lds)];
+    const auto vec = [&](const IbSide& s) { return ((a.D & 3) == 0 && (s.ld & 3) == 0 && ((uintptr_t)s.rows & 15) == 0) ? 1 : 0; };
+    if (!XT) {
+        ++g_ibs_launches[MODE][vec(a.own)];
+        ++g_ibs_launches[MODE + 4][vec(a.seg[0])];
+    } else if (MODE != 2) {
+        ++g_ibsx_launches[MODE][vec(a.seg[1])];          // forward / dq with an extra segment: the extras' width
+    } else {
+        ++g_ibsx_launches[2][vec(a.own)];                // de: the extras own,
+        ++g_ibsx_launches[3][vec(a.seg[0])];             // the queries are streamed
+    }
     return RECNOW_OK;
 }
 
@@ -265,11 +303,84 @@ extern "C" int64_t recnow_ibs_launches(int orientation, int vec) {
     return g_ibs_launches[orientation][vec];
 }
 
+extern "C" int64_t recnow_ibs_extra_launches(int which, int vec) {
+    if (which < 0 || which > 3 || vec < 0 || vec > 1) return RECNOW_EINVAL;
+    return g_ibsx_launches[which][vec];
+}
+
 static int ibs_check(const float* q, int64_t ldq, const float* v, int64_t ldv, int64_t B, int D) {
     if (B < 0 || D < 1) return RECNOW_EINVAL;
     if (!recnow_ibs_supported(B, D)) return RECNOW_EUNSUPPORTED;
     if (B > 0 && (!q || !v || ldq < D || ldv < D)) return RECNOW_EINVAL;
     if (B > ((int64_t)1 << 30)) return RECNOW_EUNSUPPORTED;
+    return RECNOW_OK;
+}
+
+// The extras of the _extra entries.  Ids come in pairs: the hit test compares one side's with the other's.
+static int ibs_check_extra(const float* extra, int64_t ld_extra, const int64_t* ids, const int64_t* extra_ids, int64_t N, int D) {
+    if (N < 0) return RECNOW_EINVAL;
+    if (N > 0 && (!extra || ld_extra < D || (ids == nullptr) != (extra_ids == nullptr))) return RECNOW_EINVAL;
+    if (N > ((int64_t)1 << 30)) return RECNOW_EUNSUPPORTED;
+    return RECNOW_OK;
+}
+
+// The forward of both entries; ex: the extras as a second streamed segment, or NULL (the square loss, today's kernels).
+static int ibs_fwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q, const uint8_t* mask,
+                   const IbSide* ex, int64_t B, int D, float inv_tau, int remove_hits, float* row_max, float* row_logsum, float* row_pos,
+                   float* row_loss, float* loss, float* n_rows, void* ws, size_t ws_bytes, void* stream) {
+    if (!row_max || !row_logsum || !row_pos || !row_loss || !loss || !n_rows || !(inv_tau > 0.f)) return RECNOW_EINVAL;
+    if (!ws || ws_bytes < recnow_ibs_workspace_bytes(B, D, 0) || ((uintptr_t)ws & 7) != 0) return RECNOW_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    IbArgs a = {};
+    a.own = ibs_side(q, ldq, B, ids, log_q, mask, nullptr, nullptr, 0);
+    a.seg[0] = ibs_side(v, ldv, B, ids, log_q, mask, nullptr, nullptr, 1);
+    a.nseg = 1;
+    a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits;
+    a.row_max = row_max; a.row_logsum = row_logsum; a.row_pos = row_pos; a.row_loss = row_loss; a.part = (double*)ws;
+    if (ex) { a.seg[1] = *ex; a.nseg = 2; }
+    const int lrc = ex ? ibs_launch<0, 1>(a, st) : ibs_launch<0, 0>(a, st);
+    if (lrc != RECNOW_OK) return lrc;
+    hipLaunchKernelGGL(k_ibs_mean, 1, 256, 0, st, (const double*)ws, rn_cdiv(B, IB_ROWS), loss, n_rows);
+    RN_LAUNCH_CHECK();
+    return RECNOW_OK;
+}
+
+// The backward of both entries.  dq streams the items, then the extras (ex, or NULL); dv is the square launch whatever ex is: its owners are
+// the items and p reaches it through the queries' saved statistic; de (ex and de given) has the extras own and streams the queries.
+static int ibs_bwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q, const uint8_t* mask,
+                   const IbSide* ex, int64_t B, int D, float inv_tau, int remove_hits, const float* row_max, const float* row_logsum,
+                   const float* n_rows, const float* gout, float* dq, int64_t lddq, float* dv, int64_t lddv, float* de, int64_t ldde,
+                   void* stream) {
+    if (!row_max || !row_logsum || !n_rows || !gout || !(inv_tau > 0.f)) return RECNOW_EINVAL;
+    if ((dq && lddq < D) || (dv && lddv < D) || (de && ldde < D)) return RECNOW_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    IbArgs a = {};
+    a.nseg = 1;
+    a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits; a.n_rows = n_rows; a.gout = gout;
+    if (dq) {
+        a.own = ibs_side(q, ldq, B, ids, log_q, mask, row_max, row_logsum, 0);
+        a.seg[0] = ibs_side(v, ldv, B, ids, log_q, mask, nullptr, nullptr, 1);
+        if (ex) { a.seg[1] = *ex; a.nseg = 2; }
+        a.dout = dq; a.ldd = lddq;
+        const int lrc = ex ? ibs_launch<1, 1>(a, st) : ibs_launch<1, 0>(a, st);
+        if (lrc != RECNOW_OK) return lrc;
+        a.seg[1] = IbSide{};                     // dv and de stream one segment: nothing of dq's second one stays behind
+        a.nseg = 1;
+    }
+    if (dv) {
+        a.own = ibs_side(v, ldv, B, ids, log_q, mask, nullptr, nullptr, 0);
+        a.seg[0] = ibs_side(q, ldq, B, ids, nullptr, mask, row_max, row_logsum, 1);
+        a.dout = dv; a.ldd = lddv;
+        const int lrc = ibs_launch<2, 0>(a, st);
+        if (lrc != RECNOW_OK) return lrc;
+    }
+    if (ex && de) {
+        a.own = *ex;
+        a.seg[0] = ibs_side(q, ldq, B, ids, nullptr, mask, row_max, row_logsum, 0);
+        a.dout = de; a.ldd = ldde;
+        const int lrc = ibs_launch<2, 1>(a, st);
+        if (lrc != RECNOW_OK) return lrc;
+    }
     return RECNOW_OK;
 }
 
@@ -279,18 +390,8 @@ extern "C" int recnow_ibs_fwd(const float* q, int64_t ldq, const float* v, int64
     const int rc = ibs_check(q, ldq, v, ldv, B, D);
     if (rc != RECNOW_OK) return rc;
     if (B == 0) return RECNOW_OK;
-    if (!row_max || !row_logsum || !row_pos || !row_loss || !loss || !n_rows || !(inv_tau > 0.f)) return RECNOW_EINVAL;
-    if (!ws || ws_bytes < recnow_ibs_workspace_bytes(B, D, 0) || ((uintptr_t)ws & 7) != 0) return RECNOW_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    IbArgs a = {};
-    a.own = q; a.ldo = ldq; a.str = v; a.lds = ldv; a.ids = ids; a.log_q = log_q; a.mask = mask;
-    a.B = B; a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits;
-    a.row_max = row_max; a.row_logsum = row_logsum; a.row_pos = row_pos; a.row_loss = row_loss; a.part = (double*)ws;
-    const int lrc = ibs_launch<0>(a, st);
-    if (lrc != RECNOW_OK) return lrc;
-    hipLaunchKernelGGL(k_ibs_mean, 1, 256, 0, st, (const double*)ws, rn_cdiv(B, IB_ROWS), loss, n_rows);
-    RN_LAUNCH_CHECK();
-    return RECNOW_OK;
+    return ibs_fwd(q, ldq, v, ldv, ids, log_q, mask, nullptr, B, D, inv_tau, remove_hits, row_max, row_logsum, row_pos, row_loss, loss, n_rows,
+                   ws, ws_bytes, stream);
 }
 
 extern "C" int recnow_ibs_bwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
@@ -301,21 +402,36 @@ extern "C" int recnow_ibs_bwd(const float* q, int64_t ldq, const float* v, int64
     const int rc = ibs_check(q, ldq, v, ldv, B, D);
     if (rc != RECNOW_OK) return rc;
     if (B == 0) return RECNOW_OK;
-    if (!row_max || !row_logsum || !n_rows || !gout || !(inv_tau > 0.f)) return RECNOW_EINVAL;
-    if ((dq && lddq < D) || (dv && lddv < D)) return RECNOW_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    IbArgs a = {};
-    a.ids = ids; a.log_q = log_q; a.mask = mask; a.B = B; a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits;
-    a.st_max = row_max; a.st_logsum = row_logsum; a.n_rows = n_rows; a.gout = gout;
-    if (dq) {
-        a.own = q; a.ldo = ldq; a.str = v; a.lds = ldv; a.dout = dq; a.ldd = lddq;
-        const int lrc = ibs_launch<1>(a, st);
-        if (lrc != RECNOW_OK) return lrc;
-    }
-    if (dv) {
-        a.own = v; a.ldo = ldv; a.str = q; a.lds = ldq; a.dout = dv; a.ldd = lddv;
-        const int lrc = ibs_launch<2>(a, st);
-        if (lrc != RECNOW_OK) return lrc;
-    }
-    return RECNOW_OK;
+    return ibs_bwd(q, ldq, v, ldv, ids, log_q, mask, nullptr, B, D, inv_tau, remove_hits, row_max, row_logsum, n_rows, gout, dq, lddq, dv, lddv,
+                   nullptr, 0, stream);
 }
+
+extern "C" int recnow_ibs_extra_fwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                                    const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                                    const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                                    float* row_max, float* row_logsum, float* row_pos, float* row_loss, float* loss, float* n_rows, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    int rc = ibs_check(q, ldq, v, ldv, B, D);
+    if (rc == RECNOW_OK) rc = ibs_check_extra(extra, ld_extra, ids, extra_ids, N, D);
+    if (rc != RECNOW_OK) return rc;
+    if (B == 0) return RECNOW_OK;
+    const IbSide ex = ibs_side(extra, ld_extra, N, extra_ids, extra_log_q, extra_mask, nullptr, nullptr, 0);
+    return ibs_fwd(q, ldq, v, ldv, ids, log_q, mask, N > 0 ? &ex : nullptr, B, D, inv_tau, remove_hits, row_max, row_logsum, row_pos, row_loss,
+                   loss, n_rows, ws, ws_bytes, stream);
+}
+
+extern "C" int recnow_ibs_extra_bwd(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                                    const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                                    const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                                    const float* row_max, const float* row_logsum, const float* n_rows, const float* gout, float* dq,
+                                    int64_t lddq, float* dv, int64_t lddv, float* de, int64_t ldde, void* ws, size_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    int rc = ibs_check(q, ldq, v, ldv, B, D);
+    if (rc == RECNOW_OK) rc = ibs_check_extra(extra, ld_extra, ids, extra_ids, N, D);
+    if (rc != RECNOW_OK) return rc;
+    if (B == 0) return RECNOW_OK;
+    const IbSide ex = ibs_side(extra, ld_extra, N, extra_ids, extra_log_q, extra_mask, nullptr, nullptr, 0);
+    return ibs_bwd(q, ldq, v, ldv, ids, log_q, mask, N > 0 ? &ex : nullptr, B, D, inv_tau, remove_hits, row_max, row_logsum, n_rows, gout, dq,
+                   lddq, dv, lddv, de, ldde, stream);
+}
+

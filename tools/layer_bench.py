@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax,in_batch_softmax_extra]"""
 import os
 import sys
 
@@ -1065,6 +1065,23 @@ def ibs_ref_eager(q, v, ids, lq, tau):
     return torch.nn.functional.cross_entropy(logits, torch.arange(B, device=q.device))
 
 
+def ibs_graph_ms(fn):
+    """GPU time of one step replayed from a captured graph; the graph and what it holds are released before the next measurement."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    ms = timeit(g.replay, reps, warm=2)
+    del g
+    torch.cuda.empty_cache()
+    return ms
+
+
 def in_batch_softmax():
     """in_batch_softmax_loss forward and forward + backward (dq and dv) at (B 16 384, D 64), (B 65 536, D 64) and (B 65 536, D 128), plain and
     with item ids + log_q: graph-replay GPU time, the routes in turn, twice, with the spread between the two passes; TFLOP/s of the flop model
@@ -1074,21 +1091,7 @@ def in_batch_softmax():
     tau = 0.5
     cases = [(16384, 64), (65536, 64), (65536, 128)]
     seen = {}
-
-    def graph_ms(fn):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            fn()
-        ms = timeit(g.replay, reps, warm=2)
-        del g
-        torch.cuda.empty_cache()
-        return ms
+    graph_ms = ibs_graph_ms
 
     for rnd in (1, 2):
         for B, D in cases:
@@ -1136,6 +1139,85 @@ def in_batch_softmax():
             verdict = 'no yardstick' if worst != worst else ('faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread')
             print('in_batch_softmax B=%d D=%d %s : fused %s (graph) %.3f / %.3f ms, spread between the passes %.1f %%; torch %.3f / %.3f ms; fused against torch '
                   'in the worse pairing %.2fx -> %s' % (B, D, tag, what, p, s, 100 * spread, rp, rs, worst, verdict))
+
+
+def ibs_extra_ref_eager(q, v, x, ids, lq, xids, xlq, tau):
+    """The in-batch sampled softmax with extra negatives from torch operators: cat, the (B, B + N) logits, a mask of the hits, cross_entropy."""
+    B = q.shape[0]
+    logits = q @ torch.cat([v, x]).T / tau
+    if lq is not None:
+        logits = logits - torch.cat([lq, xlq])[None, :]
+    if ids is not None:
+        hit = torch.cat([ids, xids])[None, :] == ids[:, None]
+        hit[:, :B].fill_diagonal_(False)
+        logits = logits.masked_fill(hit, float('-inf'))
+    return torch.nn.functional.cross_entropy(logits, torch.arange(B, device=q.device))
+
+
+def in_batch_softmax_extra():
+    """in_batch_softmax_loss with extra negatives, forward and forward + backward, at (B 16 384, N 49 152, D 64), (B 65 536, N 65 536, D 64)
+    and (B 65 536, N 65 536, D 128); extras trainable (dq, dv and de) and frozen (a memory bank: no de), plain and with ids + log_q.  The
+    harness of in_batch_softmax: graph-replay GPU time, the cases in turn, twice, the spread between the passes.  Flop model: forward
+    2 B (B + N) D, dq 4 B (B + N) D, dv 4 B^2 D, de 4 B N D, beside the 157.3 TFLOP/s exact-fp32 MFMA peak.  The yardstick is the torch
+    composition over the (B, B + N) logits in the same run -- 34 GB a matrix at B = N = 65 536 -- reported as such where it does not fit."""
+    from rec_now_amd.rec_block.in_batch_softmax import in_batch_softmax_loss
+    tau = 0.5
+    cases = [(16384, 49152, 64), (65536, 65536, 64), (65536, 65536, 128)]
+    seen = {}
+    graph_ms = ibs_graph_ms
+    for rnd in (1, 2):
+        for B, N, D in cases:
+            for frozen in (False, True):
+                for with_ids in (False, True):
+                    gen = torch.Generator(device=dev).manual_seed(B + D + N)
+                    q = (torch.randn(B, D, device=dev, generator=gen) * D ** -0.25).requires_grad_(True)
+                    v = (torch.randn(B, D, device=dev, generator=gen) * D ** -0.25).requires_grad_(True)
+                    x = (torch.randn(N, D, device=dev, generator=gen) * D ** -0.25).requires_grad_(not frozen)
+                    ids = torch.randint(0, B // 4, (B,), device=dev, generator=gen) if with_ids else None
+                    xids = torch.randint(0, B // 4, (N,), device=dev, generator=gen) if with_ids else None
+                    lq = torch.rand(B, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids else None
+                    xlq = torch.rand(N, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids else None
+                    run = lambda: in_batch_softmax_loss(q, v, ids, lq, tau, extra_item=x, extra_item_ids=xids, extra_log_q=xlq)      # noqa: E731
+                    ref = lambda: ibs_extra_ref_eager(q, v, x, ids, lq, xids, xlq, tau)      # noqa: E731
+                    wrt = [q, v] if frozen else [q, v, x]
+
+                    def fb_of(fn):
+                        def step():
+                            return torch.autograd.grad(fn(), wrt)
+                        return step
+
+                    def fwd_of(fn):
+                        def step():
+                            with torch.no_grad():
+                                return fn()
+                        return step
+                    ff = 2.0 * B * (B + N) * D
+                    fb = 4.0 * B * (B + N) * D + 4.0 * B * B * D + (0.0 if frozen else 4.0 * B * N * D)
+                    gf, gfb = graph_ms(fwd_of(run)), graph_ms(fb_of(run))
+                    tag = ('frozen extras' if frozen else 'trainable extras') + (' ids+log_q' if with_ids else ' plain')
+                    try:
+                        with torch.no_grad():
+                            err = abs(run().item() - ref().item())
+                        rgf, rgfb = graph_ms(fwd_of(ref)), graph_ms(fb_of(ref))
+                        fits = 'torch composition (forms (B, B + N)): fwd %.3f ms, bwd %.3f ms, fwd+bwd %.3f ms -> fused is %.2fx (fwd) %.2fx (bwd) %.2fx (fwd+bwd) | |loss - torch| %.2g' % (
+                            rgf, rgfb - rgf, rgfb, rgf / gf, (rgfb - rgf) / (gfb - gf), rgfb / gfb, err)
+                    except torch.cuda.OutOfMemoryError:
+                        rgf = rgfb = float('nan')
+                        fits = 'torch composition: DID NOT FIT (out of memory on its (B, B + N) tensors)'
+                    torch.cuda.synchronize()
+                    torch.cuda.empty_cache()
+                    print('pass %d in_batch_softmax_extra B=%d N=%d D=%d %s : fused (graph) fwd %.3f ms %.1f TFLOP/s (%.2f of 157.3), bwd %.3f ms %.1f TFLOP/s (%.2f), fwd+bwd %.3f ms | %s'
+                          % (rnd, B, N, D, tag, gf, ff / gf / 1e9, ff / gf / 1e9 / 157.3, gfb - gf, fb / (gfb - gf) / 1e9, fb / (gfb - gf) / 1e9 / 157.3, gfb, fits), flush=True)
+                    seen.setdefault((B, N, D, tag), []).append((gfb, rgfb, gf, rgf))
+                    del q, v, x, ids, lq, xids, xlq
+                    torch.cuda.empty_cache()
+    for (B, N, D, tag), ((a, ra, af, raf), (b, rb, bf, rbf)) in seen.items():
+        for what, (p, s, rp, rs) in (('fwd', (af, bf, raf, rbf)), ('bwd', (a - af, b - bf, ra - raf, rb - rbf)), ('fwd+bwd', (a, b, ra, rb))):
+            spread = abs(p - s) / min(p, s)
+            worst = min(rp, rs) / max(p, s)
+            verdict = 'no yardstick' if worst != worst else ('faster by more than the spread' if worst - 1 > spread else 'NOT faster by more than the spread')
+            print('in_batch_softmax_extra B=%d N=%d D=%d %s : fused %s (graph) %.3f / %.3f ms, spread between the passes %.1f %%; torch %.3f / %.3f ms; fused against '
+                  'torch in the worse pairing %.2fx -> %s' % (B, N, D, tag, what, p, s, 100 * spread, rp, rs, worst, verdict))
 
 
 def gnn_ref_eager(x, indices, ws, L, F):
@@ -1515,6 +1597,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax), ('in_batch_softmax_extra', in_batch_softmax_extra)):
         if name in which:
             fn()
