@@ -1340,6 +1340,30 @@ int recnow_ibs_extra_bwd(const float* q, int64_t ldq, const float* v, int64_t ld
                          int64_t lddq, float* dv, int64_t lddv, float* de, int64_t ldde, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * (ABI 32) In-batch retrieval ranks: for every taking-part row, how many candidates score above its positive.  Arguments, taking part,
+ * candidates C(i) and logits are those of recnow_ibs_extra_fwd (N = 0: no extras, extra may be NULL).  batch_candidates != 0: C(i) as in
+ * the loss.  batch_candidates == 0 (full-corpus evaluation): batch item i is row i's positive and no batch column is a candidate of any
+ * row; the candidates are the extras alone, with extra_mask and the id-hit rule.  With pos = s_ii and C'(i) = C(i) \ {i}, per row:
+ *   n_candidates[i] = |C'(i)|,   n_greater[i] = #{j in C'(i): not (s_ij <= pos)},   n_equal[i] = #{j in C'(i): s_ij == pos},
+ * (B) int64 each, and row_pos[i] = pos (float).  A NaN logit or a NaN pos counts as greater.  Rows that do not take part get 0, 0, 0
+ * and NaN and may hold anything; so may masked extras.  pos and every candidate logit are results of one and the same fp32 expression
+ * on the same MFMA chain: a candidate whose row and log_q are bit-identical to the positive's is counted equal wherever it stands, and
+ * row_pos is, bit for bit, the row_pos of recnow_ibs_fwd / recnow_ibs_extra_fwd.  One launch of the loss's kernel template: a workgroup
+ * owns recnow_ibs_tile(0) queries, reads its own two item tiles for pos, then walks the items (batch_candidates != 0 only) and the extras
+ * in tiles of recnow_ibs_tile(1) rows.  No workspace, no atomics, each row written once: the same input gives the same bits on every
+ * run.  B == 0: RECNOW_OK without a launch.  Errors as recnow_ibs_extra_fwd; RECNOW_EINVAL for a NULL output or inv_tau <= 0.
+ * recnow_ibs_rank_launches(which, vec): host-only count of the rank launches so far whose queries (which 0), items (which 1) or extras
+ * (which 2; launches with N > 0 only) took 16-byte (vec 1) or guarded 4-byte (vec 0) accesses; which 3: launches that walked the item
+ * segment (vec 1) or left it to the two tiles of the positives (vec 0).  Negative outside those ranges.  Rank launches are in neither
+ * recnow_ibs_launches nor recnow_ibs_extra_launches.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t recnow_ibs_rank_launches(int which, int vec);
+int recnow_ibs_rank(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                    const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                    const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                    int batch_candidates, int64_t* n_greater, int64_t* n_equal, int64_t* n_candidates, float* row_pos, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

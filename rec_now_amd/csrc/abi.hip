@@ -26,5 +26,6 @@
 // 28: recnow_gemm_route / recnow_gemm_route_info (the planned route of recnow_gemm, queryable);
 // 29: recnow_ibs_fwd / _bwd / _supported / _workspace_bytes / _tile / _launches (the in-batch sampled-softmax retrieval loss);
 // 30: recnow_fm_route, recnow_inner_pnn_route, recnow_attention_dot_route (the kernel choice of FM, InnerPNN and attention_by_dot_product, queryable);
-// 31: recnow_ibs_extra_fwd / _extra_bwd / _extra_launches (extra negatives for the in-batch sampled softmax: sampled items, a bank, other ranks).
-extern "C" int recnow_abi_version(void) { return 31; }
+// 31: recnow_ibs_extra_fwd / _extra_bwd / _extra_launches (extra negatives for the in-batch sampled softmax: sampled items, a bank, other ranks);
+// 32: recnow_ibs_rank / _rank_launches (in-batch retrieval ranks: recall@K, NDCG@K, MRR and mean rank from per-row counts).
+extern "C" int recnow_abi_version(void) { return 32; }

@@ -2,7 +2,7 @@
 // correction, the removal of accidental hits and a temperature.  Two-sided flash attention with one "value" per row, in exact fp32, and never
 // a (B, B) tensor.  DESIGN.md section 8z.
 //
-// One kernel template, three uses.  A workgroup of two waves OWNS 64 rows of one side (a wave 32 of them, as B-operand fragments in
+// One kernel template, four uses.  A workgroup of two waves OWNS 64 rows of one side (a wave 32 of them, as B-operand fragments in
 // registers for the whole launch) and STREAMS the other side through LDS in tiles of 32 rows.  The logit tile is formed TRANSPOSED on
 // v_mfma_f32_32x32x2_f32 -- streamed rows are the MFMA rows, owner rows the MFMA columns -- so that lane (n, h) = (lane & 31, lane >> 5)
 // holds, for owner row n, the 16 streamed rows  m_e = 8 (e / 4) + 4 h + e % 4:  a row reduction is 16 register steps and ONE exchange
@@ -10,6 +10,10 @@
 //   MODE 0, forward:  owner = queries, streamed = items.  Running (maximum, rescaled sum) per lane, merged across the half-waves at the end.
 //   MODE 1, dq:       owner = queries, streamed = items.  p from the owner's saved statistic.
 //   MODE 2, dv:       owner = items,   streamed = queries.  p from the streamed rows' saved statistic (staged in LDS with the tile).
+//   MODE 3, ranks:    owner = queries, streamed = items, then extras.  Three integer counts per lane -- the candidates other than the positive,
+//                     those above it, those equal to it -- merged across the half-waves at the end (recnow_ibs_rank).
+//                     The positive's logit has to be known before anything is compared with it: two tiles AHEAD of the walk, the two of
+//                     the diagonal segment that hold the workgroup's own positives, go through the same loop body and only pick it up.
 // Extra negatives (recnow_ibs_extra_*): N item-side rows with no query row of their own.  The streamed side is a
 // list of segments; the forward and dq stream the items (a segment with a diagonal), then the extras (one without), each segment from a
 // fresh tile.  dv is the square launch unchanged.  de is MODE 2 with the extras as owners and the queries streamed without a diagonal.
@@ -45,6 +49,7 @@ struct IbArgs {
     int D; float inv_tau; int remove_hits;
     float* row_max; float* row_logsum; float* row_pos; float* row_loss; double* part;                    // MODE 0
     const float* n_rows; const float* gout; float* dout; int64_t ldd;                                    // MODE 1, 2
+    int64_t* n_greater; int64_t* n_equal; int64_t* n_cand; int walk_diag;                                // MODE 3 (row_pos too)
 };
 
 // XT 0: the square loss -- one streamed segment, the batch, with its diagonal (both known at compile time).  XT 1: the segment list is read
@@ -85,7 +90,8 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
     if (MODE == 1 && o_on) { o_max = a.own.st_max[og]; o_ls = a.own.st_logsum[og]; }
 
     const float NEG_INF = -__builtin_inff();
-    float run_m = NEG_INF, run_s = 0.f, pos = 0.f;             // MODE 0
+    float run_m = NEG_INF, run_s = 0.f, pos = 0.f;             // MODE 0; pos: MODE 3 too
+    int n_gt = 0, n_eq = 0, n_cd = 0;                          // MODE 3: a lane sees half of at most 2^31 streamed rows
     ib_f16v acc[NC];                                           // MODE 1, 2: out^T, 32 columns d per block
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -97,10 +103,15 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
     // The walk is over streamed rows: the first segment's span is rounded up to whole tiles where a second one follows it.
     const int64_t span0 = XT ? (a.seg[0].count + IB_TN - 1) / IB_TN * IB_TN : a.seg[0].count;
     const int64_t span = span0 + ((XT && MODE != 2 && a.nseg > 1) ? a.seg[1].count : 0);
-    for (int64_t sw = 0; sw < span; sw += IB_TN) {
-        const int si = (XT && sw >= span0) ? 1 : 0;
+    // MODE 3: the walk is preceded by two tiles (sw < 0), the workgroup's own 64 rows of the diagonal segment, and may leave that segment
+    // out (a corpus of extras alone: the batch item is a row's positive and nobody's candidate)
+    const int64_t first = MODE == 3 ? -2 * IB_TN : 0, skip = (MODE == 3 && a.walk_diag == 0) ? span0 : 0;
+    for (int64_t sw = first; sw < span - skip; sw += IB_TN) {
+        const bool ahead = MODE == 3 && sw < 0;
+        const int64_t at = ahead ? (int64_t)blockIdx.x * IB_ROWS + (sw - first) : sw + skip;     // the tile's place among the streamed rows
+        const int si = (XT && !ahead && at >= span0) ? 1 : 0;
         const IbSide& g = a.seg[si];
-        const int64_t s0 = si ? sw - span0 : sw;
+        const int64_t s0 = si ? at - span0 : at;
         const int64_t og_d = (XT && g.has_diag == 0) ? -1 : og;  // the streamed row that is this owner's positive; none in a segment without a diagonal
         const bool svec = rn_vec4_ok(g.rows, D, g.ld);           // the access width is a segment's own
         __syncthreads();                                       // the tile before this one has been read
@@ -167,6 +178,28 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
             for (int e = 0; e < 16; ++e) add += valid[e] ? ai_exp(sv[e] - new_m) : 0.f;
             run_s = run_s * scale + add;
             run_m = new_m;
+        } else if (MODE == 3) {
+            if (ahead) {
+                // the positive of a row turns up in one of the two tiles (tile  2 blockIdx.x + wave) and in one half-wave, as in the forward;
+                // it is left in LDS, where both half-waves of the row find it after the barrier that opens the next tile
+                float pk = 0.f;
+                bool got = false;
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    if (diag[e]) { pk = sv[e]; got = true; }
+                if (got) sRedL[wave * 32 + n] = pk;
+            } else {
+                pos = sRedL[wave * 32 + n];
+                // a count is a comparison of two results of the one expression above: a copy of the positive is equal wherever it stands.
+                // "not <=" and not ">": a NaN on either side counts as greater
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const bool cand = valid[e] && !diag[e];
+                    n_cd += cand ? 1 : 0;
+                    n_gt += (cand && !(sv[e] <= pos)) ? 1 : 0;
+                    n_eq += (cand && sv[e] == pos) ? 1 : 0;
+                }
+            }
         } else {
             float w[16];
 #pragma unroll
@@ -216,6 +249,19 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
             a.part[2 * (int64_t)blockIdx.x] = sum;
             a.part[2 * (int64_t)blockIdx.x + 1] = (double)cnt;
         }
+    } else if (MODE == 3) {
+        // the two half-waves of a row: one exchange; each row is written once, by its h = 0 lane.  Rows that do not take part counted nothing
+        n_gt += __shfl_xor(n_gt, 32, 64);
+        n_eq += __shfl_xor(n_eq, 32, 64);
+        n_cd += __shfl_xor(n_cd, 32, 64);
+        __syncthreads();                                                         // a launch that walks nothing comes here from the tiles ahead
+        pos = sRedL[wave * 32 + n];
+        if (h == 0 && o_in) {
+            a.n_greater[og] = n_gt;
+            a.n_equal[og] = n_eq;
+            a.n_cand[og] = n_cd;
+            a.row_pos[og] = o_on ? pos : __builtin_nanf("");
+        }
     } else {
         const float nr = a.n_rows[0];
         const float scale = nr > 0.f ? a.gout[0] * inv_tau / nr : 0.f;
@@ -250,6 +296,7 @@ __global__ void __launch_bounds__(256) k_ibs_mean(const double* __restrict__ par
 
 static int64_t g_ibs_launches[8][2];
 static int64_t g_ibsx_launches[4][2];
+static int64_t g_ibsr_launches[4][2];
 
 static IbSide ibs_side(const float* rows, int64_t ld, int64_t count, const int64_t* ids, const float* log_q, const uint8_t* mask,
                        const float* st_max, const float* st_logsum, int has_diag) {
@@ -269,7 +316,12 @@ static int ibs_launch(const IbArgs& a, hipStream_t st) {
     }
     RN_LAUNCH_CHECK();
     const auto vec = [&](const IbSide& s) { return ((a.D & 3) == 0 && (s.ld & 3) == 0 && ((uintptr_t)s.rows & 15) == 0) ? 1 : 0; };
-    if (!XT) {
+    if (MODE == 3) {                                     // a census of its own: the loss's counts are read as deltas
+        ++g_ibsr_launches[0][vec(a.own)];
+        ++g_ibsr_launches[1][vec(a.seg[0])];
+        if (a.nseg > 1) ++g_ibsr_launches[2][vec(a.seg[1])];
+        ++g_ibsr_launches[3][a.walk_diag ? 1 : 0];
+    } else if (!XT) {
         ++g_ibs_launches[MODE][vec(a.own)];
         ++g_ibs_launches[MODE + 4][vec(a.seg[0])];
     } else if (MODE != 2) {
@@ -306,6 +358,11 @@ extern "C" int64_t recnow_ibs_launches(int orientation, int vec) {
 extern "C" int64_t recnow_ibs_extra_launches(int which, int vec) {
     if (which < 0 || which > 3 || vec < 0 || vec > 1) return RECNOW_EINVAL;
     return g_ibsx_launches[which][vec];
+}
+
+extern "C" int64_t recnow_ibs_rank_launches(int which, int vec) {
+    if (which < 0 || which > 3 || vec < 0 || vec > 1) return RECNOW_EINVAL;
+    return g_ibsr_launches[which][vec];
 }
 
 static int ibs_check(const float* q, int64_t ldq, const float* v, int64_t ldv, int64_t B, int D) {
@@ -435,3 +492,24 @@ extern "C" int recnow_ibs_extra_bwd(const float* q, int64_t ldq, const float* v,
                    lddq, dv, lddv, de, ldde, stream);
 }
 
+
+// Ranks of the positives: MODE 3 over the items (walked as candidates, or read by the two tiles ahead of the walk alone) and the extras.
+extern "C" int recnow_ibs_rank(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                               const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                               const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                               int batch_candidates, int64_t* n_greater, int64_t* n_equal, int64_t* n_candidates, float* row_pos,
+                               void* stream) {
+    int rc = ibs_check(q, ldq, v, ldv, B, D);
+    if (rc == RECNOW_OK) rc = ibs_check_extra(extra, ld_extra, ids, extra_ids, N, D);
+    if (rc != RECNOW_OK) return rc;
+    if (B == 0) return RECNOW_OK;
+    if (!n_greater || !n_equal || !n_candidates || !row_pos || !(inv_tau > 0.f)) return RECNOW_EINVAL;
+    IbArgs a = {};
+    a.own = ibs_side(q, ldq, B, ids, log_q, mask, nullptr, nullptr, 0);
+    a.seg[0] = ibs_side(v, ldv, B, ids, log_q, mask, nullptr, nullptr, 1);
+    a.nseg = 1;
+    if (N > 0) { a.seg[1] = ibs_side(extra, ld_extra, N, extra_ids, extra_log_q, extra_mask, nullptr, nullptr, 0); a.nseg = 2; }
+    a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits;
+    a.row_pos = row_pos; a.n_greater = n_greater; a.n_equal = n_equal; a.n_cand = n_candidates; a.walk_diag = batch_candidates ? 1 : 0;
+    return ibs_launch<3, 1>(a, (hipStream_t)stream);
+}

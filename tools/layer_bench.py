@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax,in_batch_softmax_extra]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax,in_batch_softmax_extra,in_batch_ranks]"""
 import os
 import sys
 
@@ -1220,6 +1220,84 @@ def in_batch_softmax_extra():
                   'torch in the worse pairing %.2fx -> %s' % (B, N, D, tag, what, p, s, 100 * spread, rp, rs, worst, verdict))
 
 
+def ibs_rank_ref_eager(q, v, x, ids, lq, xids, xlq, tau, in_batch):
+    """The rank of the positives from torch operators: cat, the (B, B + N) logits, masked_fill of the hits (and of the batch columns where the
+    corpus alone holds the candidates), (s > pos).sum(1)."""
+    B = q.shape[0]
+    s = q @ (v if x is None else torch.cat([v, x])).T / tau
+    if lq is not None:
+        s = s - (lq if x is None else torch.cat([lq, xlq]))[None, :]
+    pos = s.diagonal().clone()
+    if ids is not None:
+        drop = (ids if x is None else torch.cat([ids, xids]))[None, :] == ids[:, None]
+    else:
+        drop = torch.zeros(s.shape, dtype=torch.bool, device=s.device)
+    if in_batch:
+        drop[:, :B].fill_diagonal_(True)
+    else:
+        drop[:, :B] = True
+    return (s.masked_fill(drop, float('-inf')) > pos[:, None]).sum(1)
+
+
+def in_batch_ranks():
+    """in_batch_ranks (the count launch every retrieval metric is made of) at (B 16 384, N 49 152, D 64), (B 65 536, N 65 536, D 64 and 128)
+    and the square B 65 536, D 64: plain, with ids + log_q, and once with in_batch_candidates=False (the corpus alone).  The harness of
+    in_batch_softmax_extra: graph-replay GPU time, the cases in turn, twice, the spread between the passes.  Two yardsticks in the same run:
+    the forward of in_batch_softmax_loss at the same shape (the same tiles and MFMAs plus the exponentials, less the two tiles of the
+    positives), and the torch composition over the (B, B + N) logits -- reported as such where it does not fit.  Flop model: 2 B C D with C
+    the streamed candidates (B + N, or N for the corpus alone), beside the 157.3 TFLOP/s exact-fp32 MFMA peak."""
+    from rec_now_amd.rec_block.in_batch_softmax import in_batch_softmax_loss
+    from rec_now_amd.rec_block.retrieval_metrics import in_batch_ranks as ranks
+    tau = 0.5
+    cases = [(16384, 49152, 64), (65536, 65536, 64), (65536, 65536, 128), (65536, 0, 64)]
+    seen = {}
+    for rnd in (1, 2):
+        for B, N, D in cases:
+            for tag, with_ids, in_batch in (('plain', False, True), ('ids+log_q', True, True), ('corpus alone', False, False)):
+                if N == 0 and not in_batch:
+                    continue
+                gen = torch.Generator(device=dev).manual_seed(B + D + N)
+                q = torch.randn(B, D, device=dev, generator=gen) * D ** -0.25
+                v = torch.randn(B, D, device=dev, generator=gen) * D ** -0.25
+                x = torch.randn(N, D, device=dev, generator=gen) * D ** -0.25 if N else None
+                ids = torch.randint(0, B // 4, (B,), device=dev, generator=gen) if with_ids else None
+                xids = torch.randint(0, B // 4, (N,), device=dev, generator=gen) if with_ids and N else None
+                lq = torch.rand(B, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids else None
+                xlq = torch.rand(N, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids and N else None
+                kw = dict(extra_item=x, extra_item_ids=xids, extra_log_q=xlq)
+                run = lambda: ranks(q, v, ids, lq, tau, in_batch_candidates=in_batch, **kw).n_greater      # noqa: E731
+                ref = lambda: ibs_rank_ref_eager(q, v, x, ids, lq, xids, xlq, tau, in_batch)      # noqa: E731
+
+                def loss():
+                    with torch.no_grad():
+                        return in_batch_softmax_loss(q, v, ids, lq, tau, **kw)
+                flops = 2.0 * B * ((B if in_batch else 0) + N) * D
+                g_rank, g_loss = ibs_graph_ms(run), (ibs_graph_ms(loss) if in_batch else float('nan'))
+                try:
+                    diff = (run() != ref()).sum().item()
+                    g_ref = ibs_graph_ms(ref)
+                    fits = 'torch composition (forms (B, B + N)) %.3f ms -> fused is %.2fx | rows whose n_greater differs from torch %d of %d' % (
+                        g_ref, g_ref / g_rank, diff, B)
+                except torch.cuda.OutOfMemoryError:
+                    g_ref = float('nan')
+                    fits = 'torch composition: DID NOT FIT (out of memory on its (B, B + N) tensors)'
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                print('pass %d in_batch_ranks B=%d N=%d D=%d %s : ranks (graph) %.3f ms %.1f TFLOP/s (%.2f of 157.3) | loss forward, same shape %.3f ms -> ranks / forward %.3f | %s'
+                      % (rnd, B, N, D, tag, g_rank, flops / g_rank / 1e9, flops / g_rank / 1e9 / 157.3, g_loss, g_rank / g_loss, fits), flush=True)
+                seen.setdefault((B, N, D, tag), []).append((g_rank, g_loss, g_ref))
+                del q, v, x, ids, lq, xids, xlq, kw
+                torch.cuda.empty_cache()
+    for (B, N, D, tag), ((a, la, ra), (b, lb, rb)) in seen.items():
+        spread = max(abs(a - b) / min(a, b), abs(la - lb) / min(la, lb) if la == la else 0.0)
+        against = max(a, b) / min(la, lb) if la == la else float('nan')        # the worse pairing: the slower rank pass over the faster forward
+        verdict = 'no forward to compare with (the loss has no such candidate set)' if against != against else (
+            'no slower than the forward beyond the spread' if against - 1 <= spread else 'SLOWER than the forward beyond the spread')
+        print('in_batch_ranks B=%d N=%d D=%d %s : ranks (graph) %.3f / %.3f ms, loss forward %.3f / %.3f ms, largest spread between the passes %.1f %%; '
+              'ranks / forward in the worse pairing %.3f -> %s; torch %.3f / %.3f ms, fused against torch in the worse pairing %.2fx'
+              % (B, N, D, tag, a, b, la, lb, 100 * spread, against, verdict, ra, rb, min(ra, rb) / max(a, b)))
+
+
 def gnn_ref_eager(x, indices, ws, L, F):
     """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
     from the weight vector, matmul, add, tanh; transpose back and flatten."""
@@ -1597,6 +1675,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax), ('in_batch_softmax_extra', in_batch_softmax_extra)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax), ('in_batch_softmax_extra', in_batch_softmax_extra), ('in_batch_ranks', in_batch_ranks)):
         if name in which:
             fn()
