@@ -1364,6 +1364,32 @@ int recnow_ibs_rank(const float* q, int64_t ldq, const float* v, int64_t ldv, co
                     int batch_candidates, int64_t* n_greater, int64_t* n_equal, int64_t* n_candidates, float* row_pos, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * (ABI 33) In-batch top-K candidates: for every taking-part row, the K candidates that score highest -- hard-negative mining from the
+ * batch or a memory bank, top-K retrieval of a corpus.  Arguments, checks, taking part, C'(i) = C(i) \ {i}, the logits and
+ * batch_candidates are those of recnow_ibs_rank (N = 0 allowed); the positive is never in the list.
+ * Order: candidate a stands before candidate b iff a's score is NaN and b's is not, or score_a > score_b, or the scores compare equal
+ * (or both are NaN) and index_a < index_b.  -0.0 and 0.0 tie; NaN is greatest.  The order is total: the result is a function of the
+ * candidate set alone.  An index addresses cat(items, extras) in both candidate modes: batch column j is j, extra k is B + k.
+ * Row i of scores (B, K; float, leading dimension ld_scores >= K) and indices (B, K; int64, ld_indices >= K) holds the first
+ * min(K, |C'(i)|) candidates in that order, then the fill: score -inf, index -1.  A candidate whose logit is -inf carries its index and
+ * stands before the fill.  n_candidates[i] = |C'(i)| as recnow_ibs_rank writes it.  Rows that do not take part get all fill and 0 and
+ * may hold anything; so may masked extras.  A score is the result of the one fp32 expression recnow_ibs_rank compares and
+ * recnow_ibs_fwd exponentiates.  One launch of the loss's kernel template; the lists live in dynamic LDS (8 K + 4 bytes a row, 64 rows a
+ * workgroup).  No workspace, no atomics, every output element written once: the same input gives the same bits on every run.
+ * B == 0: RECNOW_OK without a launch.  Errors as recnow_ibs_rank; RECNOW_EINVAL for K < 1, a NULL output or a leading dimension below
+ * K; RECNOW_EUNSUPPORTED for K > recnow_ibs_topk_max_k() (128).
+ * recnow_ibs_topk_launches(which, vec): the census of recnow_ibs_rank_launches, for these launches alone; which 3: launches that walked
+ * the item segment (vec 1) or left it out (vec 0).  Top-K launches are in no other census.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_ibs_topk_max_k(void);
+int64_t recnow_ibs_topk_launches(int which, int vec);
+int recnow_ibs_topk(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                    const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                    const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                    int batch_candidates, int K, float* scores, int64_t ld_scores, int64_t* indices, int64_t ld_indices,
+                    int64_t* n_candidates, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement hook (bench.py): per-launch HIP-event timing of the GEMM kernels on the launch stream.
  * recnow_prof_enable(capacity > 0) arms `capacity` launch slots, (0) disables.  recnow_prof_collect synchronises and
  * returns per-kernel-family totals in HOST arrays of 16 entries indexed by tag: 1 = k_gemm<128,128>, 2 = k_gemm<128,160>,

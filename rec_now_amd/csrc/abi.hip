@@ -28,4 +28,5 @@
 // 30: recnow_fm_route, recnow_inner_pnn_route, recnow_attention_dot_route (the kernel choice of FM, InnerPNN and attention_by_dot_product, queryable);
 // 31: recnow_ibs_extra_fwd / _extra_bwd / _extra_launches (extra negatives for the in-batch sampled softmax: sampled items, a bank, other ranks);
 // 32: recnow_ibs_rank / _rank_launches (in-batch retrieval ranks: recall@K, NDCG@K, MRR and mean rank from per-row counts).
-extern "C" int recnow_abi_version(void) { return 32; }
+// 33: recnow_ibs_topk / _topk_max_k / _topk_launches (in-batch top-K candidates: hard-negative mining and top-K retrieval of a corpus).
+extern "C" int recnow_abi_version(void) { return 33; }

@@ -2,7 +2,7 @@
 // correction, the removal of accidental hits and a temperature.  Two-sided flash attention with one "value" per row, in exact fp32, and never
 // a (B, B) tensor.  DESIGN.md section 8z.
 //
-// One kernel template, four uses.  A workgroup of two waves OWNS 64 rows of one side (a wave 32 of them, as B-operand fragments in
+// One kernel template, five uses.  A workgroup of two waves OWNS 64 rows of one side (a wave 32 of them, as B-operand fragments in
 // registers for the whole launch) and STREAMS the other side through LDS in tiles of 32 rows.  The logit tile is formed TRANSPOSED on
 // v_mfma_f32_32x32x2_f32 -- streamed rows are the MFMA rows, owner rows the MFMA columns -- so that lane (n, h) = (lane & 31, lane >> 5)
 // holds, for owner row n, the 16 streamed rows  m_e = 8 (e / 4) + 4 h + e % 4:  a row reduction is 16 register steps and ONE exchange
@@ -14,6 +14,10 @@
 //                     those above it, those equal to it -- merged across the half-waves at the end (recnow_ibs_rank).
 //                     The positive's logit has to be known before anything is compared with it: two tiles AHEAD of the walk, the two of
 //                     the diagonal segment that hold the workgroup's own positives, go through the same loop body and only pick it up.
+//   MODE 4, top-K:    owner = queries, streamed = items, then extras.  The walk and the candidates of MODE 3; each owner row keeps the K
+//                     candidates that stand first in the total order (NaN, then the greater score, then the smaller index) as a binary
+//                     heap in dynamic LDS with the worst kept entry at its root (recnow_ibs_topk).  The positive
+//                     is excluded by index, so nothing is read ahead of the walk.
 // Extra negatives (recnow_ibs_extra_*): N item-side rows with no query row of their own.  The streamed side is a
 // list of segments; the forward and dq stream the items (a segment with a diagonal), then the extras (one without), each segment from a
 // fresh tile.  dv is the square launch unchanged.  de is MODE 2 with the extras as owners and the queries streamed without a diagonal.
@@ -50,7 +54,24 @@ struct IbArgs {
     float* row_max; float* row_logsum; float* row_pos; float* row_loss; double* part;                    // MODE 0
     const float* n_rows; const float* gout; float* dout; int64_t ldd;                                    // MODE 1, 2
     int64_t* n_greater; int64_t* n_equal; int64_t* n_cand; int walk_diag;                                // MODE 3 (row_pos too)
+    int K; float* top_s; int64_t ld_top_s; int64_t* top_i; int64_t ld_top_i;                             // MODE 4 (n_cand, walk_diag too)
 };
+
+#define IB_TOPK_MAX_K 128                       // 64 rows x 128 slots x 8 bytes = 64 KiB of dynamic LDS beside the tile
+#define IB_TOPK_LDS(K_) ((size_t)IB_ROWS * (8 * (size_t)(K_) + 4))                 // scores, indices, one length a row
+#define IB_STATIC_LDS(NC_) ((size_t)IB_TN * ((NC_) * 32 + 4) * 4 + 1536)            // the tile and (an upper bound of) the per-row vectors beside it
+
+// The total order of the top-K list as one unsigned compare: a stands before b iff ib_key(a) > ib_key(b).  The high word orders the scores
+// (-0.0 and 0.0 tie, a NaN of either sign is greatest), the low word breaks ties towards the smaller index.  Indices are distinct, so
+// keys are: the K first candidates are a function of the candidate set alone.
+__device__ __forceinline__ unsigned long long ib_key(float s, unsigned idx) {
+    unsigned u = __float_as_uint(s);
+    const bool nan = (u & 0x7fffffffu) > 0x7f800000u;
+    u = (u & 0x7fffffffu) == 0u ? 0u : u;
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    u = nan ? 0xffffffffu : u;
+    return ((unsigned long long)u << 32) | (unsigned long long)(~idx);
+}
 
 // XT 0: the square loss -- one streamed segment, the batch, with its diagonal (both known at compile time).  XT 1: the segment list is read
 // from the arguments: items then extras (MODE 0, 1), or the queries past owning extras (MODE 2, "de").
@@ -65,6 +86,7 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
     __shared__ __attribute__((aligned(16))) int64_t sId[IB_TN];
     __shared__ float sRedL[IB_ROWS];
     __shared__ int sRedN[IB_ROWS];
+    extern __shared__ __attribute__((aligned(16))) unsigned char ib_dyn[];      // MODE 4: the lists (no other mode is launched with any)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, h = lane >> 5;
     const int D = a.D;
     const int64_t og = (int64_t)blockIdx.x * IB_ROWS + wave * 32 + n;
@@ -91,7 +113,17 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
 
     const float NEG_INF = -__builtin_inff();
     float run_m = NEG_INF, run_s = 0.f, pos = 0.f;             // MODE 0; pos: MODE 3 too
-    int n_gt = 0, n_eq = 0, n_cd = 0;                          // MODE 3: a lane sees half of at most 2^31 streamed rows
+    int n_gt = 0, n_eq = 0, n_cd = 0;                          // MODE 3 (n_cd: MODE 4 too): a lane sees half of at most 2^31 streamed rows
+    // MODE 4: owner row r keeps slot s of its list at [s * IB_ROWS + r] -- a lane walks its own row's column, whatever the slot, on its own
+    // bank.  A min-heap under ib_key: slot 0 is the worst kept entry, the threshold.  Both half-waves of a row hold its length and its
+    // threshold's score; they are read again from LDS after every pass that may have changed them
+    const int K = MODE == 4 ? a.K : 0;
+    float* const lS = reinterpret_cast<float*>(ib_dyn) + (wave * 32 + n);
+    unsigned* const lP = reinterpret_cast<unsigned*>(ib_dyn) + (size_t)K * IB_ROWS + (wave * 32 + n);
+    int* const lC = reinterpret_cast<int*>(ib_dyn) + (size_t)2 * K * IB_ROWS + (wave * 32 + n);
+    int t_cnt = 0;
+    float t_s = 0.f;
+    if (MODE == 4 && h == 0) lC[0] = 0;
     ib_f16v acc[NC];                                           // MODE 1, 2: out^T, 32 columns d per block
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -105,7 +137,7 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
     const int64_t span = span0 + ((XT && MODE != 2 && a.nseg > 1) ? a.seg[1].count : 0);
     // MODE 3: the walk is preceded by two tiles (sw < 0), the workgroup's own 64 rows of the diagonal segment, and may leave that segment
     // out (a corpus of extras alone: the batch item is a row's positive and nobody's candidate)
-    const int64_t first = MODE == 3 ? -2 * IB_TN : 0, skip = (MODE == 3 && a.walk_diag == 0) ? span0 : 0;
+    const int64_t first = MODE == 3 ? -2 * IB_TN : 0, skip = ((MODE == 3 || MODE == 4) && a.walk_diag == 0) ? span0 : 0;
     for (int64_t sw = first; sw < span - skip; sw += IB_TN) {
         const bool ahead = MODE == 3 && sw < 0;
         const int64_t at = ahead ? (int64_t)blockIdx.x * IB_ROWS + (sw - first) : sw + skip;     // the tile's place among the streamed rows
@@ -200,6 +232,69 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
                     n_eq += (cand && sv[e] == pos) ? 1 : 0;
                 }
             }
+        } else if (MODE == 4) {
+            // the common tile: 16 compares against the threshold's score.  "not <": an equal score goes on to the index, a NaN to the key
+            const unsigned base = (unsigned)((si ? a.seg[0].count : 0) + s0) + 4u * h;       // of cat(items, extras); below 2^31
+            unsigned hit = 0;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const bool cand = valid[e] && !diag[e];
+                n_cd += cand ? 1 : 0;
+                hit |= (cand && (t_cnt < K || !(sv[e] < t_s))) ? (1u << e) : 0u;
+            }
+            if (__builtin_amdgcn_ballot_w64(hit != 0) != 0) {
+                // the two half-waves of a row share its list: h = 0 inserts, then h = 1, each from the state the other left in LDS
+                for (int hh = 0; hh < 2; ++hh) {
+                    if (h == hh) {
+                        while (hit) {
+                            const int e = __builtin_ctz(hit);
+                            hit &= hit - 1;
+                            float cs = sv[0];
+#pragma unroll
+                            for (int u = 1; u < 16; ++u) cs = e == u ? sv[u] : cs;
+                            const unsigned cp = base + 8u * (e >> 2) + (e & 3);
+                            const unsigned long long ck = ib_key(cs, cp);
+                            if (t_cnt < K) {
+                                // not yet full: every candidate is taken, a -inf one included; sift it up from the end
+                                int s = t_cnt++;
+                                while (s > 0) {
+                                    const int par = (s - 1) >> 1;
+                                    const float pf = lS[par * IB_ROWS];
+                                    const unsigned pp = lP[par * IB_ROWS];
+                                    if (ib_key(pf, pp) <= ck) break;
+                                    lS[s * IB_ROWS] = pf; lP[s * IB_ROWS] = pp;
+                                    s = par;
+                                }
+                                lS[s * IB_ROWS] = cs; lP[s * IB_ROWS] = cp;
+                            } else if (ck > ib_key(lS[0], lP[0])) {
+                                // it stands before the worst kept entry: that one leaves, the candidate sifts down from the root
+                                int s = 0;
+                                for (;;) {
+                                    int c = 2 * s + 1;
+                                    if (c >= K) break;
+                                    float cf = lS[c * IB_ROWS];
+                                    unsigned cq = lP[c * IB_ROWS];
+                                    unsigned long long kk = ib_key(cf, cq);
+                                    if (c + 1 < K) {
+                                        const float rf = lS[(c + 1) * IB_ROWS];
+                                        const unsigned rq = lP[(c + 1) * IB_ROWS];
+                                        const unsigned long long rk = ib_key(rf, rq);
+                                        if (rk < kk) { cf = rf; cq = rq; kk = rk; ++c; }
+                                    }
+                                    if (kk >= ck) break;
+                                    lS[s * IB_ROWS] = cf; lP[s * IB_ROWS] = cq;
+                                    s = c;
+                                }
+                                lS[s * IB_ROWS] = cs; lP[s * IB_ROWS] = cp;
+                            }
+                        }
+                        lC[0] = t_cnt;
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    t_cnt = lC[0];
+                    t_s = lS[0];                                 // slot 0 of an empty list is never compared: t_cnt < K comes first
+                }
+            }
         } else {
             float w[16];
 #pragma unroll
@@ -262,6 +357,26 @@ __global__ void __launch_bounds__(IB_THREADS) k_ibs(IbArgs a) {
             a.n_cand[og] = n_cd;
             a.row_pos[og] = o_on ? pos : __builtin_nanf("");
         }
+    } else if (MODE == 4) {
+        n_cd += __shfl_xor(n_cd, 32, 64);
+        __builtin_amdgcn_wave_barrier();
+        // order by counting: an entry's place is the number of entries that stand before it; keys are distinct, so places are.  The two
+        // half-waves of a row take every other slot; each output element is written once, the fill included
+        if (o_in) {
+            float* const os = a.top_s + og * a.ld_top_s;
+            int64_t* const oi = a.top_i + og * a.ld_top_i;
+            for (int j = h; j < t_cnt; j += 2) {
+                const float fj = lS[j * IB_ROWS];
+                const unsigned pj = lP[j * IB_ROWS];
+                const unsigned long long kj = ib_key(fj, pj);
+                int place = 0;
+                for (int i = 0; i < t_cnt; ++i) place += ib_key(lS[i * IB_ROWS], lP[i * IB_ROWS]) > kj ? 1 : 0;
+                os[place] = fj;
+                oi[place] = (int64_t)pj;
+            }
+            for (int j = t_cnt + h; j < K; j += 2) { os[j] = NEG_INF; oi[j] = -1; }
+            if (h == 0) a.n_cand[og] = n_cd;
+        }
     } else {
         const float nr = a.n_rows[0];
         const float scale = nr > 0.f ? a.gout[0] * inv_tau / nr : 0.f;
@@ -297,6 +412,7 @@ __global__ void __launch_bounds__(256) k_ibs_mean(const double* __restrict__ par
 static int64_t g_ibs_launches[8][2];
 static int64_t g_ibsx_launches[4][2];
 static int64_t g_ibsr_launches[4][2];
+static int64_t g_ibst_launches[4][2];
 
 static IbSide ibs_side(const float* rows, int64_t ld, int64_t count, const int64_t* ids, const float* log_q, const uint8_t* mask,
                        const float* st_max, const float* st_logsum, int has_diag) {
@@ -308,19 +424,29 @@ template <int MODE, int XT>
 static int ibs_launch(const IbArgs& a, hipStream_t st) {
     const int nc = (a.D + IB_DG - 1) / IB_DG;
     const int grid = rn_cdiv(a.own.count, IB_ROWS);
+    // MODE 4: the lists (K scores and K indices a row) and their lengths, in dynamic LDS.  With the tile that passes 64 KiB from K = 92
+    // (D > 96) to K = 116 (D <= 32) on; the limit is raised once per kernel and device, to what K = IB_TOPK_MAX_K needs
+    const size_t dyn = MODE == 4 ? IB_TOPK_LDS(a.K) : 0;
+    const bool grant = dyn + IB_STATIC_LDS(nc) > 64 * 1024;
     switch (nc) {
-        case 1: hipLaunchKernelGGL((k_ibs<1, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_ibs<2, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((k_ibs<3, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
-        default: hipLaunchKernelGGL((k_ibs<4, MODE, XT>), grid, IB_THREADS, 0, st, a); break;
+#define IB_CASE(NC_)                                                                                                              \
+        if (grant) RN_HIP(rn_lds_grant((const void*)k_ibs<NC_, MODE, XT>, IB_TOPK_LDS(IB_TOPK_MAX_K) + IB_STATIC_LDS(NC_)));      \
+        hipLaunchKernelGGL((k_ibs<NC_, MODE, XT>), grid, IB_THREADS, dyn, st, a);                                                 \
+        break;
+        case 1: IB_CASE(1)
+        case 2: IB_CASE(2)
+        case 3: IB_CASE(3)
+        default: IB_CASE(4)
+#undef IB_CASE
     }
     RN_LAUNCH_CHECK();
     const auto vec = [&](const IbSide& s) { return ((a.D & 3) == 0 && (s.ld & 3) == 0 && ((uintptr_t)s.rows & 15) == 0) ? 1 : 0; };
-    if (MODE == 3) {                                     // a census of its own: the loss's counts are read as deltas
-        ++g_ibsr_launches[0][vec(a.own)];
-        ++g_ibsr_launches[1][vec(a.seg[0])];
-        if (a.nseg > 1) ++g_ibsr_launches[2][vec(a.seg[1])];
-        ++g_ibsr_launches[3][a.walk_diag ? 1 : 0];
+    if (MODE == 3 || MODE == 4) {                        // a census of its own each: the loss's counts are read as deltas
+        int64_t (*c)[2] = MODE == 3 ? g_ibsr_launches : g_ibst_launches;
+        ++c[0][vec(a.own)];
+        ++c[1][vec(a.seg[0])];
+        if (a.nseg > 1) ++c[2][vec(a.seg[1])];
+        ++c[3][a.walk_diag ? 1 : 0];
     } else if (!XT) {
         ++g_ibs_launches[MODE][vec(a.own)];
         ++g_ibs_launches[MODE + 4][vec(a.seg[0])];
@@ -364,6 +490,13 @@ extern "C" int64_t recnow_ibs_rank_launches(int which, int vec) {
     if (which < 0 || which > 3 || vec < 0 || vec > 1) return RECNOW_EINVAL;
     return g_ibsr_launches[which][vec];
 }
+
+extern "C" int64_t recnow_ibs_topk_launches(int which, int vec) {
+    if (which < 0 || which > 3 || vec < 0 || vec > 1) return RECNOW_EINVAL;
+    return g_ibst_launches[which][vec];
+}
+
+extern "C" int recnow_ibs_topk_max_k(void) { return IB_TOPK_MAX_K; }
 
 static int ibs_check(const float* q, int64_t ldq, const float* v, int64_t ldv, int64_t B, int D) {
     if (B < 0 || D < 1) return RECNOW_EINVAL;
@@ -512,4 +645,28 @@ extern "C" int recnow_ibs_rank(const float* q, int64_t ldq, const float* v, int6
     a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits;
     a.row_pos = row_pos; a.n_greater = n_greater; a.n_equal = n_equal; a.n_cand = n_candidates; a.walk_diag = batch_candidates ? 1 : 0;
     return ibs_launch<3, 1>(a, (hipStream_t)stream);
+}
+
+// The K first candidates of every row: MODE 4 over the items (walked as candidates, or not at all) and the extras.
+extern "C" int recnow_ibs_topk(const float* q, int64_t ldq, const float* v, int64_t ldv, const int64_t* ids, const float* log_q,
+                               const uint8_t* mask, int64_t B, int D, const float* extra, int64_t ld_extra, const int64_t* extra_ids,
+                               const float* extra_log_q, const uint8_t* extra_mask, int64_t N, float inv_tau, int remove_hits,
+                               int batch_candidates, int K, float* scores, int64_t ld_scores, int64_t* indices, int64_t ld_indices,
+                               int64_t* n_candidates, void* stream) {
+    int rc = ibs_check(q, ldq, v, ldv, B, D);
+    if (rc == RECNOW_OK) rc = ibs_check_extra(extra, ld_extra, ids, extra_ids, N, D);
+    if (rc != RECNOW_OK) return rc;
+    if (K < 1) return RECNOW_EINVAL;
+    if (K > IB_TOPK_MAX_K) return RECNOW_EUNSUPPORTED;
+    if (B == 0) return RECNOW_OK;
+    if (!scores || !indices || !n_candidates || ld_scores < K || ld_indices < K || !(inv_tau > 0.f)) return RECNOW_EINVAL;
+    IbArgs a = {};
+    a.own = ibs_side(q, ldq, B, ids, log_q, mask, nullptr, nullptr, 0);
+    a.seg[0] = ibs_side(v, ldv, B, ids, log_q, mask, nullptr, nullptr, 1);
+    a.nseg = 1;
+    if (N > 0) { a.seg[1] = ibs_side(extra, ld_extra, N, extra_ids, extra_log_q, extra_mask, nullptr, nullptr, 0); a.nseg = 2; }
+    a.D = D; a.inv_tau = inv_tau; a.remove_hits = remove_hits;
+    a.n_cand = n_candidates; a.walk_diag = batch_candidates ? 1 : 0;
+    a.K = K; a.top_s = scores; a.ld_top_s = ld_scores; a.top_i = indices; a.ld_top_i = ld_indices;
+    return ibs_launch<4, 1>(a, (hipStream_t)stream);
 }

@@ -1,6 +1,6 @@
 """Per-row measurements of the other hot-path kernels at BASELINE config sizes (1x MI355X), fwd+bwd, inputs resident.
 Reports the figure each kernel's roofline is priced in: HBM GB/s for FM / DCN-v1 / MoE mix,
-rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax,in_batch_softmax_extra,in_batch_ranks]"""
+rows/s and pairs/s for the ranking losses, TFLOP/s for CIN / MMoE / PLE.   usage: python tools/layer_bench.py [reps] [fm,dcn,pair,pair_table,pair_kind,pair_lambda,pair_auc,pair_auc_sort,list,listmle,approx_ndcg,cin,ple,star,stacked,gnn,ipnn,senet,attn,din,focal,embed,hash,cross,slot,tensor_util,can,bilinear,autoint,afm,in_batch_softmax,in_batch_softmax_extra,in_batch_ranks,in_batch_top_k]"""
 import os
 import sys
 
@@ -1298,6 +1298,81 @@ def in_batch_ranks():
               % (B, N, D, tag, a, b, la, lb, 100 * spread, against, verdict, ra, rb, min(ra, rb) / max(a, b)))
 
 
+def ibs_topk_ref_eager(q, v, x, ids, lq, xids, xlq, tau, in_batch, k):
+    """The K highest candidates from torch operators: cat, the (B, B + N) logits, masked_fill of the positive and the hits (and of the batch
+    columns where the corpus alone holds the candidates), topk."""
+    B = q.shape[0]
+    s = q @ (v if x is None else torch.cat([v, x])).T / tau
+    if lq is not None:
+        s = s - (lq if x is None else torch.cat([lq, xlq]))[None, :]
+    if ids is not None:
+        drop = (ids if x is None else torch.cat([ids, xids]))[None, :] == ids[:, None]
+    else:
+        drop = torch.zeros(s.shape, dtype=torch.bool, device=s.device)
+    if in_batch:
+        drop[:, :B].fill_diagonal_(True)
+    else:
+        drop[:, :B] = True
+    return torch.topk(s.masked_fill(drop, float('-inf')), k, dim=1)
+
+
+def in_batch_top_k():
+    """in_batch_top_k at the shapes of in_batch_ranks: plain, with ids + log_q, and the corpus alone, each at K = 10 and K = 100.  The
+    harness of in_batch_ranks: graph-replay GPU time, the cases in turn, twice, the spread between the passes.  Two yardsticks in the same
+    run: in_batch_ranks at the same shape (the same walk: the ratio is the cost of selection) and the torch composition cat + (B, B + N)
+    logits + masked_fill + topk -- reported as such where it does not fit.  Flop model: 2 B C D with C the streamed candidates."""
+    from rec_now_amd.rec_block.retrieval_metrics import in_batch_ranks as ranks
+    from rec_now_amd.rec_block.retrieval_topk import in_batch_top_k as top_k
+    tau = 0.5
+    cases = [(16384, 49152, 64), (65536, 65536, 64), (65536, 65536, 128), (65536, 0, 64)]
+    seen = {}
+    for rnd in (1, 2):
+        for B, N, D in cases:
+            for tag, with_ids, in_batch in (('plain', False, True), ('ids+log_q', True, True), ('corpus alone', False, False)):
+                if N == 0 and not in_batch:
+                    continue
+                gen = torch.Generator(device=dev).manual_seed(B + D + N)
+                q = torch.randn(B, D, device=dev, generator=gen) * D ** -0.25
+                v = torch.randn(B, D, device=dev, generator=gen) * D ** -0.25
+                x = torch.randn(N, D, device=dev, generator=gen) * D ** -0.25 if N else None
+                ids = torch.randint(0, B // 4, (B,), device=dev, generator=gen) if with_ids else None
+                xids = torch.randint(0, B // 4, (N,), device=dev, generator=gen) if with_ids and N else None
+                lq = torch.rand(B, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids else None
+                xlq = torch.rand(N, device=dev, generator=gen).mul_(0.95).add_(0.05).log_() if with_ids and N else None
+                kw = dict(extra_item=x, extra_item_ids=xids, extra_log_q=xlq)
+                flops = 2.0 * B * ((B if in_batch else 0) + N) * D
+                g_rank = ibs_graph_ms(lambda: ranks(q, v, ids, lq, tau, in_batch_candidates=in_batch, **kw).n_greater)
+                for k in (10, 100):
+                    run = lambda: top_k(q, v, ids, lq, tau, k=k, in_batch_candidates=in_batch, **kw)      # noqa: E731
+                    ref = lambda: ibs_topk_ref_eager(q, v, x, ids, lq, xids, xlq, tau, in_batch, k)      # noqa: E731
+                    g_top = ibs_graph_ms(run)
+                    try:
+                        got, (rs, ri) = run(), ref()
+                        diff = (got.indices != ri).any(1).sum().item()
+                        err = (got.scores - rs).abs().max().item()
+                        del got, rs, ri
+                        g_ref = ibs_graph_ms(ref)
+                        fits = 'torch composition (forms (B, B + N)) %.3f ms -> fused is %.2fx%s | rows whose index list differs from torch %d of %d, max |score - torch| %.2g' % (
+                            g_ref, g_ref / g_top, '' if g_ref >= g_top else ' **SLOWER than torch**', diff, B, err)
+                    except torch.cuda.OutOfMemoryError:
+                        g_ref = float('nan')
+                        fits = 'torch composition: DID NOT FIT (out of memory on its (B, B + N) tensors)'
+                    torch.cuda.synchronize()
+                    torch.cuda.empty_cache()
+                    print('pass %d in_batch_top_k B=%d N=%d D=%d K=%d %s : top-K (graph) %.3f ms %.1f TFLOP/s (%.2f of 157.3) | in_batch_ranks, same shape %.3f ms -> top-K / ranks %.3f | %s'
+                          % (rnd, B, N, D, k, tag, g_top, flops / g_top / 1e9, flops / g_top / 1e9 / 157.3, g_rank, g_top / g_rank, fits), flush=True)
+                    seen.setdefault((B, N, D, k, tag), []).append((g_top, g_rank, g_ref))
+                del q, v, x, ids, lq, xids, xlq, kw
+                torch.cuda.empty_cache()
+    for (B, N, D, k, tag), ((a, la, ra), (b, lb, rb)) in seen.items():
+        spread = max(abs(a - b) / min(a, b), abs(la - lb) / min(la, lb))
+        worst = min(ra, rb) / max(a, b)
+        print('in_batch_top_k B=%d N=%d D=%d K=%d %s : top-K (graph) %.3f / %.3f ms, ranks %.3f / %.3f ms, largest spread between the passes %.1f %%; '
+              'top-K / ranks %.3f / %.3f; torch %.3f / %.3f ms, fused against torch in the worse pairing %.2fx%s'
+              % (B, N, D, k, tag, a, b, la, lb, 100 * spread, a / la, b / lb, ra, rb, worst,
+                 '' if worst != worst or worst - 1 > spread else ' -> **NOT faster than torch beyond the spread**'))
+
+
 def gnn_ref_eager(x, indices, ws, L, F):
     """The reference algorithm (sparse_gnn_layer.py:183-236) in torch eager: transpose to (B, D, F), per layer a dense (F, F) matrix scattered
     from the weight vector, matmul, add, tanh; transpose back and flatten."""
@@ -1675,6 +1750,6 @@ if __name__ == '__main__':
             star(mode)
     if 'gnn' in which:
         gnn()
-    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax), ('in_batch_softmax_extra', in_batch_softmax_extra), ('in_batch_ranks', in_batch_ranks)):
+    for name, fn in (('ipnn', ipnn), ('senet', senet), ('attn', attn), ('din', din), ('focal', focal), ('embed', embed), ('hash', hash), ('cross', cross), ('slot', slot), ('tensor_util', tensor_util), ('can', can), ('bilinear', bilinear), ('autoint', autoint), ('afm', afm), ('in_batch_softmax', in_batch_softmax), ('in_batch_softmax_extra', in_batch_softmax_extra), ('in_batch_ranks', in_batch_ranks), ('in_batch_top_k', in_batch_top_k)):
         if name in which:
             fn()
