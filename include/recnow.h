@@ -1427,6 +1427,39 @@ int recnow_stream_wait_event(void* stream, void* event);
 int recnow_scale_by_inv_count(float* x, int64_t n, const float* count, float eps, const float* loss_sum, float* stats_out,
                               void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * attention_by_softmax (C ABI 34): masked multi-head softmax target attention of a padded history against H queries per sample.
+ * An addition; the reference has no softmax attention.  user: (B, L, D) fp32, keys and values; query: (B, H, D) fp32; lengths: (B) int32
+ * or NULL (values below 0 act as 0, above L as L); mask: (B, L) uint8 or NULL (non-zero: a key).  Position l is a key of sample b iff
+ * l < lengths[b] and mask[b][l] != 0 (a NULL argument does not restrict).  scale finite and > 0.  Over the keys K(b):
+ *   s_hl = scale <query[b,h], user[b,l]>;   a_hl = exp(s_hl - m_h) / S_h,  m_h = max_l s_hl,  S_h = sum_l exp(s_hl - m_h)
+ *   out[b,h] = sum_l a_hl user[b,l]   (B, H, D);     stat[b,h] = (m_h, log2 S_h)   (B, H, 2):  lse = m_h + ln 2 * log2 S_h
+ * (the logarithm to base 2, the hardware's own: a sum that is a power of two comes back exactly).  A sample without a key gets out = 0
+ * and stat = (-inf, -inf).  Positions outside K(b) are kept out by selects: they may hold NaN or inf, and positions at or beyond the
+ * length are not read.  recnow_attention_softmax_bwd recomputes the scores from user, query and stat and writes, with dc = dout (B, H, D),
+ *   ds_hl = a_hl (<dc_h, x_l> - <dc_h, out_h>);   duser[b,l] = sum_h (a_hl dc_h + scale ds_hl q_h)  (0 outside K(b));
+ *   dquery[b,h] = scale sum_l ds_hl x_l.
+ * duser or dquery NULL: that output is not computed (both NULL: no launch).  No workspace, no atomics, no LDS; every row is written once,
+ * the same input gives the same bits on every run.  B == 0: RECNOW_OK without a launch.  D > 256 or H > 8: RECNOW_EUNSUPPORTED;
+ * recnow_attention_softmax_supported: host-only, 1 for L >= 0, 1 <= D <= 256, 1 <= H <= 8, else 0.
+ * recnow_attention_softmax_route: host-only, which kernel _fwd (which = 0) / _bwd (which = 1) launch.  align_mask: one bit per tensor that
+ * starts OFF a 16-byte boundary: 1 user, 2 query, 4 out, and for the backward 8 dout, 16 duser, 32 dquery.  Returns 200000 + 100 CPL + HB
+ * for the vector kernels k_as_v4_fwd / _bwd<CPL, HB> (D = 4 CPL, CPL in {1, 2, 4, 8, 16}, every tensor aligned), 100000 + 100 GS + HB for the
+ * guarded kernels k_as_fwd / _bwd<GS, HB> (GS = 16 / 32 / 64 lanes per sample for D <= 16 / <= 32 / <= 256); HB in {1, 2, 4, 8} is H rounded
+ * up to a power of two.  0 for B = 0; RECNOW_EUNSUPPORTED as above; RECNOW_EINVAL: which outside {0, 1}, B < 0, L < 0, D < 1, H < 1, or an
+ * align_mask outside the direction's bits.
+ * recnow_attention_softmax_tile(which): 0 the samples per wave of the vector route, 1 the float4 pieces of a sample per loop trip, 2 the
+ * lanes per sample; anything else RECNOW_EINVAL.
+ * ---------------------------------------------------------------------------------------------------------- */
+int recnow_attention_softmax_supported(int L, int D, int H);
+int recnow_attention_softmax_route(int which, int64_t B, int L, int D, int H, int align_mask);
+int recnow_attention_softmax_tile(int which);
+int recnow_attention_softmax_fwd(const float* user, const float* query, const int32_t* lengths, const uint8_t* mask, int64_t B, int L, int D,
+                                 int H, float scale, float* out, float* stat, void* stream);
+int recnow_attention_softmax_bwd(const float* user, const float* query, const int32_t* lengths, const uint8_t* mask, const float* out,
+                                 const float* stat, const float* dout, int64_t B, int L, int D, int H, float scale, float* duser,
+                                 float* dquery, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

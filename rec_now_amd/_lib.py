@@ -199,6 +199,11 @@ SIGNATURES = {
     'recnow_ibs_topk_launches': (_L, [_I, _I]),
     'recnow_ibs_topk_max_k': (_I, []),
     'recnow_ibs_topk': (_I, [_P, _L, _P, _L, _P, _P, _P, _L, _I, _P, _L, _P, _P, _P, _L, _F, _I, _I, _I, _P, _L, _P, _L, _P, _P]),
+    'recnow_attention_softmax_supported': (_I, [_I, _I, _I]),
+    'recnow_attention_softmax_route': (_I, [_I, _L, _I, _I, _I, _I]),
+    'recnow_attention_softmax_tile': (_I, [_I]),
+    'recnow_attention_softmax_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
+    'recnow_attention_softmax_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
     'recnow_prof_enable': (_I, [_I]),
     'recnow_prof_sample_every': (_I, [_I]),
     'recnow_prof_collect': (_I, [_P, _P, _P, _P]),
@@ -239,7 +244,7 @@ class GemmRouteInfo(ctypes.Structure):
         'splitk', 'kchunk', 'grid_x', 'grid_y', 'grid_z', 'xcd_remap', 'tail_pairs', 'reduce_variant', 'reduce_blocks', 'tag')]
 
 
-ABI_VERSION = 33 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 34 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

@@ -29,4 +29,5 @@
 // 31: recnow_ibs_extra_fwd / _extra_bwd / _extra_launches (extra negatives for the in-batch sampled softmax: sampled items, a bank, other ranks);
 // 32: recnow_ibs_rank / _rank_launches (in-batch retrieval ranks: recall@K, NDCG@K, MRR and mean rank from per-row counts).
 // 33: recnow_ibs_topk / _topk_max_k / _topk_launches (in-batch top-K candidates: hard-negative mining and top-K retrieval of a corpus).
-extern "C" int recnow_abi_version(void) { return 33; }
+// 34: recnow_attention_softmax_fwd / _bwd / _supported / _route / _tile (attention_by_softmax: masked multi-head softmax target attention).
+extern "C" int recnow_abi_version(void) { return 34; }

@@ -7,3 +7,4 @@ from .fix_length_layer import FixLengthLayer  # noqa: F401
 from .interacting_layer import InteractingLayer  # noqa: F401
 from .multi_hash_layer import FastMultiHashLayer, MultiHashLayer  # noqa: F401
 from .pooling_layer import PoolingLayer  # noqa: F401
+from .target_attention_layer import TargetAttentionLayer  # noqa: F401

@@ -1,8 +1,11 @@
 """attention_by_dot_product and attention_by_dnn -- drop-ins for rec_now/rec_block/attention.py:12-38 and :41-82
 (/root/reference/rec_now/rec_block/attention.py).  One fused HIP kernel per direction each: the dot product is HBM-bound (the
 (B,L,D) user embeddings are read once forward, once backward with the scores recomputed); the DIN unit runs its Dense stack per
-tile of positions on the exact-fp32 matrix cores without forming any (B,L,H) activation (csrc/attention_dnn.hip)."""
+tile of positions on the exact-fp32 matrix cores without forming any (B,L,H) activation (csrc/attention_dnn.hip).
+attention_by_softmax is an addition (the reference has no softmax attention): masked multi-head softmax target attention, one fused
+kernel per direction that never forms the (B, H, L) scores (csrc/attention_softmax.hip)."""
 import ctypes
+import math
 
 import torch
 
@@ -179,3 +182,132 @@ def attention_by_dnn(user_emb, doc_emb, dnn_dims, dnn_activation='relu', dnn_nam
     model = DinAttention(dnn_dims, dnn_activation=dnn_activation, name=dnn_name)
     attn_mat, attn_score_sum = model(user_emb, doc_emb)
     return attn_mat, attn_score_sum, model
+
+
+_SOFTMAX_MAX_D = 256                                     # AS_MAX_D / AS_MAX_H of csrc/attention_softmax.hip
+_SOFTMAX_MAX_H = 8
+_LN2 = math.log(2.0)
+
+
+def attention_softmax_supported(L, D, H):
+    """Whether the kernels take this shape (host-only query of the library, no device call)."""
+    return bool(_lib.load().recnow_attention_softmax_supported(int(L), int(D), int(H)))
+
+
+class _AttnSoftmaxFunction(torch.autograd.Function):
+    """(user_emb (B, L, D), query (B, H, D), lengths (B,) int32 | None, mask (B, L) uint8 | None, scale) -> out (B, H, D), stat (B, H, 2).
+    stat = (maximum, log2 of the sum rescaled by it) per (b, h): what the backward recomputes the weights from.  Saves its inputs, out and
+    stat; nothing of size B H L exists in either direction."""
+
+    @staticmethod
+    def forward(ctx, user_emb, query, lengths, mask, scale):
+        u = _lib.f32c(user_emb, 'user_emb')
+        q = _lib.f32c(query, 'query')
+        B, L, D = u.shape
+        H = q.shape[1]
+        if B == 0 or L == 0:                               # nothing to launch: no key anywhere
+            out = torch.zeros((B, H, D), dtype=torch.float32, device=u.device)
+            stat = torch.full((B, H, 2), float('-inf'), dtype=torch.float32, device=u.device)
+        else:
+            out = torch.empty((B, H, D), dtype=torch.float32, device=u.device)
+            stat = torch.empty((B, H, 2), dtype=torch.float32, device=u.device)
+            _lib.call('recnow_attention_softmax_fwd', _lib.ptr(u), _lib.ptr(q), _lib.ptr(lengths), _lib.ptr(mask), B, L, D, H, scale,
+                      _lib.ptr(out), _lib.ptr(stat), _lib.stream())
+        ctx.save_for_backward(u, q, out, stat)
+        ctx.keys = (lengths, mask)
+        ctx.scale = scale
+        ctx.mark_non_differentiable(stat)
+        ctx.set_materialize_grads(False)                   # no zeros tensor for the statistic's absent gradient
+        return out, stat
+
+    @staticmethod
+    def backward(ctx, dout, _dstat):
+        u, q, out, stat = ctx.saved_tensors
+        lengths, mask = ctx.keys
+        B, L, D = u.shape
+        H = q.shape[1]
+        need_u, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if dout is None:
+            return None, None, None, None, None
+        if B == 0 or L == 0:
+            return (torch.zeros_like(u) if need_u else None, torch.zeros_like(q) if need_q else None, None, None, None)
+        du = torch.empty_like(u) if need_u else None       # every row is written by the kernel
+        dq = torch.empty_like(q) if need_q else None
+        if need_u or need_q:
+            dout = _lib.f32c(dout, 'grad')
+            _lib.call('recnow_attention_softmax_bwd', _lib.ptr(u), _lib.ptr(q), _lib.ptr(lengths), _lib.ptr(mask), _lib.ptr(out), _lib.ptr(stat),
+                      _lib.ptr(dout), B, L, D, H, ctx.scale, _lib.ptr(du), _lib.ptr(dq), _lib.stream())
+        return du, dq, None, None, None
+
+
+def attention_by_softmax(user_emb, query, lengths=None, mask=None, scale=None, return_lse=False):
+    """Masked multi-head softmax target attention: the candidate item is the query, the L history positions are keys and values.
+
+    Args:
+        user_emb: (B, L, D) float32 GPU tensor, the keys and also the values;
+        query: (B, D) for one head or (B, H, D) for H heads;
+        lengths: (B,) or (B, 1) integers, position l of sample b is a key iff l < lengths[b] (above L acts as L, negative as 0);
+        mask: (B, L) of any integer, bool or float dtype, non-zero = key; with lengths too, the two are ANDed; neither: every position is a key;
+        scale: a finite float > 0, None = 1 / sqrt(D);
+        return_lse: also return lse = log sum_{keys} exp(score), (B, H) or (B,), not differentiable.
+    Returns:
+        out[b, h] = sum_l softmax_l(scale <query[b, h], user_emb[b, l]>) user_emb[b, l] over the keys: (B, H, D), or (B, D) for a 2-D query.
+        A sample without a key gets out = 0 and lse = -inf and contributes nothing to any gradient; positions that are not keys may hold
+        NaN or inf, their d user_emb rows are 0.
+    Limits of the fused kernels (NotImplementedError): D <= 256, H <= 8.  One HIP kernel per direction (csrc/attention_softmax.hip), no
+    host synchronisation, no atomics; the backward recomputes the scores from the inputs and a per-(b, h) (maximum, log-sum) pair.
+    """
+    for t, what in ((user_emb, 'user_emb'), (query, 'query')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %s' % (what, type(t)))
+    if user_emb.dim() != 3 or query.dim() not in (2, 3):
+        raise ValueError('user_emb must be (B, L, D) and query (B, D) or (B, H, D); got %s and %s' % (tuple(user_emb.shape), tuple(query.shape)))
+    B, L, D = user_emb.shape
+    two_d = query.dim() == 2
+    H = 1 if two_d else query.shape[1]
+    if query.shape[0] != B or query.shape[-1] != D or H < 1 or D < 1:
+        raise ValueError('user_emb must be (B, L, D) and query (B, D) or (B, H, D) with the same B and D >= 1, H >= 1; got %s and %s'
+                         % (tuple(user_emb.shape), tuple(query.shape)))
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor):
+            raise TypeError('lengths must be a torch.Tensor, got %s' % type(lengths))
+        if lengths.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError('lengths must be integers (int32 or int64), got %s' % lengths.dtype)
+        if lengths.numel() != B or lengths.dim() not in (1, 2):
+            raise ValueError('lengths must be (B,) or (B, 1) with B = %d; got %s' % (B, tuple(lengths.shape)))
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor):
+            raise TypeError('mask must be a torch.Tensor, got %s' % type(mask))
+        if mask.dim() != 2 or mask.shape[0] != B or mask.shape[1] != L or mask.dtype.is_complex:
+            raise ValueError('mask must be (B, L) = (%d, %d); got %s' % (B, L, tuple(mask.shape)))
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError('scale must be a finite float > 0, got %r' % (scale,))
+    if D > _SOFTMAX_MAX_D:
+        raise NotImplementedError('attention_by_softmax kernels cover embedding_dim <= %d; got %d' % (_SOFTMAX_MAX_D, D))
+    if H > _SOFTMAX_MAX_H:
+        raise NotImplementedError('attention_by_softmax kernels cover at most %d heads; got %d' % (_SOFTMAX_MAX_H, H))
+    _lib.require_gpu(user_emb, 'user_emb')                 # after the argument checks: those hold on any device
+    _lib.require_gpu(query, 'query')
+    if lengths is not None:
+        _lib.require_gpu(lengths, 'lengths')
+        lengths = lengths.reshape(-1)
+        if lengths.dtype != torch.int32:
+            lengths = lengths.clamp(0, L).to(torch.int32)  # before the narrowing: an int64 above 2^31 acts as L
+        lengths = lengths.contiguous()
+    if mask is not None:
+        _lib.require_gpu(mask, 'mask')
+        if mask.dtype not in (torch.uint8, torch.bool):
+            mask = mask != 0
+        mask = mask.contiguous()
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    out, stat = _AttnSoftmaxFunction.apply(user_emb, query.unsqueeze(1) if two_d else query, lengths, mask, scale)
+    if two_d:
+        out = out.reshape(B, D)
+    if not return_lse:
+        return out
+    lse = (stat[..., 0].double() + stat[..., 1].double() * _LN2).to(torch.float32)     # -inf for a sample without a key
+    return out, (lse.reshape(B) if two_d else lse)
