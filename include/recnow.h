@@ -824,6 +824,14 @@ int recnow_senet_scale_bwd_w(const float* const* fields, const int32_t* dims, co
                              const float* dout, float* dw, int uniform_d, void* stream);
 int recnow_senet_scale_bwd_x(float* const* dfields, const int32_t* dims, const int32_t* offs, int F, int total, int64_t B,
                              const float* w, const float* dout, const float* dsq, int uniform_d, void* stream);
+/* The kernel the four entries above run for (B, F, total, uniform_d); mode 0 squeeze, 1 scale_fwd, 2 scale_bwd_w, 3 scale_bwd_x (all four choose
+ * alike).  Host only: nothing is launched, no device memory is touched; the launchers run the very plan these report.
+ *   recnow_senet_route: 0 nothing to do (B = 0); 100000 + R the LDS tile kernel on R rows per workgroup (1 .. 32); 200000 + Q the float4 kernel
+ *   with Q = uniform_d / 4 lanes per field row; RECNOW_EUNSUPPORTED one concatenated row does not fit in LDS (total > 12287, not uniform);
+ *   RECNOW_EINVAL mode outside 0 .. 3, F < 1, B < 0, total < 1, uniform_d < 0.
+ *   recnow_senet_grid: the workgroups of that launch (the route's code where that is <= 0). */
+int recnow_senet_route(int mode, int64_t B, int F, int total, int uniform_d);
+int recnow_senet_grid(int mode, int64_t B, int F, int total, int uniform_d);
 
 /* SENETLayer in one pass per direction (senet_layer.py:93-119), for equal field widths D (D % 4 == 0, D/4 a power of two,
  * F*D/4 <= 256), F <= 64, hidden width M <= 64 and RECNOW_ACT_* activations: squeeze, the F -> M -> F excitation and the
@@ -840,6 +848,16 @@ int recnow_senet_fused_bwd(const float* const* fields, float* const* dfields, in
                            const float* W2, int M, int act1, int act2, const float* dout, const float* sq_save,
                            const float* h_save, const float* w_save, float* dW1, float* db1, float* dW2, float* db2, void* ws,
                            size_t ws_bytes, void* stream);
+/* The kernel recnow_senet_fused_fwd (which = 0) / _bwd (which = 1) runs; out_misaligned: `out` is not on a 16-byte boundary (forward only).  The
+ * launchers run the very plan these report.
+ *   recnow_senet_fused_route: 0 nothing to do (B = 0); forward 100000 (4 rows per step) or 200000 (8 rows per step: D = 16, F % 8 == 0, out
+ *   aligned) + 10 P + grant, P the threads that share one hidden unit (1, 2, 4, 8), grant 1 when the launch needs more than 64 KiB of LDS;
+ *   backward 300000 + NACC, the instantiation (3, 5, 9, 17, 34 weight-gradient outputs per thread); RECNOW_EUNSUPPORTED outside
+ *   recnow_senet_fused_supported; RECNOW_EINVAL which / out_misaligned outside {0, 1}, B < 0.  Launches nothing, touches no device memory.
+ *   recnow_senet_fused_grid: the workgroups of that launch (the route's code where that is <= 0); the backward's follows the occupancy the
+ *   runtime reports for the instantiation (at most 256 x occupancy workgroups), so it needs a device. */
+int recnow_senet_fused_route(int which, int64_t B, int F, int D, int M, int out_misaligned);
+int recnow_senet_fused_grid(int which, int64_t B, int F, int D, int M, int out_misaligned);
 
 /* attention_by_dot_product: rec_now/rec_block/attention.py:12-38.  user (B,L,D), doc (B,D), D <= 256:
  *   s_l = <user[b][l], doc[b]> (max(.,0) when filter_neg, :31-32);  mat[b] = sum_l user[b][l] * s_l;  score_sum[b] = sum_l s_l

@@ -114,10 +114,14 @@ SIGNATURES = {
     'recnow_senet_scale_fwd': (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _P]),
     'recnow_senet_scale_bwd_w': (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _P]),
     'recnow_senet_scale_bwd_x': (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _P, _I, _P]),
+    'recnow_senet_route': (_I, [_I, _L, _I, _I, _I]),
+    'recnow_senet_grid': (_I, [_I, _L, _I, _I, _I]),
     'recnow_senet_fused_supported': (_I, [_I, _I, _I]),
     'recnow_senet_fused_workspace_bytes': (_Z, [_L, _I, _I]),
     'recnow_senet_fused_fwd': (_I, [_P, _I, _I, _L, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'recnow_senet_fused_bwd': (_I, [_P, _P, _I, _I, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'recnow_senet_fused_route': (_I, [_I, _L, _I, _I, _I, _I]),
+    'recnow_senet_fused_grid': (_I, [_I, _L, _I, _I, _I, _I]),
     'recnow_attention_dot_fwd': (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _P]),
     'recnow_attention_dot_bwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
     'recnow_attention_dot_route': (_I, [_I, _L, _I, _I, _I]),
@@ -244,7 +248,7 @@ class GemmRouteInfo(ctypes.Structure):
         'splitk', 'kchunk', 'grid_x', 'grid_y', 'grid_z', 'xcd_remap', 'tail_pairs', 'reduce_variant', 'reduce_blocks', 'tag')]
 
 
-ABI_VERSION = 34 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
+ABI_VERSION = 35 # the recnow_abi_version() the SIGNATURES above were written for (csrc/abi.hip)
 
 class StepDesc(ctypes.Structure):
     """recnow_dcn_mix_step_desc of include/recnow.h."""

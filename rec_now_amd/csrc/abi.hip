@@ -30,4 +30,5 @@
 // 32: recnow_ibs_rank / _rank_launches (in-batch retrieval ranks: recall@K, NDCG@K, MRR and mean rank from per-row counts).
 // 33: recnow_ibs_topk / _topk_max_k / _topk_launches (in-batch top-K candidates: hard-negative mining and top-K retrieval of a corpus).
 // 34: recnow_attention_softmax_fwd / _bwd / _supported / _route / _tile (attention_by_softmax: masked multi-head softmax target attention).
-extern "C" int recnow_abi_version(void) { return 34; }
+// 35: recnow_senet_route / _grid, recnow_senet_fused_route / _fused_grid (the kernel choice and the grid of every SENET entry, queryable).
+extern "C" int recnow_abi_version(void) { return 35; }

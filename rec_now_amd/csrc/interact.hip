@@ -613,33 +613,69 @@ static inline int senet_uniform_ok(int D, int F, int total) {
     const int q = D / 4;
     return (q & (q - 1)) == 0 && q <= 64 ? D : 0;
 }
-static int senet_launch(int mode, const float* const* fields, float* const* dfields, const int32_t* dims, const int32_t* offs, int F,
-                        int total, int64_t B, const float* w, const float* in, const float* dsq, float* out, int uniform_d, hipStream_t st) {
+// The choices of senet_launch, stated once: the launcher launches what senet_plan returns and recnow_senet_route / _grid answer the same questions
+// without a launch (tests/_senet_routes.py mirrors them).  uniform_d is what senet_uniform_ok made of the caller's promise.
+enum { SENET_TILE = 1, SENET_UNIFORM = 2 };
+struct SenetPlan {
+    int family;          // SENET_TILE: k_senet_tile<MODE>, SENET_UNIFORM: k_senet_uniform<MODE>
+    int rq;              // tile: R rows per workgroup (1 .. 32); uniform: Q = D / 4 lanes per field row
+    int grid;
+    size_t lds;
+};
+static int senet_plan(int64_t B, int total, int uniform_d, SenetPlan* p) {
     if (uniform_d > 0) {
         const int64_t n = (B + SENET_RU - 1) / SENET_RU * (total / 4);       // (row group, float4 of the concatenated row) items
         int64_t g = (n + 255) / 256;
         if (g > 16384) g = 16384;
-        const int D = uniform_d;
-        switch (mode) {
-            case SENET_MODE_SQUEEZE: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_SQUEEZE>, (int)g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
-            case SENET_MODE_SCALE: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_SCALE>, (int)g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
-            case SENET_MODE_DW: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_DW>, (int)g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
-            default: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_DX>, (int)g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
-        }
-        RN_LAUNCH_CHECK();
+        *p = {SENET_UNIFORM, uniform_d / 4, (int)g, 0};
         return RECNOW_OK;
     }
     int R = (int)((48 * 1024) / ((size_t)(total + 1) * sizeof(float)));
     if (R < 1) return RECNOW_EUNSUPPORTED;            // one row of the concatenation must fit in LDS (total <= 12287)
     if (R > 32) R = 32;
-    const size_t lds = (size_t)R * (total + 1) * sizeof(float);
     int64_t g = (B + R - 1) / R;
     if (g > 4096) g = 4096;
+    *p = {SENET_TILE, R, (int)g, (size_t)R * (total + 1) * sizeof(float)};
+    return RECNOW_OK;
+}
+extern "C" int recnow_senet_route(int mode, int64_t B, int F, int total, int uniform_d) {
+    if (mode < SENET_MODE_SQUEEZE || mode > SENET_MODE_DX || F < 1 || B < 0 || total < 1 || uniform_d < 0) return RECNOW_EINVAL;
+    if (B == 0) return 0;
+    SenetPlan p;
+    const int rc = senet_plan(B, total, senet_uniform_ok(uniform_d, F, total), &p);
+    return rc ? rc : p.family * 100000 + p.rq;
+}
+extern "C" int recnow_senet_grid(int mode, int64_t B, int F, int total, int uniform_d) {
+    const int rc = recnow_senet_route(mode, B, F, total, uniform_d);
+    if (rc <= 0) return rc;
+    SenetPlan p;
+    senet_plan(B, total, senet_uniform_ok(uniform_d, F, total), &p);
+    return p.grid;
+}
+static int senet_launch(int mode, const float* const* fields, float* const* dfields, const int32_t* dims, const int32_t* offs, int F,
+                        int total, int64_t B, const float* w, const float* in, const float* dsq, float* out, int uniform_d, hipStream_t st) {
+    SenetPlan p;
+    const int rc = senet_plan(B, total, uniform_d, &p);
+    if (rc) return rc;
+    const int g = p.grid;
+    if (p.family == SENET_UNIFORM) {
+        const int D = uniform_d;
+        switch (mode) {
+            case SENET_MODE_SQUEEZE: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_SQUEEZE>, g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
+            case SENET_MODE_SCALE: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_SCALE>, g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
+            case SENET_MODE_DW: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_DW>, g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
+            default: hipLaunchKernelGGL(k_senet_uniform<SENET_MODE_DX>, g, 256, 0, st, fields, dfields, F, D, B, w, in, dsq, out); break;
+        }
+        RN_LAUNCH_CHECK();
+        return RECNOW_OK;
+    }
+    const int R = p.rq;
+    const size_t lds = p.lds;
     switch (mode) {
-        case SENET_MODE_SQUEEZE: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_SQUEEZE>, (int)g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
-        case SENET_MODE_SCALE: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_SCALE>, (int)g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
-        case SENET_MODE_DW: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_DW>, (int)g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
-        default: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_DX>, (int)g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
+        case SENET_MODE_SQUEEZE: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_SQUEEZE>, g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
+        case SENET_MODE_SCALE: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_SCALE>, g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
+        case SENET_MODE_DW: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_DW>, g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
+        default: hipLaunchKernelGGL(k_senet_tile<SENET_MODE_DX>, g, 256, lds, st, fields, dfields, dims, offs, F, total, B, R, w, in, dsq, out); break;
     }
     RN_LAUNCH_CHECK();
     return RECNOW_OK;

@@ -30,6 +30,13 @@ static inline int sf_grid(int64_t B) {
     int64_t g = (B + SF_R - 1) / SF_R;
     return (int)(g > 2048 ? 2048 : (g > 0 ? g : 1));
 }
+// threads that share one hidden unit's k range in the products over F (a power of two <= 8, while `rows` x M outputs of P threads fill at most half a
+// workgroup): the kernels split by it and sf_plan reports it
+__host__ __device__ static inline int sf_split(int rows, int M) {
+    int P = 1;
+    while (P < 8 && 2 * P * rows * M <= 256) P *= 2;
+    return P;
+}
 // LDS floats: W1 [F][M], W2 [M][F], b1 [M], b2 [F], then per-row vectors
 static inline size_t sf_lds_floats(int F, int M) { return (size_t)2 * F * M + M + F + (size_t)SF_R * (4 * F + 2 * M); }
 
@@ -62,8 +69,7 @@ k_senet_fused_fwd(const float* const* __restrict__ fields, SfDims dm, int64_t B,
     const int f = col ? t / Q : 0, d = col ? (t - f * Q) * 4 : 0;
     const rn_gcf xf = (rn_gcf)fields[f] + d;      // global address space: see common.hpp
     const int64_t FD = (int64_t)F * D;
-    int P = 1;                                             // threads per hidden unit in the first product (power of two <= 8)
-    while (P < 8 && 2 * P * SF_R * M <= 256) P *= 2;
+    const int P = sf_split(SF_R, M);                       // threads per hidden unit in the first product (power of two <= 8)
     // Round 5: the rows of step s + 1 are REQUESTED while step s runs its excitation (a second register set, unconditional loads from clamped
     // rows -- a load under a lane condition ends in a full wait at its merge, DESIGN.md 5e -- masked when used): a step was
     // load -> wait -> squeeze -> two small products -> scale -> store, strictly in series per workgroup (3.5 TB/s with eight workgroups per CU).
@@ -158,8 +164,7 @@ k_senet_fused_fwd8(const float* const* __restrict__ fields, SfDims dm, int64_t B
 #pragma unroll
     for (int p = 0; p < 8; ++p) fp[p] = (rn_gcf)fields[(p < NP ? 8 * p : 0) + 2 * w + fi] + 4 * q;
     const int64_t FD = (int64_t)F * D;
-    int P = 1;
-    while (P < 8 && 2 * P * S8_R * M <= 256) P *= 2;
+    const int P = sf_split(S8_R, M);
     sf_f4 vn[8];
     auto request = [&](int64_t r0) {
         const int64_t row = r0 + r < B ? r0 + r : B - 1;
@@ -263,8 +268,7 @@ k_senet_fused_bwd(const float* const* __restrict__ fields, float* const* __restr
     const rn_gf dxf = (rn_gf)dfields[f] + d;
     const int64_t FD = (int64_t)F * D;
     const int NOUT = 2 * FM + M + F;
-    int P = 1;                                             // threads per hidden unit in dz2 W2^T (power of two <= 8)
-    while (P < 8 && 2 * P * SF_R * M <= 256) P *= 2;
+    const int P = sf_split(SF_R, M);                       // threads per hidden unit in dz2 W2^T (power of two <= 8)
     // every weight-gradient output is sum_j a[j] * b[j] over the rows j of a step, a and b taken from the row vectors
     float acc[NACC];
     int pa[NACC], pb[NACC];                    // offsets into sf_lds (pointers would be generic: 64-bit, read with flat loads)
@@ -381,6 +385,67 @@ extern "C" size_t recnow_senet_fused_workspace_bytes(int64_t B, int F, int M) {
     return rn_align((size_t)sf_grid(B) * nout * sizeof(float)) + rn_colsum_ws_bytes(sf_grid(B), nout) + rn_align((size_t)nout * sizeof(float)) + 256;
 }
 
+// The choices of recnow_senet_fused_fwd / _bwd, stated once: the launchers launch what sf_plan returns and recnow_senet_fused_route / _grid answer
+// the same questions without a launch (tests/_senet_routes.py mirrors them).  Only for B > 0 and sf_ok(F, D, M).
+enum { SF_FWD4 = 1, SF_FWD8 = 2, SF_BWD = 3 };
+struct SfPlan {
+    int family;          // SF_FWD4: k_senet_fused_fwd, SF_FWD8: k_senet_fused_fwd8, SF_BWD: k_senet_fused_bwd<nacc>
+    int P;               // threads per hidden unit of the kernel's P-way product (sf_split)
+    int grant;           // forward: the dynamic LDS is over 64 KiB and needs rn_lds_grant
+    int nacc;            // backward: the NACC instantiation (3, 5, 9, 17, 34)
+    int grid;            // workgroups (the backward's is filled in by sf_bwd_grid: it asks the runtime for the occupancy)
+    size_t lds;          // dynamic LDS bytes
+};
+static SfPlan sf_plan(int which, int64_t B, int F, int D, int M, bool out_misaligned) {
+    SfPlan p = {SF_FWD4, sf_split(SF_R, M), 0, 0, sf_grid(B), sf_lds_floats(F, M) * sizeof(float)};
+    if (which == 0) {
+        if (sf8_ok(F, D, M) && !out_misaligned) {
+            p.family = SF_FWD8;
+            p.P = sf_split(S8_R, M);
+            p.lds = sf8_lds_floats(F, M) * sizeof(float);
+            p.grant = p.lds > 64 * 1024;
+            const int64_t g = (B + S8_R - 1) / S8_R;
+            p.grid = (int)(g > 2048 ? 2048 : g);
+        }
+        return p;
+    }
+    const int nout = 2 * F * M + M + F, need = (nout + 255) / 256;
+    p.family = SF_BWD;
+    p.nacc = need <= 3 ? 3 : need <= 5 ? 5 : need <= 9 ? 9 : need <= 17 ? 17 : 34;
+    p.lds = ((size_t)F * (M + 1) + (size_t)M * (F + 1) + 7 * SF_R * SF_RS) * sizeof(float);
+    return p;
+}
+static const void* sf_bwd_kernel(int nacc) {
+    switch (nacc) {
+        case 3: return (const void*)k_senet_fused_bwd<3>;
+        case 5: return (const void*)k_senet_fused_bwd<5>;
+        case 9: return (const void*)k_senet_fused_bwd<9>;
+        case 17: return (const void*)k_senet_fused_bwd<17>;
+        default: return (const void*)k_senet_fused_bwd<34>;
+    }
+}
+// one resident wave of workgroups (rows are grid-strided): every further workgroup costs a weight fill and a slab of partial sums that
+// the column sum reads back (as the DCNLayer backward): 0.85 -> 0.78 ms for the layer's step at B = 131 072; the forward measured the same either way
+static int sf_bwd_grid(const SfPlan& p) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, sf_bwd_kernel(p.nacc), 256, p.lds) != hipSuccess || occ < 1) occ = 1;
+    return p.grid > 256 * occ ? 256 * occ : p.grid;
+}
+
+extern "C" int recnow_senet_fused_route(int which, int64_t B, int F, int D, int M, int out_misaligned) {
+    if ((which != 0 && which != 1) || B < 0 || (out_misaligned != 0 && out_misaligned != 1)) return RECNOW_EINVAL;
+    if (!sf_ok(F, D, M)) return RECNOW_EUNSUPPORTED;
+    if (B == 0) return 0;
+    const SfPlan p = sf_plan(which, B, F, D, M, out_misaligned != 0);
+    return p.family * 100000 + (which == 0 ? p.P * 10 + p.grant : p.nacc);
+}
+extern "C" int recnow_senet_fused_grid(int which, int64_t B, int F, int D, int M, int out_misaligned) {
+    const int rc = recnow_senet_fused_route(which, B, F, D, M, out_misaligned);
+    if (rc <= 0) return rc;
+    const SfPlan p = sf_plan(which, B, F, D, M, out_misaligned != 0);
+    return which == 0 ? p.grid : sf_bwd_grid(p);
+}
+
 extern "C" int recnow_senet_fused_fwd(const float* const* fields, int F, int D, int64_t B, const float* W1, const float* b1,
                                       const float* W2, const float* b2, int M, int act1, int act2, float* out, float* sq_save,
                                       float* h_save, float* w_save, void* stream) {
@@ -388,17 +453,13 @@ extern "C" int recnow_senet_fused_fwd(const float* const* fields, int F, int D, 
     if (B == 0) return RECNOW_OK;
     if (!fields || !W1 || !W2 || !out || !sq_save || !h_save || !w_save) return RECNOW_EINVAL;
     const SfDims dm = {F, D, M, act1, act2, (b1 || b2) ? 1 : 0};
-    if (sf8_ok(F, D, M) && ((uintptr_t)out & 15) == 0) {
-        const size_t lds = sf8_lds_floats(F, M) * sizeof(float);
-        if (lds > 64 * 1024) RN_HIP(rn_lds_grant((const void*)k_senet_fused_fwd8, sf8_lds_floats(64, 64) * sizeof(float)));
-        int64_t g = (B + S8_R - 1) / S8_R;
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(k_senet_fused_fwd8, (int)g, 256, lds, (hipStream_t)stream, fields, dm, B, W1, b1, W2, b2, out, sq_save, h_save, w_save);
-        RN_LAUNCH_CHECK();
-        return RECNOW_OK;
+    const SfPlan p = sf_plan(0, B, F, D, M, ((uintptr_t)out & 15) != 0);
+    if (p.family == SF_FWD8) {
+        if (p.grant) RN_HIP(rn_lds_grant((const void*)k_senet_fused_fwd8, sf8_lds_floats(64, 64) * sizeof(float)));
+        hipLaunchKernelGGL(k_senet_fused_fwd8, p.grid, 256, p.lds, (hipStream_t)stream, fields, dm, B, W1, b1, W2, b2, out, sq_save, h_save, w_save);
+    } else {
+        hipLaunchKernelGGL(k_senet_fused_fwd, p.grid, 256, p.lds, (hipStream_t)stream, fields, dm, B, W1, b1, W2, b2, out, sq_save, h_save, w_save);
     }
-    hipLaunchKernelGGL(k_senet_fused_fwd, sf_grid(B), 256, sf_lds_floats(F, M) * sizeof(float), (hipStream_t)stream, fields, dm, B, W1,
-                       b1, W2, b2, out, sq_save, h_save, w_save);
     RN_LAUNCH_CHECK();
     return RECNOW_OK;
 }
@@ -420,29 +481,23 @@ extern "C" int recnow_senet_fused_bwd(const float* const* fields, float* const* 
     }
     if (!fields || !dfields || !W1 || !W2 || !dout || !sq_save || !h_save || !w_save || !dW1 || !dW2 || !ws) return RECNOW_EINVAL;
     if (ws_bytes < recnow_senet_fused_workspace_bytes(B, F, M)) return RECNOW_EWORKSPACE;
-    int nb = sf_grid(B);
+    const SfPlan p = sf_plan(1, B, F, D, M, false);
+    const int nb = sf_bwd_grid(p);
     RnCarver c(ws, ws_bytes);
-    float* part = c.take<float>((size_t)nb * nout);
+    float* part = c.take<float>((size_t)sf_grid(B) * nout);
     float* sums = c.take<float>((size_t)nout);
     void* cws = (void*)(c.base + c.off);
     const size_t cbytes = ws_bytes - c.off;
     const SfDims dm = {F, D, M, act1, act2, 0};
-    const size_t lds = ((size_t)F * (M + 1) + (size_t)M * (F + 1) + 7 * SF_R * SF_RS) * sizeof(float);
-    const int nacc = (nout + 255) / 256;
-    // one resident wave of workgroups (rows are grid-strided): every further workgroup costs a weight fill and a slab of partial sums that
-    // the column sum reads back (as the DCNLayer backward): 0.85 -> 0.78 ms for the layer's step at B = 131 072; the forward measured the same either way
-#define SF_BWD(NA) do {                                                                                                            \
-        int occ = 0;                                                                                                               \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_senet_fused_bwd<NA>, 256, lds) != hipSuccess || occ < 1) occ = 1; \
-        if (nb > 256 * occ) nb = 256 * occ;                                                                                        \
-        hipLaunchKernelGGL(k_senet_fused_bwd<NA>, nb, 256, lds, st, fields, dfields, dm, B, W1, W2, dout, sq_save, h_save, w_save, part); \
-    } while (0)
-    if (nacc <= 3) SF_BWD(3);
-    else if (nacc <= 5) SF_BWD(5);
-    else if (nacc <= 9) SF_BWD(9);
-    else if (nacc <= 17) SF_BWD(17);
-    else SF_BWD(34);
-#undef SF_BWD
+#define SF_BWD_LAUNCH(NA) hipLaunchKernelGGL(k_senet_fused_bwd<NA>, nb, 256, p.lds, st, fields, dfields, dm, B, W1, W2, dout, sq_save, h_save, w_save, part)
+    switch (p.nacc) {
+        case 3: SF_BWD_LAUNCH(3); break;
+        case 5: SF_BWD_LAUNCH(5); break;
+        case 9: SF_BWD_LAUNCH(9); break;
+        case 17: SF_BWD_LAUNCH(17); break;
+        default: SF_BWD_LAUNCH(34); break;
+    }
+#undef SF_BWD_LAUNCH
     RN_LAUNCH_CHECK();
     int rc = rn_colsum(part, nullptr, 0, 0, nb, nout, nout, sums, 0, cws, cbytes, st);
     if (rc) return rc;
@@ -452,3 +507,4 @@ extern "C" int recnow_senet_fused_bwd(const float* const* fields, float* const* 
     if (db2) RN_HIP(hipMemcpyAsync(db2, sums + 2 * FM + M, (size_t)F * sizeof(float), hipMemcpyDeviceToDevice, st));
     return RECNOW_OK;
 }
+

@@ -6,6 +6,12 @@ from ._keras import DenseBase, Layer, activation_code
 from ._ops import multi_dense
 
 
+def _aligned(t):
+    """t on a 16-byte boundary: the float4 kernels read the upstream gradient without testing its base pointer, and a contiguous view that starts a few
+    floats into a larger buffer (a slice of a concatenated gradient) passes f32c"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _Holder:
     """Per-call device arrays shared by the squeeze and scale nodes."""
 
@@ -59,6 +65,8 @@ class _SenetFunction(torch.autograd.Function):
         h, B = ctx.h, ctx.wd.shape[0]
         dev = ctx.wd.device
         dout = _lib.f32c(dout, 'grad')
+        if h.uniform:
+            dout = _aligned(dout)
         dw = torch.empty((B, h.F), dtype=torch.float32, device=dev)
         _lib.call('recnow_senet_scale_bwd_w', _lib.ptr(h.ptrs), _lib.ptr(h.dims), _lib.ptr(h.offs), h.F, h.total, B, _lib.ptr(dout),
                   _lib.ptr(dw), h.uniform, _lib.stream())
@@ -86,7 +94,7 @@ class _SenetFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, act1, act2, w1, b1, w2, b2, *fields):
-        xs = [_lib.f32c(x, 'SENET input') for x in fields]
+        xs = _lib.aligned_fields([_lib.f32c(x, 'SENET input') for x in fields], True)      # the fused kernels read float4 pieces of every field
         B, D = xs[0].shape
         F, M = len(xs), w1.shape[1]
         dev = xs[0].device
@@ -111,7 +119,7 @@ class _SenetFused(torch.autograd.Function):
         B, D = xs[0].shape
         F, M = len(xs), w1c.shape[1]
         dev = dout.device
-        dout = _lib.f32c(dout, 'grad')
+        dout = _aligned(_lib.f32c(dout, 'grad'))
         dx = torch.empty((F, B, D), dtype=torch.float32, device=dev)
         dw1, dw2 = torch.empty_like(w1c), torch.empty_like(w2c)
         db1 = torch.empty(M, dtype=torch.float32, device=dev) if has_b1 else None
@@ -202,7 +210,7 @@ class SENETLayer(DenseBase):
 
     def _fused_plan(self, inputs):
         """(act1, act2) codes when the one-kernel-per-direction path applies: equal widths inside the kernel's limits,
-        built-in activations, 16-byte aligned fp32 CUDA fields."""
+        built-in activations, fp32 CUDA fields (_SenetFused copies a field or an upstream gradient that is off a 16-byte boundary)."""
         d0, d1 = self.senet
         if d0.act_code is None or d1.act_code is None:
             return None

@@ -37,6 +37,20 @@ def test_route_queries_need_no_device():
     assert lib.recnow_fm_route(2, 64, 8, 16, 1) == -1 and lib.recnow_inner_pnn_route(0, 64, 8, 65, 0) == -3 and lib.recnow_attention_dot_route(0, 64, 50, 257, 0) == -3
 
 
+def test_senet_route_queries_need_no_device():
+    """ABI 35: the kernel choice and the grid of every SENET entry are host functions (tests/test_senet_census_cpu.py sweeps them)"""
+    from rec_now_amd import _lib
+    lib = _lib.load()
+    assert _lib.ABI_VERSION >= 35 and lib.recnow_abi_version() >= 35
+    assert lib.recnow_senet_route(0, 0, 3, 6, 0) == 0 and lib.recnow_senet_fused_route(0, 0, 8, 16, 4, 0) == 0
+    assert lib.recnow_senet_route(0, 7, 3, 6, 0) == 100032 and lib.recnow_senet_route(3, 7, 65, 260, 4) == 200001 and lib.recnow_senet_route(1, 7, 2, 12288, 0) == -3
+    assert lib.recnow_senet_grid(2, 131109, 3, 6, 0) == 4096 and lib.recnow_senet_grid(0, 7, 65, 260, 4) == 1
+    assert lib.recnow_senet_fused_route(0, 64, 8, 16, 4, 0) == 200080 and lib.recnow_senet_fused_route(0, 64, 8, 16, 4, 1) == 100080
+    assert lib.recnow_senet_fused_route(0, 64, 64, 16, 64, 0) == 200011 and lib.recnow_senet_fused_route(1, 64, 14, 4, 26, 0) == 300003
+    assert lib.recnow_senet_fused_route(1, 64, 64, 4, 64, 0) == 300034 and lib.recnow_senet_fused_grid(0, 16395, 8, 16, 4, 0) == 2048
+    assert lib.recnow_senet_route(4, 7, 3, 6, 0) == -1 and lib.recnow_senet_fused_route(2, 64, 8, 16, 4, 0) == -1 and lib.recnow_senet_fused_route(0, 64, 65, 16, 4, 0) == -3
+
+
 def test_cpu_tensor_is_refused_loudly():
     import pytest
     import torch
